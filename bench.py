@@ -17,8 +17,14 @@ per trial; the median of the trials' ratios is reported.
 Steps run as hipGraph replays — G = --graph-steps steps (default 20) per captured graph, K/G replays per
 timed trial; --trials trials of exactly K steps (median reported), each replay also timed by HIP events —
 and noise is in-kernel Philox (perf mode).
-Also reported in the same line: acceptance rate (engine/metrics.py:123-129) over >= 200 untimed
-steps, per-kernel timings with the HBM roofline of the step's DOMINANT kernel (the largest
+
+A plain run (--gpus N --steps K --warmup W) sets up, runs W eager warm-up steps, captures the graph,
+times ONE trial of K steps, writes the last step's outputs when --dump-outputs DIR is given, and prints
+the result line: value, ms_per_step (the timed trial's wall time / K), the timed steps' own
+acceptance rate and the per-replay event times.  Nothing else runs.
+
+With --full the timed part is 5 trials, and the same line also reports, each from runs of its
+own after the timed part: acceptance rate (engine/metrics.py:123-129) over >= 200 untimed steps, per-kernel timings with the HBM roofline of the step's DOMINANT kernel (the largest
 per-step share; HIP events on the launch stream, algorithmic bytes = every logit row the kernel
 must read, once), the same step in STREAM mode (the reference's torch-generator noise, bit-exact
 tokens, in a noise session as the drop-in engine runs it), the strong-scaling variant of
@@ -27,7 +33,7 @@ shards measured on one GPU when N = 1, the configs[1] batch-1 step latencies, th
 n-gram verify step, and the CPU baseline = the oracle (reference semantics, torch-CPU) timed on a
 bounded sample of the same workload on this host.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -71,10 +77,18 @@ def parse():
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip the end-to-end line (random-init Llama-3-8B / 3.2-1B shaped models, drop-in engine)")
     ap.add_argument("--e2e-gen", type=int, default=64, help="new tokens per row in the end-to-end line")
-    ap.add_argument("--trials", type=int, default=5,
-                    help="timed trials of exactly --steps steps each (median reported)")
+    ap.add_argument("--trials", type=int, default=None,
+                    help="timed trials of exactly --steps steps each (median reported); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, everything else the line reports: 5 timed trials, the untimed "
+                         "acceptance sample, per-kernel / roofline timings, STREAM mode, shards, the large-batch "
+                         "sweep, configs[1] / [4], the end-to-end line and the CPU baseline (each with its --no-* "
+                         "switch); N > 1: the strong-scaling variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (draft tokens, their rows' statistics and the "
+                         "verify's per-row outputs) as DIR/<name>.npy")
     ap.add_argument("--profile-only", action="store_true",
-                    help="only the B-row engine step (no shards, configs[1]/[4], STREAM or CPU lines): every "
+                    help="--full without the shard, sweep, configs[1]/[4], STREAM, end-to-end and CPU lines: every "
                          "sd:: launch of the run has the headline shape, for rocprofv3 / PMC passes")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="dispatch option for A/B runs (sd_set_option), e.g. FUSED_VERIFY=0 or LEAN_VERIFY=0")
@@ -83,9 +97,12 @@ def parse():
     a = ap.parse_args()
     a.sweep_batches = [int(x) for x in a.sweep_batches.split(",") if x.strip()]
     if a.profile_only:
+        a.full = True
         a.no_cpu_baseline = a.no_configs1 = a.no_shards = a.no_e2e = True
         a.stream_steps = 0
         a.sweep_batches = []
+    if a.trials is None:
+        a.trials = 5 if a.full else 1
     return a
 
 
@@ -226,6 +243,27 @@ def kernel_events(fn, repeat, n_pairs):
     return sum(ts) / len(ts)
 
 
+def dump_outputs(path, step, out, rank):
+    """--dump-outputs: what a caller of the timed step receives from its last run — the γ draws' tokens
+    and row statistics and every per-row output of the verify — one .npy each (integers as float64,
+    exact for token ids; floats as float32), a few KiB in all.  resample_mass is NaN by contract in
+    the rows that formed no residual (include/specdec.h); those are written as -1 (a mass is >= 0), so
+    every array compares with plain equality.  The logits, the Philox seed and the count of launches
+    before the last step depend on the arguments alone, so two builds run with the same arguments can
+    be compared array for array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"draft_tokens": step.draft, "draft_row_stats": step.dstats}
+    arrays.update({f: getattr(out, f) for f in type(out).__dataclass_fields__})
+    mass = arrays["resample_mass"]
+    arrays["resample_mass"] = torch.where(mass.isnan(), torch.full_like(mass, -1.0), mass)
+    tag = f".rank{rank}" if rank else ""
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        np.save(os.path.join(path, f"{name}{tag}.npy"),
+                t.to(torch.float32 if t.is_floating_point() else torch.float64).numpy())
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -289,6 +327,47 @@ def main():
     value = trial_rate[mid]
     elapsed = trial_s[mid]
     rsum_t, rcnt_t = positive_rate_sums(acc_t, g * args.steps * n_trials)
+    ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:   # the last timed step's outputs, before anything else replays the graph
+        dump_outputs(args.dump_outputs, step, outs[-1], rank)
+    _, tot_t = dp.aggregate(elapsed, {"rate_sum_t": rsum_t, "rate_cnt_t": rcnt_t}, dev, dist)
+    line = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "tokens/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic (target logits ~ N(0,3^2), drafter = target + N(0,1), draft ids sampled from the drafter)",
+        "config": {"workload": "configs[2]: Llama-3-8B/3.2-1B logit shapes, engine step sampling path: "
+                               "γ drafter draws + verify (rule A10)",
+                   "rows_per_gpu": args.batch, "global_batch": args.batch * world, "gamma": g, "vocab": V,
+                   "parallelism": f"dp{world}", "noise": "philox", "graph_steps": G, "replays_per_trial": replays,
+                   "trials": n_trials, "verify_path": _lib.PATH_NAMES.get(verify_path, str(verify_path))},
+        # engine/metrics.py:123-129: mean of per-row acc/tot over the rows with a positive rate (the timed steps)
+        "acceptance_rate_timed": tot_t["rate_sum_t"] / tot_t["rate_cnt_t"] if tot_t["rate_cnt_t"] else 0.0,
+        "tokens_timed": trial_tok[mid],
+        "replays": {"count": replays * n_trials, "steps_per_replay": G,
+                    "ms_median": statistics.median(replay_ms), "ms_min": min(replay_ms),
+                    "ms_max": max(replay_ms),
+                    "ms_per_step_median": statistics.median(replay_ms) / G,
+                    "trial_ms_per_step": [t / args.steps * 1e3 for t in trial_s],
+                    "trial_tokens_per_s": trial_rate,
+                    "note": "HIP events between back-to-back replays of the captured steps (rank 0); "
+                            "trial_ms_per_step: each trial's wall time / K; value = the median trial's "
+                            "tokens / its time (ms_per_step is that trial's)"},
+    }
+    if not args.full:   # the plain run ends here: the headline figure and nothing that takes runs of its own
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # acceptance over a larger untimed sample (>= 200 steps of the same graph, fresh noise each)
     n_count = max(1, -(-max(200, args.steps) // G))
@@ -303,7 +382,6 @@ def main():
 
     _, tot = dp.aggregate(elapsed, {"accepted": float(acc_t.sum()),
                                           "drafted": B * g * args.steps * n_trials, "rate_sum": rsum, "rate_cnt": rcnt,
-                                          "rate_sum_t": rsum_t, "rate_cnt_t": rcnt_t,
                                           "accepted_c": float(counts_c[:, 0].sum()),
                                           "drafted_c": B * g * G * n_count}, dev, dist)
 
@@ -325,7 +403,6 @@ def main():
     torch.cuda.synchronize()
     stats_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev) / PROF_REPEAT
     sample_ms = max(verify_ms - stats_ms, 0.0)
-    ms_per_step = elapsed / args.steps * 1e3
     row_bytes = B * V * 2
     kernels = {
         # per launch: algorithmic bytes = each logit row the kernel must read, once
@@ -410,40 +487,12 @@ def main():
         dk = kernels[dominant]
         step_bytes = B * 2 * g * V * 2          # the step: every target and drafter row once
         step_gbs = step_bytes / (ms_per_step * 1e-3) / 1e9
-        line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "tokens/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": "synthetic (target logits ~ N(0,3^2), drafter = target + N(0,1), draft ids sampled from the drafter)",
-            "config": {"workload": "configs[2]: Llama-3-8B/3.2-1B logit shapes, engine step sampling path: "
-                                   "γ drafter draws + verify (rule A10)",
-                       "rows_per_gpu": args.batch, "global_batch": args.batch * world, "gamma": g, "vocab": V,
-                       "parallelism": f"dp{world}", "noise": "philox", "graph_steps": G, "replays_per_trial": replays,
-                       "trials": n_trials, "verify_path": _lib.PATH_NAMES.get(verify_path, str(verify_path))},
+        line.update({
             # engine/metrics.py:123-129: mean of per-row acc/tot over the rows with a positive rate,
             # over >= 200 untimed steps of the same graph (the timed steps' own figure beside it)
             "acceptance_rate": tot["rate_sum"] / tot["rate_cnt"] if tot["rate_cnt"] else 0.0,
             "acceptance_rate_pooled": tot["accepted_c"] / tot["drafted_c"],
             "acceptance_steps": G * n_count,
-            "acceptance_rate_timed": tot["rate_sum_t"] / tot["rate_cnt_t"] if tot["rate_cnt_t"] else 0.0,
-            "tokens_timed": trial_tok[mid],
-            "replays": {"count": replays * n_trials, "steps_per_replay": G,
-                        "ms_median": statistics.median(replay_ms), "ms_min": min(replay_ms),
-                        "ms_max": max(replay_ms),
-                        "ms_per_step_median": statistics.median(replay_ms) / G,
-                        "trial_ms_per_step": [t / args.steps * 1e3 for t in trial_s],
-                        "trial_tokens_per_s": trial_rate,
-                        "note": "HIP events between back-to-back replays of the captured steps (rank 0); "
-                                "trial_ms_per_step: each trial's wall time / K; value = the median trial's "
-                                "tokens / its time (ms_per_step is that trial's)"},
             "roofline": {"bound": "hbm", "achieved": dk["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": dk["frac"], "traffic": traffic,
                          "kernel": dominant, "kernel_ms": dk["ms"], "launches_per_step": dk["launches_per_step"],
@@ -461,7 +510,7 @@ def main():
             "configs4": cfg4,
             "e2e": e2e,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -1,16 +1,17 @@
 #!/bin/bash
-# Copy a gpu_round.sh run's evidence from gpurun_out/ into profiles/ under a round tag.
+# Copy a gpu_round.sh run's evidence from $OUT (default: bench_out/) into profiles/ under a round tag.
 # usage: scripts/save_round.sh r4a
 set -e
 TAG=$1
 cd "$(dirname "$0")/.."
-cp gpurun_out/prof/run_kernel_stats.csv profiles/${TAG}_kernel_stats_profile_only.csv
-python scripts/trace_summary.py gpurun_out/prof profiles/${TAG}_kernel_trace_by_shape.csv > /dev/null
-[ -f gpurun_out/prof.json ] && cp gpurun_out/prof.json profiles/${TAG}_prof_bench.json
-[ -f gpurun_out/bench.json ] && cp gpurun_out/bench.json profiles/${TAG}_bench.json
-[ -f gpurun_out/gpu_tests.log ] && tail -3 gpurun_out/gpu_tests.log > profiles/${TAG}_gpu_tests.txt
-[ -f gpurun_out/ngs_timing.json ] && cp gpurun_out/ngs_timing.json profiles/${TAG}_ngram_store_timing.json
-python scripts/pmc_summary.py gpurun_out ${TAG} engine_b32_g4_v128256 > /dev/null
+OUT=${OUT:-bench_out}
+cp $OUT/prof/run_kernel_stats.csv profiles/${TAG}_kernel_stats_profile_only.csv
+python scripts/trace_summary.py $OUT/prof profiles/${TAG}_kernel_trace_by_shape.csv > /dev/null
+[ -f $OUT/prof.json ] && cp $OUT/prof.json profiles/${TAG}_prof_bench.json
+[ -f $OUT/bench.json ] && cp $OUT/bench.json profiles/${TAG}_bench.json
+[ -f $OUT/gpu_tests.log ] && tail -3 $OUT/gpu_tests.log > profiles/${TAG}_gpu_tests.txt
+[ -f $OUT/ngs_timing.json ] && cp $OUT/ngs_timing.json profiles/${TAG}_ngram_store_timing.json
+python scripts/pmc_summary.py $OUT ${TAG} engine_b32_g4_v128256 > /dev/null
 python - "$TAG" <<'PY'
 import csv, json, sys
 tag = sys.argv[1]
