@@ -282,9 +282,13 @@ const char* sd_last_hip_error(void);   /* hipGetErrorString of the last failed l
  * reads the environment (SD_POLL / SD_POLL_SPIN_LIMIT seed the poll policy once, at first use).
  * sd_set_option returns SD_ERR_INVALID for an unknown option or value.                        */
 typedef enum {
-    SD_OPT_FUSED_VERIFY = 1,    /* 1 (default): k_verify_fused for B >= 8; 2: any B; 0: never    */
+    SD_OPT_FUSED_VERIFY = 1,    /* 1 (default): k_verify_fused for B >= 8; 2: any B; 0: never.
+                                   Whatever the value, only calls with at most 17 target rows
+                                   (gamma <= 16 under SD_RULE_SPEC, <= 17 under SD_RULE_ENGINE):
+                                   longer windows take k_stats + k_sample                         */
     SD_OPT_LEAN_VERIFY = 2,     /* -1 (default): k_verify_lean for <= 8 sequences; 1: any batch
-                                   the occupancy check admits; 0: never                           */
+                                   the occupancy check admits; 0: never.  Whatever the value, only
+                                   gamma <= 8 and 16-byte aligned 16-bit rows                     */
     SD_OPT_THRESHOLD_POLL = 3,  /* 1 (default): the top-k / nucleus search in one launch when its
                                    grid is resident; 0: the launch-per-phase design               */
     SD_OPT_DRAW_STREAM = 4,     /* 1 (default): STREAM multinomial draws in one pass
@@ -309,8 +313,8 @@ int32_t sd_get_option(int32_t option, int32_t* value);
  * bench can tell which kernel it measured without reading the dispatch rules).                 */
 typedef enum {
     SD_PATH_NONE = 0,
-    SD_PATH_VERIFY_LEAN = 1,        /* k_verify_lean: one launch, <= 8 sequences                 */
-    SD_PATH_VERIFY_FUSED = 2,       /* k_verify_fused: one launch                                 */
+    SD_PATH_VERIFY_LEAN = 1,        /* k_verify_lean: one launch, <= 8 sequences, gamma <= 8     */
+    SD_PATH_VERIFY_FUSED = 2,       /* k_verify_fused: one launch, <= 17 target rows              */
     SD_PATH_VERIFY_TWO_LAUNCH = 3,  /* k_stats (+ decider) then k_sample                          */
     SD_PATH_VERIFY_STREAM = 4,      /* STREAM: k_stats, k_decide, k_walk, k_resample, k_finalize  */
     SD_PATH_VERIFY_FUSED_TICKET = 5,/* k_verify_fused in ticket order (ABI 11): one launch, any B  */

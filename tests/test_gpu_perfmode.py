@@ -19,8 +19,8 @@ import numpy as np
 import pytest
 import torch
 
-import philox_ref as ph
 from oracle import specdec_ref as ref
+from perf_walk import flip_slack, host_walk_engine, host_walk_spec
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -95,14 +95,6 @@ def expect_path(sd, out, B, draws, stochastic=True):
     assert out.path in want, sd.lib.PATH_NAMES.get(out.path)
 
 
-def flip_slack(logits_row, dtype):
-    """Σ over the row's elements of how far its rounded probability can move when the softmax
-    normaliser is off by 1e-6 (relative): the exact fp64 value, scaled by 1 ± 1e-6, rounded to the
-    row's dtype both ways."""
-    v = torch.softmax(logits_row.double(), dim=-1)
-    return float(((v * (1 + 1e-6)).to(dtype).double() - (v * (1 - 1e-6)).to(dtype).double()).sum())
-
-
 def chi2_check(samples, probs, label):
     """Pearson chi-square of integer samples against probabilities (bins with expected < 5 pooled)."""
     from scipy.stats import chisquare
@@ -126,35 +118,6 @@ def chi2_check(samples, probs, label):
 
 
 # ---------------------------------------------------------------- accept walk
-def host_walk_spec(p, q, seed, off, b, g):
-    """sampling/speculative_decoding.py:139-145 on Philox uniforms: n, and whether any comparison
-    sat within fp32 rounding of the threshold (then the device may legitimately differ)."""
-    n, close = g, False
-    for i in range(g):
-        r = ph.accept_uniform(seed, off, b, i)
-        frac = np.float32(p[i]) / np.float32(q[i]) if q[i] != 0 else np.float32(np.inf if p[i] > 0 else np.nan)
-        close |= bool(abs(float(r) - float(frac)) <= 1e-6 * max(1.0, float(frac)))
-        if r > frac and n == g:
-            n = i
-    return n, close
-
-
-def host_walk_engine(p, q, toks, ends, seed, off, b, g):
-    """engine/infer_engine.py:297-330 on Philox uniforms: (n, rejected, finished, close)."""
-    n, close = 0, False
-    for i in range(g):
-        u = float(ph.accept_uniform(seed, off, b, i))
-        ap = 1.0 if q[i] <= 0 else min(1.0, float(p[i]) / float(q[i]))
-        close |= abs(u - ap) <= 1e-6
-        if u < ap:
-            n += 1
-            if int(toks[i]) in ends:
-                return n, False, True, close
-        else:
-            return n, True, False, close
-    return n, False, False, close
-
-
 @pytest.mark.parametrize("draws", [False, True], ids=["stats-in-verify", "stats-from-draws"])
 @pytest.mark.parametrize("kind,V,B,dtype", [("multi_t1", 4096, 64, torch.bfloat16),
                                             ("multi_t07", 4096, 16, torch.float32),
