@@ -313,12 +313,17 @@ __global__ void __launch_bounds__(1024) k_ngram_finalize(Plan P) {
 
 namespace {
 
-template <int DT>
-int32_t launch_ngram_rows_dt(const sd::Plan& P, void* stream) {
-    const dim3 grid(P.rn_chunks, P.B * P.slots);
-    if (P.noise.mode == SD_NOISE_STREAM) SD_LAUNCH((sd::k_ngram_rows<DT, SD_NOISE_STREAM>), grid, dim3(sd::kThreads), stream, P);
-    else SD_LAUNCH((sd::k_ngram_rows<DT, SD_NOISE_PHILOX>), grid, dim3(sd::kThreads), stream, P);
-    return SD_OK;
+// one pass: every row's candidates and filler ids (k_ngram_rows), then the walk (k_ngram_finalize)
+int32_t launch_ngram_pass(const sd::Plan& P, void* stream) {
+    const int32_t st = dispatch_dtype(P.tdt, [&](auto dt_) {
+        return dispatch_int<SD_NOISE_STREAM, SD_NOISE_PHILOX>(P.noise.mode, [&](auto nz_) {
+            return launch(sd::k_ngram_rows<decltype(dt_)::value, decltype(nz_)::value>, dim3(P.rn_chunks, P.B * P.slots),
+                          dim3(sd::kThreads), 0, stream, P);
+        });
+    });
+    if (st != SD_OK) return st;
+    const dim3 fin_block(sd::kWave * (P.slots < 16 ? P.slots : 16));
+    return launch(sd::k_ngram_finalize, dim3(P.B), fin_block, 0, stream, P);
 }
 
 void carve_ngram(sd::Plan& P, Carve& c, int B, int gamma, int vocab) {
@@ -353,11 +358,9 @@ int32_t sd_ngram_verify(const sd_ngram_args* a, void* stream) {
     if (a->workspace_bytes < sd_ngram_workspace_size(a->batch, a->gamma, a->vocab) || !a->workspace)
         return SD_ERR_WORKSPACE;
     sd::Plan P{};
-    P.B = a->batch; P.gamma = a->gamma; P.V = a->vocab; P.rule = -1;
-    P.n_tslots = a->gamma + 1; P.n_dslots = 0; P.slots = P.n_tslots; P.stat_slots = P.slots;
-    P.tdt = a->target_dtype; P.ddt = a->target_dtype;
-    P.t_keep = needs_keep(a->proc); P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
-    P.tT = a->proc.temperature; P.dT = 1.f;
+    plan_rows(P, a->batch, a->gamma + 1, a->vocab, a->target_dtype, a->proc);
+    P.gamma = a->gamma;
+    P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
     for (int t = 0; t <= a->gamma; ++t) P.trow[t] = a->target_rows[t];
     P.tstride = a->target_stride_b;
     P.draft_tokens = a->draft_tokens; P.tok_stride = a->draft_tokens_stride_b;
@@ -370,7 +373,6 @@ int32_t sd_ngram_verify(const sd_ngram_args* a, void* stream) {
     P.filler_pass = 0;
     P.filler_kp = a->filler_k < sd::kNgMaxK ? a->filler_k : sd::kNgMaxK;
     P.status_or = a->status_or;
-    P.spin_limit = spin_limit();
     set_stats_chunks(P, P.B * P.slots);
     Carve c{static_cast<char*>(a->workspace)};
     carve_ngram(P, c, a->batch, a->gamma, a->vocab);
@@ -380,23 +382,13 @@ int32_t sd_ngram_verify(const sd_ngram_args* a, void* stream) {
     }
     set_rchunks(P);
     if (int32_t st = launch_stats(P, stream)) return st;
-    int32_t st;
-    if (P.tdt == SD_BF16) st = launch_ngram_rows_dt<SD_BF16>(P, stream);
-    else if (P.tdt == SD_F32) st = launch_ngram_rows_dt<SD_F32>(P, stream);
-    else st = launch_ngram_rows_dt<SD_F16>(P, stream);
-    if (st != SD_OK) return st;
-    const dim3 fin_block(sd::kWave * (P.slots < 16 ? P.slots : 16));
-    SD_LAUNCH(sd::k_ngram_finalize, dim3(P.B), fin_block, stream, P);
+    if (int32_t st = launch_ngram_pass(P, stream)) return st;
     // filler ids beyond kNgMaxK: one more (rows, finalize) pair per kNgMaxK ids, each starting after
     // the previous pass's last pick
     for (int q = 1; q * sd::kNgMaxK < P.filler_k; ++q) {
         P.filler_pass = q;
         P.filler_kp = P.filler_k - q * sd::kNgMaxK < sd::kNgMaxK ? P.filler_k - q * sd::kNgMaxK : sd::kNgMaxK;
-        if (P.tdt == SD_BF16) st = launch_ngram_rows_dt<SD_BF16>(P, stream);
-        else if (P.tdt == SD_F32) st = launch_ngram_rows_dt<SD_F32>(P, stream);
-        else st = launch_ngram_rows_dt<SD_F16>(P, stream);
-        if (st != SD_OK) return st;
-        SD_LAUNCH(sd::k_ngram_finalize, dim3(P.B), fin_block, stream, P);
+        if (int32_t st = launch_ngram_pass(P, stream)) return st;
     }
     return SD_OK;
 }

@@ -1086,26 +1086,23 @@ int32_t launch_threshold(const sd::Plan& P, const sd_processor& tproc, const sd_
     const int nsl = (P.V + sd::kThrSlice - 1) / sd::kThrSlice;
     const bool fast16 = w16 && nsl <= sd::kThrMaxSlices && rows <= sd::kCntMax;
     if (fast16) {
-        const dim3 grid(nsl, rows);
+        const dim3 grid(nsl, rows), block(sd::kThrThreads);
         // the slice maxima exchanged inside k_thr_hist (polled records) when its whole grid is
         // resident; otherwise k_thr_max computes them in a launch of its own
         sd::Plan Q = P;
         Q.thr_poll = thr_poll_ok((int64_t)nsl * rows);
         if (!Q.thr_poll)
-            hipLaunchKernelGGL(sd::k_thr_max, grid, dim3(sd::kThrThreads), 0, (hipStream_t)stream, Q, tt, td);
-        hipLaunchKernelGGL(sd::k_thr_hist, grid, dim3(sd::kThrThreads), 0, (hipStream_t)stream, Q, tt, td);
+            if (int32_t st = launch(sd::k_thr_max, grid, block, 0, stream, Q, tt, td)) return st;
+        if (int32_t st = launch(sd::k_thr_hist, grid, block, 0, stream, Q, tt, td)) return st;
         // tie searches, and the radix descent of the rows k_thr_hist handed over (first workgroup) —
         // both inside k_thr_hist in poll mode
         if (!Q.thr_poll)
-            hipLaunchKernelGGL(sd::k_thr_tie, grid, dim3(sd::kThrThreads), 0, (hipStream_t)stream, P, tt, td);
+            if (int32_t st = launch(sd::k_thr_tie, grid, block, 0, stream, P, tt, td)) return st;
     }
     // fp32 rows and 16-bit rows beyond the histogram kernels' limits: the radix descent
     const bool any32 = (P.t_keep && P.tdt == SD_F32) || (d_rows && P.d_keep && P.ddt == SD_F32);
     if (any32 || (w16 && !fast16))
-        hipLaunchKernelGGL(sd::k_threshold, dim3(rows), dim3(sd::kThreshThreads), 0, (hipStream_t)stream,
-                           P, tt, td, w16 && !fast16 ? 1 : 0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_error = e; return SD_ERR_LAUNCH; }
+        return launch(sd::k_threshold, dim3(rows), dim3(sd::kThreshThreads), 0, stream, P, tt, td, w16 && !fast16 ? 1 : 0);
     return SD_OK;
 }
 }  // namespace

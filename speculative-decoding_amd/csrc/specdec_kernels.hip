@@ -3,22 +3,28 @@
 // One verify step (sd_verify) is a short chain of memory-bound kernels on one stream,
 // with no host sync and no allocation.
 //
-// PHILOX (perf) mode — two launches:
-//   k_stats<TAIL>   grid (span, row): per-span max / Σexp of the processed row -> partials.
-//                   The last workgroup of each sequence (agent-scope counter) then decides it:
-//                   row stats, p(x_i)/q(x_i), the accept walk -> Decision, prune lengths.
-//   k_sample        grid (chunk, B): per-chunk Σ weight of the row to sample — (p_n - q_n)+
-//                   (residual) or p (bonus / p-row) — then the last workgroup of each sequence
-//                   draws the token by inverse CDF (fp64 scan inside one chunk), writes the
-//                   outputs and applies the engine state.  Greedy rows take an exact argmax.
+// k_threshold (top-k / nucleus rows whose keep predicates did not come with the draws) runs first.
+//
+// PHILOX (perf) mode, first path that applies:
+//   k_verify_lean    (sd_verify_lean.inc) at most 8 sequences: spans, decision and sampling of a
+//                    sequence in one launch whose whole grid is resident.
+//   k_verify_fused   from 8 sequences, stochastic target rows, the drafter statistics from the
+//                    draws: spans, a decider and samplers per sequence in one launch, in block-id
+//                    order or, for large or non-resident grids, ticket order.
+//   k_stats<TAIL> + k_sample  the two-launch fallback: row statistics with the decision in each
+//                    sequence's last workgroup, then the per-chunk weights and the inverse-CDF draw
+//                    in the last sampling workgroup.
 //
 // STREAM (parity) mode keeps the reference's serial noise order:
 //   k_stats -> k_decide (grid B) -> k_walk (serial over rows) -> k_resample (exponential race
 //   with exact candidates, torch's own words) -> k_finalize.
 //
-// k_threshold (top-k / nucleus rows only) runs first in both modes.  Every logit row is read
-// once by k_stats (the algorithmic bytes); the sampling pass re-reads at most two rows per
-// sequence (served from the 256 MiB Infinity Cache).  See DESIGN.md.
+// Draws (sd_sample), first path that applies: the nucleus draw by rejection (k_draw_nuc), PHILOX
+// k_draw_lean / k_draw, STREAM k_draw_stream, greedy k_draw_lean<GREEDY>, then the three launches
+// k_stats + k_rowsample + k_sample_finalize.
+//
+// Every logit row is read once by the statistics pass (the algorithmic bytes); the sampling pass
+// re-reads at most two rows per sequence (served from the 256 MiB Infinity Cache).  See DESIGN.md.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -145,6 +151,11 @@ struct Plan {
     int32_t filler_pass;    // filler top-K in passes of kNgMaxK: this launch's pass (> 0: filler only)
     int32_t filler_kp;      //   ids this pass selects, <= kNgMaxK
     float2* ng_thr;         //   per row: the last id the previous pass took (value, index bits)
+
+    // host: the FAST kernels' case, T == 1 and no top-k / nucleus mask (plain softmax) — on both
+    // sides (the engine rule), or on the target side alone
+    bool fast() const { return tT == 1.0f && dT == 1.0f && !t_keep && !d_keep; }
+    bool t_fast() const { return tT == 1.0f && !t_keep; }
 };
 
 // Phase timestamps (diagnostic builds, -DSD_PHASE_TIMING): thread 0 of workgroup `wg` records
@@ -3614,6 +3625,31 @@ int spin_limit() {
     return g_spin_limit.load(std::memory_order_relaxed);
 }
 int resident_cap(const void* kern, int threads = sd::kThreads, size_t dyn = 0);
+
+// Every launch of the library: SD_OK, or SD_ERR_LAUNCH with the error recorded — the caller returns
+// it at once and starts nothing after it.
+template <typename K, typename... A>
+int32_t launch(K kern, dim3 grid, dim3 block, size_t dyn_lds, void* stream, const A&... args) {
+    hipLaunchKernelGGL(kern, grid, block, (unsigned)dyn_lds, (hipStream_t)stream, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_last_error = e; return SD_ERR_LAUNCH; }
+    return SD_OK;
+}
+
+// Runtime value -> template argument: f(std::integral_constant<int, V>{}) for the V of the pack
+// that equals v; the last of the pack takes every other value (the else branch of a ladder).
+template <int V0, int... VS, typename F>
+auto dispatch_int(int v, F&& f) {
+    if constexpr (sizeof...(VS) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<VS...>(v, f);
+}
+template <typename F>
+auto dispatch_dtype(int dt, F&& f) { return dispatch_int<SD_BF16, SD_F32, SD_F16>(dt, f); }
+// the kernels without fp32 variants (the caller has excluded SD_F32)
+template <typename F>
+auto dispatch_dtype16(int dt, F&& f) { return dispatch_int<SD_BF16, SD_F16>(dt, f); }
+template <typename F>
+auto dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 }  // namespace
 
 #include "sd_threshold.inc"
@@ -3693,45 +3729,30 @@ void set_stats_chunks(sd::Plan& P, int rows, int target_wgs = 2048, int min_stag
     P.n_chunks = (P.V + P.chunk - 1) / P.chunk;
 }
 
-// Resample / sample passes: 1 or 2 stages of 2048 elements per workgroup, about 1024 workgroups so
-// the whole grid is resident at once (these kernels carry more SGPRs, so fewer blocks fit per CU).
+// Resample / sample passes: one stage of 2048 elements per workgroup (measured: 2 stages, 116 VGPRs
+// and 4 waves/SIMD, ran 1.8x slower than 1 stage at 8)
 void set_rchunks(sd::Plan& P) {
-    const int64_t stage = kThreads * kEptSmall;
-    int64_t per_wg = ((int64_t)P.B * ((P.V + stage - 1) / stage) + 1023) / 1024;
-    per_wg = 1;   // measured: 2 stages (116 VGPRs, 4 waves/SIMD) ran 1.8x slower than 1 stage at 8
-    P.rchunk = (int32_t)(per_wg * stage);
+    P.rchunk = kThreads * kEptSmall;
     P.rn_chunks = (P.V + P.rchunk - 1) / P.rchunk;
 }
 
-int32_t launch_stats(const sd::Plan& P, void* stream, bool tail = false);
+// What the Plans of the calls without a drafter share (sd_sample, sd_probs, sd_ngram_verify): B
+// sequences of `slots` target rows each under one processor, no acceptance rule, the poll bound
+void plan_rows(sd::Plan& P, int B, int slots, int vocab, int dtype, const sd_processor& proc) {
+    P.B = B; P.V = vocab; P.rule = -1;
+    P.n_tslots = slots; P.n_dslots = 0; P.slots = slots; P.stat_slots = slots;
+    P.tdt = dtype; P.ddt = dtype;
+    P.t_keep = needs_keep(proc);
+    P.tT = proc.temperature; P.dT = 1.f;
+    P.spin_limit = spin_limit();
+}
 
-#define SD_LAUNCH(kern, grid, block, stream, ...)                                             \
-    do {                                                                                      \
-        hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, __VA_ARGS__);            \
-        const hipError_t e_ = hipGetLastError();                                              \
-        if (e_ != hipSuccess) { g_last_error = e_; return SD_ERR_LAUNCH; }                    \
-    } while (0)
+int32_t launch_stats(const sd::Plan& P, void* stream, bool tail = false);
 
 // errors left behind by earlier, unrelated runtime calls must not be blamed on our launches
 inline void clear_stale_error() { (void)hipGetLastError(); }
 
 bool sample_poll_ok(int B, const void* kern);
-
-template <int DT, bool TAIL>
-int32_t launch_stats_dt(const sd::Plan& P, bool fast, int slot_lo, int slot_cnt, void* stream) {
-    const dim3 grid(P.n_chunks, P.B * slot_cnt);
-    // poll-mode decide tail: the drafter stats came with the draws (target slots only, one launch)
-    sd::Plan Q = P;
-    Q.kpoll = TAIL && P.dstats && P.n_chunks <= kWave && P.stat_slots == P.n_tslots &&
-              P.n_tslots <= sd::kFastSlots && slot_lo == 0 &&
-              slot_cnt == P.stat_slots &&
-              sample_poll_ok(P.B, fast ? (const void*)k_stats<DT, true, TAIL> : (const void*)k_stats<DT, false, TAIL>);
-    // poll mode: a 1-D grid with one decider workgroup per sequence after its spans (k_stats)
-    const dim3 g2 = Q.kpoll ? dim3(P.B * (slot_cnt * P.n_chunks + 1)) : grid;
-    if (fast) SD_LAUNCH((k_stats<DT, true, TAIL>), g2, dim3(kThreads), stream, Q, slot_lo, slot_cnt);
-    else SD_LAUNCH((k_stats<DT, false, TAIL>), g2, dim3(kThreads), stream, Q, slot_lo, slot_cnt);
-    return SD_OK;
-}
 
 // resident capacity of a kernel's workgroups (256 threads unless given) on this device (occupancy x
 // CUs), cached per (device, kernel, block, dynamic LDS) under a mutex: any host thread may call
@@ -3752,41 +3773,31 @@ int resident_cap(const void* kern, int threads, size_t dyn) {
     return it->second;
 }
 
+// the fused kernel of P's dtype and FAST case, in block-id or ticket order
+using FusedKernel = void (*)(sd::Plan, int, int);
+FusedKernel fused_kernel(const sd::Plan& P, bool ticket) {
+    return dispatch_dtype(P.tdt, [&](auto dt_) {
+        return dispatch_bool(P.fast(), [&](auto fast_) {
+            return dispatch_bool(ticket, [&](auto ticket_) -> FusedKernel {
+                return k_verify_fused<decltype(dt_)::value, decltype(fast_)::value, decltype(ticket_)::value>;
+            });
+        });
+    });
+}
+
 // The whole perf-mode verify of stochastic target rows in ONE launch (k_stats<.., TAIL, SAMP>): the
 // spans, a decider and P.n_samp samplers per sequence, every workgroup resident (the decider and the
 // samplers poll).  1 launched, 0 not applicable (the caller runs k_stats + k_sample), < 0 an error.
-template <int DT>
-int32_t launch_fused_dt(const sd::Plan& P, bool fast, void* stream) {
+int32_t launch_fused(const sd::Plan& P, void* stream) {
+    if (!poll_allowed()) return 0;
     const int64_t head = (int64_t)P.B * (P.n_tslots * P.n_chunks + 1);
     // ticket mode: every label gets ceil(B / labels) sequences' workgroups (stats_body)
     const int64_t seqs = P.ticket ? (int64_t)P.labels * ((P.B + P.labels - 1) / P.labels) : P.B;
     const int64_t total = P.ticket ? seqs * (P.n_tslots * P.n_chunks + 1 + P.n_samp) : head + (int64_t)P.B * P.n_samp;
-    if (!poll_allowed()) return 0;
     sd::Plan Q = P;
     Q.kpoll = 1;
-    if (P.ticket) {
-        if (fast) SD_LAUNCH((k_verify_fused<DT, true, true>), dim3((uint32_t)total), dim3(kThreads), stream, Q, 0, P.n_tslots);
-        else SD_LAUNCH((k_verify_fused<DT, false, true>), dim3((uint32_t)total), dim3(kThreads), stream, Q, 0, P.n_tslots);
-    } else {
-        if (fast) SD_LAUNCH((k_verify_fused<DT, true, false>), dim3((uint32_t)total), dim3(kThreads), stream, Q, 0, P.n_tslots);
-        else SD_LAUNCH((k_verify_fused<DT, false, false>), dim3((uint32_t)total), dim3(kThreads), stream, Q, 0, P.n_tslots);
-    }
-    return 1;
-}
-
-// the block-id layout's kernel (its residency decides between the layouts, fused_layout)
-const void* fused_kernel(const sd::Plan& P) {
-    const bool fast = P.tT == 1.0f && P.dT == 1.0f && !P.t_keep && !P.d_keep;
-    if (P.tdt == SD_BF16) return fast ? (const void*)k_verify_fused<SD_BF16, true, false> : (const void*)k_verify_fused<SD_BF16, false, false>;
-    if (P.tdt == SD_F16) return fast ? (const void*)k_verify_fused<SD_F16, true, false> : (const void*)k_verify_fused<SD_F16, false, false>;
-    return fast ? (const void*)k_verify_fused<SD_F32, true, false> : (const void*)k_verify_fused<SD_F32, false, false>;
-}
-
-int32_t launch_fused(const sd::Plan& P, void* stream) {
-    const bool fast = P.tT == 1.0f && P.dT == 1.0f && !P.t_keep && !P.d_keep;
-    if (P.tdt == SD_BF16) return launch_fused_dt<SD_BF16>(P, fast, stream);
-    if (P.tdt == SD_F16) return launch_fused_dt<SD_F16>(P, fast, stream);
-    return launch_fused_dt<SD_F32>(P, fast, stream);
+    const int32_t st = launch(fused_kernel(P, P.ticket != 0), dim3((uint32_t)total), dim3(kThreads), 0, stream, Q, 0, P.n_tslots);
+    return st == SD_OK ? 1 : st;
 }
 
 // The fused verify's work layout for F (n_samp set): block-id order when the spans and deciders are
@@ -3803,7 +3814,8 @@ constexpr int kTicketLag = 1;       // default lag (SD_OPT_TICKET_LAG pins it): 
 constexpr int kTicketSampChunks = 4;   // chunks per sampler in ticket order (SD_OPT_SAMP_CHUNKS pins it): 4 measured best at B = 128 / 512
 constexpr int kTicketSpan = 16 * kThreads * 8;   // 32768 elements: 4 spans per Llama-3 row
 bool fused_layout(sd::Plan& F) {
-    const int cap = resident_cap(fused_kernel(F));
+    // the block-id layout's kernel: its residency decides between the layouts
+    const int cap = resident_cap((const void*)fused_kernel(F, false));
     const int64_t head = (int64_t)F.B * (F.n_tslots * F.n_chunks + 1);
     const bool resident = cap > 0 && 2 * head <= cap;
     const int tmode = opt(g_opt_ticket);
@@ -3825,16 +3837,25 @@ bool fused_layout(sd::Plan& F) {
     return true;
 }
 
+// one k_stats launch over the slots [slot_lo, slot_lo + slot_cnt), which share a dtype
 int32_t launch_stats_group(const sd::Plan& P, int dt, bool fast, int slot_lo, int slot_cnt, bool tail, void* stream) {
     if (slot_cnt <= 0) return SD_OK;
-    if (tail) {
-        if (dt == SD_BF16) return launch_stats_dt<SD_BF16, true>(P, fast, slot_lo, slot_cnt, stream);
-        if (dt == SD_F32) return launch_stats_dt<SD_F32, true>(P, fast, slot_lo, slot_cnt, stream);
-        return launch_stats_dt<SD_F16, true>(P, fast, slot_lo, slot_cnt, stream);
-    }
-    if (dt == SD_BF16) return launch_stats_dt<SD_BF16, false>(P, fast, slot_lo, slot_cnt, stream);
-    if (dt == SD_F32) return launch_stats_dt<SD_F32, false>(P, fast, slot_lo, slot_cnt, stream);
-    return launch_stats_dt<SD_F16, false>(P, fast, slot_lo, slot_cnt, stream);
+    return dispatch_dtype(dt, [&](auto dt_) {
+        return dispatch_bool(fast, [&](auto fast_) {
+            return dispatch_bool(tail, [&](auto tail_) {
+                constexpr bool TAIL = decltype(tail_)::value;
+                const auto kern = k_stats<decltype(dt_)::value, decltype(fast_)::value, TAIL>;
+                // poll-mode decide tail: the drafter stats came with the draws (target slots only, one launch)
+                sd::Plan Q = P;
+                Q.kpoll = TAIL && P.dstats && P.n_chunks <= kWave && P.stat_slots == P.n_tslots &&
+                          P.n_tslots <= sd::kFastSlots && slot_lo == 0 && slot_cnt == P.stat_slots &&
+                          sample_poll_ok(P.B, (const void*)kern);
+                // poll mode: a 1-D grid with one decider workgroup per sequence after its spans (k_stats)
+                const dim3 grid = Q.kpoll ? dim3(P.B * (slot_cnt * P.n_chunks + 1)) : dim3(P.n_chunks, P.B * slot_cnt);
+                return launch(kern, grid, dim3(kThreads), 0, stream, Q, slot_lo, slot_cnt);
+            });
+        });
+    });
 }
 
 // A poll-mode exchange (k_sample's finish, k_stats' decide tail) needs its B consumers plus producers
@@ -3845,67 +3866,48 @@ bool sample_poll_ok(int B, const void* kern) {
     return 2 * B <= resident_cap(kern);
 }
 
-template <int TDT, int DDT>
-int32_t launch_resample_dd(const sd::Plan& P, void* stream) {
-    const dim3 grid(P.rn_chunks, P.B);
-    // FAST: T == 1 and no top-k / nucleus mask on either side (the engine rule, plain softmax)
-    const bool fast = P.tT == 1.0f && P.dT == 1.0f && !P.t_keep && !P.d_keep;
-    if (P.noise.mode == SD_NOISE_STREAM) {
-        if (fast) SD_LAUNCH((k_resample<TDT, DDT, 8, true>), grid, dim3(kThreads), stream, P);
-        else SD_LAUNCH((k_resample<TDT, DDT, 8, false>), grid, dim3(kThreads), stream, P);
-    } else if (P.t_stoch) {
-        // poll-mode finish when the consumers (one per sequence) leave room for every producer
-        sd::Plan Q = P;
-        Q.spoll = sample_poll_ok(P.B, fast ? (const void*)k_sample<TDT, DDT, true, true>
-                                           : (const void*)k_sample<TDT, DDT, false, true>);
-        if (fast) SD_LAUNCH((k_sample<TDT, DDT, true, true>), grid, dim3(kThreads), stream, Q);
-        else SD_LAUNCH((k_sample<TDT, DDT, false, true>), grid, dim3(kThreads), stream, Q);
-    } else {
-        if (fast) SD_LAUNCH((k_sample<TDT, DDT, true, false>), grid, dim3(kThreads), stream, P);
-        else SD_LAUNCH((k_sample<TDT, DDT, false, false>), grid, dim3(kThreads), stream, P);
-    }
-    return SD_OK;
-}
-
-template <int TDT>
-int32_t launch_resample_t(const sd::Plan& P, int ddt, void* stream) {
-    if (ddt == SD_BF16) return launch_resample_dd<TDT, SD_BF16>(P, stream);
-    if (ddt == SD_F32) return launch_resample_dd<TDT, SD_F32>(P, stream);
-    return launch_resample_dd<TDT, SD_F16>(P, stream);
-}
-
+// After k_stats: STREAM k_resample, or perf-mode k_sample (its tail finalizes).  The drafter rows are
+// fp32 when the caller passed probabilities.
 int32_t launch_resample(const sd::Plan& P, void* stream) {
-    const int ddt = P.draft_is_probs ? SD_F32 : P.ddt;
-    if (P.tdt == SD_BF16) return launch_resample_t<SD_BF16>(P, ddt, stream);
-    if (P.tdt == SD_F32) return launch_resample_t<SD_F32>(P, ddt, stream);
-    return launch_resample_t<SD_F16>(P, ddt, stream);
-}
-
-template <int DT>
-int32_t launch_rowsample_dt(const sd::Plan& P, void* stream) {
     const dim3 grid(P.rn_chunks, P.B);
-    // FAST: T = 1 and no top-k / nucleus mask (the engine's plain softmax draws)
-    const bool fast = P.tT == 1.0f && !P.t_keep;
-    if (P.noise.mode == SD_NOISE_STREAM) {
-        if (fast) SD_LAUNCH((k_rowsample<DT, SD_NOISE_STREAM, 8, true>), grid, dim3(kThreads), stream, P);
-        else SD_LAUNCH((k_rowsample<DT, SD_NOISE_STREAM, 8>), grid, dim3(kThreads), stream, P);
-    } else {
-        SD_LAUNCH((k_rowsample<DT, SD_NOISE_PHILOX, 8>), grid, dim3(kThreads), stream, P);
-    }
-    return SD_OK;
+    return dispatch_dtype(P.tdt, [&](auto tdt_) {
+        return dispatch_dtype(P.draft_is_probs ? SD_F32 : P.ddt, [&](auto ddt_) {
+            return dispatch_bool(P.fast(), [&](auto fast_) {
+                constexpr int TDT = decltype(tdt_)::value, DDT = decltype(ddt_)::value;
+                constexpr bool FAST = decltype(fast_)::value;
+                if (P.noise.mode == SD_NOISE_STREAM)
+                    return launch(k_resample<TDT, DDT, 8, FAST>, grid, dim3(kThreads), 0, stream, P);
+                return dispatch_bool(P.t_stoch != 0, [&](auto stoch_) {
+                    constexpr bool STOCH = decltype(stoch_)::value;
+                    const auto kern = k_sample<TDT, DDT, FAST, STOCH>;
+                    // poll-mode finish when the consumers (one per sequence) leave room for every producer
+                    sd::Plan Q = P;
+                    if (STOCH) Q.spoll = sample_poll_ok(P.B, (const void*)kern);
+                    return launch(kern, grid, dim3(kThreads), 0, stream, Q);
+                });
+            });
+        });
+    });
 }
 
+// argmax of every chunk (k_rowsample; under PHILOX there is no FAST variant)
 int32_t launch_rowsample(const sd::Plan& P, void* stream) {
-    if (P.tdt == SD_BF16) return launch_rowsample_dt<SD_BF16>(P, stream);
-    if (P.tdt == SD_F32) return launch_rowsample_dt<SD_F32>(P, stream);
-    return launch_rowsample_dt<SD_F16>(P, stream);
+    const dim3 grid(P.rn_chunks, P.B);
+    return dispatch_dtype(P.tdt, [&](auto dt_) {
+        constexpr int DT = decltype(dt_)::value;
+        if (P.noise.mode != SD_NOISE_STREAM)
+            return launch(k_rowsample<DT, SD_NOISE_PHILOX, 8>, grid, dim3(kThreads), 0, stream, P);
+        return dispatch_bool(P.t_fast(), [&](auto fast_) {
+            return launch(k_rowsample<DT, SD_NOISE_STREAM, 8, decltype(fast_)::value>, grid, dim3(kThreads), 0, stream, P);
+        });
+    });
 }
 
 // Row statistics for every slot: one launch when target and drafter rows share a dtype.
 // tail: perf-mode decision in the last workgroup per sequence (both launches count arrivals; the
 // second launch starts after the first has finished, so the last arrival is always in it).
 int32_t launch_stats(const sd::Plan& P, void* stream, bool tail) {
-    const bool t_fast = P.tT == 1.0f && !P.t_keep, d_fast = P.dT == 1.0f && !P.d_keep;
+    const bool t_fast = P.t_fast(), d_fast = P.dT == 1.0f && !P.d_keep;
     const int d_cnt = P.stat_slots - P.n_tslots;   // drafter slots without stashed stats
     if (d_cnt == 0 || (P.tdt == P.ddt && t_fast == d_fast))
         return launch_stats_group(P, P.tdt, t_fast, 0, P.stat_slots, tail, stream);
@@ -3914,24 +3916,24 @@ int32_t launch_stats(const sd::Plan& P, void* stream, bool tail) {
 }
 
 // perf-mode sd_sample of stochastic rows: k_draw (one launch, one pass)
-template <int DT>
-int32_t launch_draw_dt(const sd::Plan& P, int nst, void* stream) {
-    const dim3 grid(P.n_chunks, P.B);
-    const bool fast = P.tT == 1.0f && !P.t_keep;
-    if (nst == 1) {
-        if (fast) SD_LAUNCH((k_draw<DT, true, 1>), grid, dim3(kThreads), stream, P);
-        else SD_LAUNCH((k_draw<DT, false, 1>), grid, dim3(kThreads), stream, P);
-    } else if (nst == 4) {
-        if (fast) SD_LAUNCH((k_draw<DT, true, 4>), grid, dim3(kThreads), stream, P);
-        else SD_LAUNCH((k_draw<DT, false, 4>), grid, dim3(kThreads), stream, P);
-    } else {
-        if (fast) SD_LAUNCH((k_draw<DT, true, 2>), grid, dim3(kThreads), stream, P);
-        else SD_LAUNCH((k_draw<DT, false, 2>), grid, dim3(kThreads), stream, P);
-    }
-    return SD_OK;
+int32_t launch_draw_nst(const sd::Plan& P, int nst, void* stream) {
+    return dispatch_dtype(P.tdt, [&](auto dt_) {
+        return dispatch_bool(P.t_fast(), [&](auto fast_) {
+            return dispatch_int<1, 4, 2>(nst, [&](auto nst_) {
+                return launch(k_draw<decltype(dt_)::value, decltype(fast_)::value, decltype(nst_)::value>,
+                              dim3(P.n_chunks, P.B), dim3(kThreads), 0, stream, P);
+            });
+        });
+    });
 }
 
 // k_draw_lean's cases: T = 1, no processor, 16-bit rows, every row 16-byte aligned, <= 128 spans
+bool draw_lean_ok(const sd::Plan& P) {
+    const bool al = (reinterpret_cast<uintptr_t>(P.trow[0]) & 15) == 0 && (P.tstride * 2) % 16 == 0;
+    const int64_t span = (int64_t)kThreads * 8;   // one 2048-element span per stage (4096-element spans measured slower)
+    return P.t_fast() && P.tdt != SD_F32 && al && P.V >= 8 && (P.V + span - 1) / span <= 128;
+}
+
 template <int DT, int NST, bool GREEDY = false>
 int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
     DrawLean A{};
@@ -3952,8 +3954,7 @@ int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
     A.spin_limit = P.spin_limit;
     A.status_or = P.status_or;
     A.ts = P.ts;
-    SD_LAUNCH((k_draw_lean<DT, NST, GREEDY>), dim3(A.n_span, P.B), dim3(kThreads), stream, A);
-    return SD_OK;
+    return launch(k_draw_lean<DT, NST, GREEDY>, dim3(A.n_span, P.B), dim3(kThreads), 0, stream, A);
 }
 
 // The one-launch verify of a few sequences (sd_verify_lean.inc): 1 launched, 0 not applicable (the
@@ -3984,36 +3985,20 @@ int32_t launch_verify_lean(const sd::Plan& P0, void* stream) {
         if (reinterpret_cast<uintptr_t>(P0.trow[t]) & 15) { lean_why(8); return 0; }
     for (int t = 0; t < P0.gamma; ++t)
         if (reinterpret_cast<uintptr_t>(P0.drow[t]) & 15) { lean_why(9); return 0; }
-    const bool fast = P0.tT == 1.0f && P0.dT == 1.0f && !P0.t_keep && !P0.d_keep;
     const bool stoch = P0.t_stoch != 0;
-    const int di = P0.tdt == SD_BF16 ? 0 : 1;
     using K = void (*)(sd::Plan);
-    static const K kerns[2][2][2] = {
-        {{sd::k_verify_lean<SD_BF16, false, false>, sd::k_verify_lean<SD_BF16, false, true>},
-         {sd::k_verify_lean<SD_BF16, true, false>, sd::k_verify_lean<SD_BF16, true, true>}},
-        {{sd::k_verify_lean<SD_F16, false, false>, sd::k_verify_lean<SD_F16, false, true>},
-         {sd::k_verify_lean<SD_F16, true, false>, sd::k_verify_lean<SD_F16, true, true>}}};
-    const K kern = kerns[di][fast][stoch];
+    const K kern = dispatch_dtype16(P0.tdt, [&](auto dt_) {
+        return dispatch_bool(P0.fast(), [&](auto fast_) {
+            return dispatch_bool(stoch, [&](auto stoch_) -> K {
+                return sd::k_verify_lean<decltype(dt_)::value, decltype(fast_)::value, decltype(stoch_)::value>;
+            });
+        });
+    });
     // the staged spans: the target rows and the drafter rows the launch loads, 4 KB each
     const int nload = P0.n_tslots + ((stoch || !P0.dstats) ? P0.gamma : 0);
     const size_t dyn = (size_t)nload * kThreads * sizeof(uint4);
-    static std::mutex mu;
-    static std::map<std::tuple<int, const void*, size_t>, int> caps;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { lean_why(10); return 0; }
-    int cap;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = caps.find({dev, (const void*)kern, dyn});
-        if (it == caps.end()) {
-            int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, sd::kLeanThreads, dyn) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-                per_cu = cus = 0;
-            it = caps.emplace(std::make_tuple(dev, (const void*)kern, dyn), per_cu * cus).first;
-        }
-        cap = it->second;
-    }
+    const int cap = resident_cap((const void*)kern, sd::kLeanThreads, dyn);
+    if (cap <= 0) { lean_why(10); return 0; }   // no device, or the occupancy query failed
     // headroom: every workgroup polls its sequence's others, so the whole grid must be resident; a
     // kernel of another stream holding some CUs must not push it past that, so the grid takes at
     // most half the device's slots (at V = 128256: up to 4 sequences); beyond, k_stats + k_sample
@@ -4028,8 +4013,7 @@ int32_t launch_verify_lean(const sd::Plan& P0, void* stream) {
     // both fit the workspace's rpart region: B (2γ+1) (nc+1) ResParts >= B n_span (ResPart + 16 (2γ+1))
     const uintptr_t srec = reinterpret_cast<uintptr_t>(P0.rpart + (int64_t)P0.B * n_span);
     P.srec = reinterpret_cast<uint4*>((srec + 15) & ~uintptr_t(15));
-    hipLaunchKernelGGL(kern, dim3(n_span, P.B), dim3(sd::kLeanThreads), (unsigned)dyn, (hipStream_t)stream, P);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) { g_last_error = e; return SD_ERR_LAUNCH; }
+    if (int32_t st = launch(kern, dim3(n_span, P.B), dim3(sd::kLeanThreads), dyn, stream, P)) return st;
     lean_why(0);
     return 1;
 }
@@ -4040,15 +4024,12 @@ int32_t launch_verify_lean(const sd::Plan& P0, void* stream) {
 // must leave room for every producer (the occupancy check), and sd_set_poll_policy must allow it;
 // SD_OPT_DRAW_STREAM = 0 turns it off (A/B, tests).
 int32_t launch_draw_stream(const sd::Plan& P, void* stream) {
-    if (P.noise.mode != SD_NOISE_STREAM || !P.t_stoch || P.tT != 1.0f || P.t_keep || P.tdt == SD_F32) return 0;
+    if (P.noise.mode != SD_NOISE_STREAM || !P.t_stoch || !P.t_fast() || P.tdt == SD_F32) return 0;
     if (P.token_prob || P.keep_out || P.B > kCntMax || !poll_allowed() || opt(g_opt_draw_stream) == 0) return 0;
     const bool al = (reinterpret_cast<uintptr_t>(P.trow[0]) & 15) == 0 && (P.tstride * 2) % 16 == 0;
     const int n_span = (int)((P.V + kThreads * 8 - 1) / (kThreads * 8));
     if (!al || P.V < 8 || n_span > 128) return 0;
     if ((int64_t)n_span * sd::kDsRecs * 16 > (int64_t)(max_chunks(P.V) + 1) * (int64_t)sizeof(sd::ResPart)) return 0;
-    const int cap = resident_cap(P.tdt == SD_BF16 ? (const void*)sd::k_draw_stream<SD_BF16>
-                                                  : (const void*)sd::k_draw_stream<SD_F16>);
-    if (cap <= 0 || 2 * P.B > cap) return 0;
     sd::DrawStream A{};
     A.rows = static_cast<const char*>(P.trow[0]);
     A.stride_bytes = P.tstride * 2;
@@ -4066,43 +4047,39 @@ int32_t launch_draw_stream(const sd::Plan& P, void* stream) {
     A.n_span = n_span;
     A.spin_limit = P.spin_limit;
     A.rows_total = P.B;
-    const dim3 grid(n_span, P.B);
-    if (P.tdt == SD_BF16) SD_LAUNCH((sd::k_draw_stream<SD_BF16>), grid, dim3(kThreads), stream, A);
-    else SD_LAUNCH((sd::k_draw_stream<SD_F16>), grid, dim3(kThreads), stream, A);
-    return 1;
+    return dispatch_dtype16(P.tdt, [&](auto dt_) -> int32_t {
+        const auto kern = sd::k_draw_stream<decltype(dt_)::value>;
+        const int cap = resident_cap((const void*)kern);
+        if (cap <= 0 || 2 * P.B > cap) return 0;
+        const int32_t st = launch(kern, dim3(n_span, P.B), dim3(kThreads), 0, stream, A);
+        return st == SD_OK ? 1 : st;
+    });
 }
 
 // greedy sd_sample rows in one pass (k_draw_lean<GREEDY>): 1 if launched, 0 if the shape needs the
 // three-launch path (statistics, per-chunk argmax, finalize), < 0 on a launch error
 int32_t launch_greedy_lean(const sd::Plan& P, void* stream) {
-    const bool fast = P.tT == 1.0f && !P.t_keep && P.tdt != SD_F32;
-    const bool al = (reinterpret_cast<uintptr_t>(P.trow[0]) & 15) == 0 && (P.tstride * 2) % 16 == 0;
-    const int64_t span = (int64_t)kThreads * 8;
-    if (!fast || !al || P.V < 8 || (P.V + span - 1) / span > 128) return 0;
-    const int32_t st = P.tdt == SD_BF16 ? launch_draw_lean_t<SD_BF16, 1, true>(P, stream)
-                                        : launch_draw_lean_t<SD_F16, 1, true>(P, stream);
+    if (!draw_lean_ok(P)) return 0;
+    const int32_t st = dispatch_dtype16(P.tdt, [&](auto dt_) {
+        return launch_draw_lean_t<decltype(dt_)::value, 1, true>(P, stream);
+    });
     return st == SD_OK ? 1 : st;
 }
 
 int32_t launch_draw(sd::Plan& P, void* stream) {
-    {
-        const bool fast = P.tT == 1.0f && !P.t_keep && P.tdt != SD_F32;
-        const bool al = (reinterpret_cast<uintptr_t>(P.trow[0]) & 15) == 0 && (P.tstride * 2) % 16 == 0;
-        // one 2048-element span per workgroup (4096-element spans measured slower)
-        const int64_t span = (int64_t)kThreads * 8;
-        if (fast && al && P.V >= 8 && (P.V + span - 1) / span <= 128) {
-            // stages per workgroup: one 2048-element span while the grid is a few thousand
-            // workgroups; a large batch takes 2 or 4 stages per workgroup, so each holds more bytes
-            // in flight and the grid stays a few resident rounds (SD_OPT_DRAW_SPAN pins it)
-            int nst = opt(g_opt_draw_span);
-            if (nst == 0) nst = P.B <= kDrawSpan4MinB ? 1 : 4;
-            int32_t st;
-            if (nst == 4) st = P.tdt == SD_BF16 ? launch_draw_lean_t<SD_BF16, 4>(P, stream) : launch_draw_lean_t<SD_F16, 4>(P, stream);
-            else if (nst == 2) st = P.tdt == SD_BF16 ? launch_draw_lean_t<SD_BF16, 2>(P, stream) : launch_draw_lean_t<SD_F16, 2>(P, stream);
-            else st = P.tdt == SD_BF16 ? launch_draw_lean_t<SD_BF16, 1>(P, stream) : launch_draw_lean_t<SD_F16, 1>(P, stream);
-            if (st == SD_OK) g_sample_path = SD_PATH_SAMPLE_DRAW_LEAN;   // only once the launch succeeded
-            return st;
-        }
+    if (draw_lean_ok(P)) {
+        // stages per workgroup: one 2048-element span while the grid is a few thousand
+        // workgroups; a large batch takes 2 or 4 stages per workgroup, so each holds more bytes
+        // in flight and the grid stays a few resident rounds (SD_OPT_DRAW_SPAN pins it)
+        int nst = opt(g_opt_draw_span);
+        if (nst == 0) nst = P.B <= kDrawSpan4MinB ? 1 : 4;
+        const int32_t st = dispatch_dtype16(P.tdt, [&](auto dt_) {
+            return dispatch_int<4, 2, 1>(nst, [&](auto nst_) {
+                return launch_draw_lean_t<decltype(dt_)::value, decltype(nst_)::value>(P, stream);
+            });
+        });
+        if (st == SD_OK) g_sample_path = SD_PATH_SAMPLE_DRAW_LEAN;   // only once the launch succeeded
+        return st;
     }
     // spans of NST stages (2048 elements each): 2 once the grid passes ~1024 workgroups
     // (measured at 32 rows of 128256 bf16: NST 1 9.0 us, 2 8.5, 4 10.6 — its registers spill)
@@ -4115,9 +4092,7 @@ int32_t launch_draw(sd::Plan& P, void* stream) {
     P.n_chunks = (int32_t)((P.V + P.chunk - 1) / P.chunk);
     P.rn_chunks = P.n_chunks;   // pick_chunk's count
     P.xcd_affine = P.B % 8 == 0;
-    const int32_t st = P.tdt == SD_BF16 ? launch_draw_dt<SD_BF16>(P, nst, stream)
-                     : P.tdt == SD_F32  ? launch_draw_dt<SD_F32>(P, nst, stream)
-                                        : launch_draw_dt<SD_F16>(P, nst, stream);
+    const int32_t st = launch_draw_nst(P, nst, stream);
     if (st == SD_OK) g_sample_path = SD_PATH_SAMPLE_DRAW;
     return st;
 }
@@ -4154,14 +4129,10 @@ int32_t launch_draw_nuc(const sd::Plan& P, const sd_processor& proc, void* strea
     A.top_p = proc.top_p;
     A.spin_limit = P.spin_limit;
     A.status_or = P.status_or;
-    const dim3 grid(nsl, P.B);
-    if (P.tdt == SD_BF16)
-        hipLaunchKernelGGL(sd::k_draw_nuc<SD_BF16>, grid, dim3(sd::kNucThreads), 0, (hipStream_t)stream, A);
-    else
-        hipLaunchKernelGGL(sd::k_draw_nuc<SD_F16>, grid, dim3(sd::kNucThreads), 0, (hipStream_t)stream, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_error = e; return SD_ERR_LAUNCH; }
-    return 1;
+    const int32_t st = dispatch_dtype16(P.tdt, [&](auto dt_) {
+        return launch(sd::k_draw_nuc<decltype(dt_)::value>, dim3(nsl, P.B), dim3(sd::kNucThreads), 0, stream, A);
+    });
+    return st == SD_OK ? 1 : st;
 }
 
 }  // namespace
@@ -4361,11 +4332,12 @@ int32_t sd_verify(const sd_verify_args* a, void* stream) {
         if (int32_t st = launch_stats(P, stream, perf)) return st;
     if (a->prof_stats_end) (void)hipEventRecord((hipEvent_t)a->prof_stats_end, (hipStream_t)stream);
     if (!perf) {   // parity mode: the reference's serial noise order
-        SD_LAUNCH(k_decide, dim3(P.B), dim3(256), stream, P);
-        SD_LAUNCH(k_walk, dim3(1), dim3(256), stream, P);
+        if (int32_t st = launch(k_decide, dim3(P.B), dim3(256), 0, stream, P)) return st;
+        if (int32_t st = launch(k_walk, dim3(1), dim3(256), 0, stream, P)) return st;
     }
     if (int32_t st = launch_resample(P, stream)) return st;   // perf mode: k_sample finalizes in its tail
-    if (!perf) SD_LAUNCH(k_finalize, dim3(P.B), dim3(64), stream, P);
+    if (!perf)
+        if (int32_t st = launch(k_finalize, dim3(P.B), dim3(64), 0, stream, P)) return st;
     g_verify_path = perf ? SD_PATH_VERIFY_TWO_LAUNCH : SD_PATH_VERIFY_STREAM;
     return SD_OK;
 }
@@ -4385,11 +4357,9 @@ int32_t sd_sample(const sd_sample_args* a, void* stream) {
     if (a->noise.mode == SD_NOISE_STREAM && a->proc.kind != SD_PROC_GREEDY && !a->noise.words) return SD_ERR_INVALID;
     if (a->workspace_bytes < sd_sample_workspace_size(a->rows, a->vocab) || !a->workspace) return SD_ERR_WORKSPACE;
     Plan P{};
-    P.B = a->rows; P.gamma = 1; P.V = a->vocab; P.rule = -1;
-    P.n_tslots = 1; P.n_dslots = 0; P.slots = 1; P.stat_slots = 1;
-    P.tdt = a->dtype; P.ddt = a->dtype;
-    P.t_keep = needs_keep(a->proc); P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
-    P.tT = a->proc.temperature; P.dT = 1.f;
+    plan_rows(P, a->rows, 1, a->vocab, a->dtype, a->proc);
+    P.gamma = 1;
+    P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
     P.trow[0] = a->logits; P.tstride = a->stride_r;
     P.noise = a->noise;
     P.next_token = a->tokens; P.next_token_stride = a->tokens_stride;
@@ -4397,7 +4367,6 @@ int32_t sd_sample(const sd_sample_args* a, void* stream) {
     P.row_stats = reinterpret_cast<float2*>(a->row_stats);
     P.keep_out = reinterpret_cast<RowKeep*>(a->row_keep);
     P.status_or = a->status_or;
-    P.spin_limit = spin_limit();
     set_stats_chunks(P, P.B);
     Carve c{static_cast<char*>(a->workspace)};
     carve(P, c, a->rows, a->rows, 1, a->vocab);
@@ -4431,7 +4400,7 @@ int32_t sd_sample(const sd_sample_args* a, void* stream) {
     set_rchunks(P);
     if (int32_t st = launch_stats(P, stream)) return st;
     if (int32_t st = launch_rowsample(P, stream)) return st;
-    SD_LAUNCH(k_sample_finalize, dim3(P.B), dim3(64), stream, P);
+    if (int32_t st = launch(k_sample_finalize, dim3(P.B), dim3(64), 0, stream, P)) return st;
     g_sample_path = SD_PATH_SAMPLE_MULTI;
     return SD_OK;
 }
@@ -4444,13 +4413,9 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
     if (!valid_dtype(a->dtype) || !valid_proc(a->proc) || !(a->proc.temperature > 0.f)) return SD_ERR_INVALID;
     if (a->workspace_bytes < sd_probs_workspace_size(a->rows, a->vocab) || !a->workspace) return SD_ERR_WORKSPACE;
     Plan P{};
-    P.B = a->rows; P.gamma = 1; P.V = a->vocab; P.rule = -1;
-    P.n_tslots = 1; P.n_dslots = 0; P.slots = 1; P.stat_slots = 1;
-    P.tdt = a->dtype; P.ddt = a->dtype;
-    P.t_keep = needs_keep(a->proc);
-    P.tT = a->proc.temperature; P.dT = 1.f;
+    plan_rows(P, a->rows, 1, a->vocab, a->dtype, a->proc);
+    P.gamma = 1;
     P.trow[0] = a->logits; P.tstride = a->stride_r;
-    P.spin_limit = spin_limit();
     set_stats_chunks(P, P.B);
     Carve c{static_cast<char*>(a->workspace)};
     carve(P, c, a->rows, a->rows, 1, a->vocab);
@@ -4462,11 +4427,10 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
     if (int32_t st = launch_stats(P, stream)) return st;
     P.rchunk = kThreads * kEptSmall;   // plain streaming write: one stage per workgroup
     P.rn_chunks = (P.V + P.rchunk - 1) / P.rchunk;
-    const dim3 wg(P.rn_chunks, P.B);
-    if (P.tdt == SD_BF16) SD_LAUNCH((k_writeprobs<SD_BF16, 8>), wg, dim3(kThreads), stream, P, a->probs, a->probs_stride_r);
-    else if (P.tdt == SD_F32) SD_LAUNCH((k_writeprobs<SD_F32, 8>), wg, dim3(kThreads), stream, P, a->probs, a->probs_stride_r);
-    else SD_LAUNCH((k_writeprobs<SD_F16, 8>), wg, dim3(kThreads), stream, P, a->probs, a->probs_stride_r);
-    return SD_OK;
+    return dispatch_dtype(P.tdt, [&](auto dt_) {
+        return launch(k_writeprobs<decltype(dt_)::value, 8>, dim3(P.rn_chunks, P.B), dim3(kThreads), 0, stream, P,
+                      a->probs, a->probs_stride_r);
+    });
 }
 
 }  // extern "C"

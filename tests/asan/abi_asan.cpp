@@ -79,6 +79,36 @@ static void sample_probs_rejections() {
     CHECK(sd_ngram_verify(&n, nullptr) == SD_ERR_INVALID);
 }
 
+// On a host without a device, a compute entry whose arguments are all valid fails at its first
+// launch: it returns SD_ERR_LAUNCH at once and sd_last_hip_error() names the runtime's error.
+// sd_sample with a top-k processor fails in the threshold launcher, sd_probs in the row statistics.
+// (With a device present the fake pointers must never reach a kernel: skipped.)
+extern "C" int hipGetDeviceCount(int* count);   // the HIP runtime the library links; 0 = hipSuccess
+static void launch_failure_without_device() {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) == 0 && n_dev > 0) {
+        std::printf("abi_asan: a device is present, launch-failure checks skipped\n");
+        return;
+    }
+    sd_sample_args s;
+    std::memset(&s, 0, sizeof s);
+    s.rows = 3; s.vocab = 5000; s.logits = fake(1); s.stride_r = 5000; s.tokens = static_cast<int64_t*>(fake(2));
+    s.tokens_stride = 1;
+    s.row_status = static_cast<int32_t*>(fake(3));
+    s.dtype = SD_BF16; s.proc = sd_processor{SD_PROC_TOPK, 0.7f, 50, 1.f};
+    s.noise.mode = SD_NOISE_PHILOX;
+    s.workspace = fake(50); s.workspace_bytes = sd_sample_workspace_size(s.rows, s.vocab);
+    CHECK(sd_sample(&s, nullptr) == SD_ERR_LAUNCH);
+    CHECK(std::strcmp(sd_last_hip_error(), "no error") != 0);
+    sd_probs_args p;
+    std::memset(&p, 0, sizeof p);
+    p.rows = 2; p.vocab = 100; p.logits = fake(3); p.stride_r = 100; p.probs = fake(4); p.probs_stride_r = 100;
+    p.dtype = SD_F32; p.proc = sd_processor{SD_PROC_MULTINOMIAL, 1.f, 0, 1.f};
+    p.workspace = fake(50); p.workspace_bytes = sd_probs_workspace_size(p.rows, p.vocab);
+    CHECK(sd_probs(&p, nullptr) == SD_ERR_LAUNCH);
+    CHECK(std::strcmp(sd_last_hip_error(), "no error") != 0);
+}
+
 static void workspace_shapes() {
     const int32_t Bs[] = {1, 2, 31, 32, 512, 16384};
     const int32_t Vs[] = {1, 7, 2048, 50257, 128256, 262144};
@@ -150,6 +180,7 @@ int main(int argc, char** argv) {
     verify_rejections();
     sample_probs_rejections();
     workspace_shapes();
+    launch_failure_without_device();
     if (argc >= 3) mt_host(argv[1], argv[2]);
     std::printf("abi_asan: %d checks, %d failed\n", g_checks, g_fail);
     return g_fail ? 1 : 0;
