@@ -13,7 +13,10 @@
 // final key group (equal values) the crossing rank is solved in closed form.  The running sums
 // are exact (hence equal to the reference's sequential fp32 sum) whenever every kept p is a
 // multiple of the accumulator's ulp — p >= 2^-17 for bf16/fp16, p >= 2^-29 for fp32 — else the
-// row is flagged SD_ROW_NUCLEUS_INEXACT.  Tied values at the cut are kept lowest-index first
+// row is flagged SD_ROW_NUCLEUS_INEXACT.  An fp32 row is flagged as well when the cumulative mass
+// at its cut (or the whole row's, when nothing crosses) lies within kCutSlackF32 of top_p: there the
+// last-bit rounding of the p themselves (exp and the normaliser, which the reference rounds its own
+// way) decides what crosses — top_p = 1 is always that case.  Tied values at the cut are kept lowest-index first
 // (a stable order); torch's unstable CPU sort orders ties implementation-defined (DESIGN.md).
 
 namespace sd {
@@ -48,6 +51,10 @@ template <int DT>
 __device__ __forceinline__ float masked_value(float x, float tau_k) {
     return x >= tau_k ? x : round_dt<DT>(kNegFill);
 }
+
+// fp32 rows: how near top_p a crossing is decided by the p's rounding (the suite's fp32 tolerance
+// on a probability is 2e-6 relative; the cumulative mass is at most 1)
+constexpr double kCutSlackF32 = 1.0 / (1 << 19);
 
 template <int DT>
 __device__ __forceinline__ bool nucleus_crosses(double cum, float tp) {
@@ -153,7 +160,7 @@ __device__ void threshold_row(const Plan& P, const void* row, ThreshRowParams tp
                     if (nucleus_crosses<DT>(end, tpd)) { dsel = d; break; }
                     acc = end;
                 }
-                if (dsel < 0) s_done = 1;   // never crosses: nothing removed
+                if (dsel < 0) { s_done = 1; s_acc = acc; }   // never crosses: nothing removed (s_acc: the row's mass)
                 else { s_prefix = prefix | ((uint32_t)dsel << shift); s_acc = acc; }
             }
             __syncthreads();
@@ -176,7 +183,9 @@ __device__ void threshold_row(const Plan& P, const void* row, ThreshRowParams tp
             keep.tau = val;
             keep.tie_idx = INT_MAX;
             const double min_exact = DT == SD_F32 ? 1.862645149230957e-09 : 7.62939453125e-06;  // 2^-29, 2^-17
-            if ((double)pg < min_exact || (DT != SD_F32 && A + (double)(t_cut + 1) * pg >= 1.0))
+            const double at_cut = A + (double)(t_cut + 1) * pg;
+            if ((double)pg < min_exact || (DT != SD_F32 && at_cut >= 1.0) ||
+                (DT == SD_F32 && at_cut - (double)tpd <= kCutSlackF32))
                 keep.flags |= SD_ROW_NUCLEUS_INEXACT;
             if (t_cut + 1 < cnt) {
                 // cut inside a run of equal values: keep the first t_cut+1 occurrences by index
@@ -204,9 +213,13 @@ __device__ void threshold_row(const Plan& P, const void* row, ThreshRowParams tp
         // combined predicate: x >= tau_k (top-k) AND nucleus-kept; nucleus tau >= tau_k always
         if (!s_done) {
             if (tp.kind == SD_PROC_TOPK_NUCLEUS && keep.tau < tau_k) { keep.tau = tau_k; keep.tie_idx = INT_MAX; }
-        } else if (tp.kind == SD_PROC_NUCLEUS) {
-            keep.tau = -INFINITY;
-            keep.tie_idx = INT_MAX;
+        } else {
+            if (tp.kind == SD_PROC_NUCLEUS) {
+                keep.tau = -INFINITY;
+                keep.tie_idx = INT_MAX;
+            }
+            // the whole row's mass stays this close below top_p: the reference's own rounding may cross
+            if (DT == SD_F32 && (double)tpd - s_acc <= kCutSlackF32) keep.flags |= SD_ROW_NUCLEUS_INEXACT;
         }
     }
     if (tid == 0) *out = keep;

@@ -3959,12 +3959,13 @@ int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
 
 // The one-launch verify of a few sequences (sd_verify_lean.inc): 1 launched, 0 not applicable (the
 // caller runs k_stats + k_sample), < 0 a launch error.  Perf mode with the drafter stats from the
-// draws, no top-k / nucleus, 16-bit rows of one dtype, V <= 64 spans, every row 16-byte aligned, and
-// the whole grid resident (every workgroup polls).  Up to kLeanVerifyMaxB sequences by default;
+// draws, no top-k / nucleus, 16-bit rows of one dtype, 8 <= V <= 64 spans (one whole 16-byte vector:
+// ld16_clamped's precondition, below it the clamped load would start before the row), every row
+// 16-byte aligned, and the whole grid resident (every workgroup polls).  Up to kLeanVerifyMaxB sequences by default;
 // SD_OPT_LEAN_VERIFY = 0 turns it off, = 1 allows any batch the occupancy check admits (A/B, tests).
 constexpr int kLeanVerifyMaxB = 8;
 
-// why the lean verify was not taken (1..11), kept for diagnostics (a debugger / a printf build)
+// why the lean verify was not taken (1..12), kept for diagnostics (a debugger / a printf build)
 thread_local int g_lean_why = 0;
 static void lean_why(int k) { g_lean_why = k; }
 
@@ -3978,6 +3979,8 @@ int32_t launch_verify_lean(const sd::Plan& P0, void* stream) {
     const int mode = opt(g_opt_lean);
     if (mode == 0 || (mode < 0 && P0.B > kLeanVerifyMaxB)) { lean_why(5); return 0; }
     constexpr int kSpan = kThreads * 8;
+    // k_verify_lean loads through ld16_clamped: it needs one whole vector inside the row
+    if (P0.V < 8) { lean_why(12); return 0; }
     const int n_span = (P0.V + kSpan - 1) / kSpan;
     if (n_span > kWave || P0.rn_chunks != n_span || P0.rchunk != kSpan) { lean_why(6); return 0; }
     if ((P0.tstride * 2) % 16 || (P0.dstride * 2) % 16) { lean_why(7); return 0; }

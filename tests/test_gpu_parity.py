@@ -132,9 +132,15 @@ def run_spec_oracle(tl, dl, ids, proc, gen, stops, skip=False, exact=False):
     return res
 
 
-def run_spec_hip(sd, tl, dl, ids, proc, gen, stops, skip=False):
+def to_device(t):
+    return t.to(DEV)
+
+
+def run_spec_hip(sd, tl, dl, ids, proc, gen, stops, skip=False, place=to_device):
+    """place: how the logits reach the device (tests/test_gpu_row_edges.py lays the rows out in a
+    poisoned buffer); packed rows by default."""
     g = ids.shape[1]
-    tld, dld, idd = tl.to(DEV), dl.to(DEV), ids.to(DEV)
+    tld, dld, idd = place(tl), place(dl), ids.to(DEV)
     out = sd.ops.verify([tld[:, t, :] for t in range(g + 1)], [dld[:, d, :] for d in range(g)], idd,
                         sd.lib.SD_RULE_SPEC, spec_of(sd, proc), spec_of(sd, proc), sd.StreamNoise(gen),
                         torch.tensor(stops, dtype=torch.long, device=DEV), skip_sample_adjustment=skip)
@@ -167,13 +173,13 @@ def note_divergence(label, what):
     print(f"[parity] {what}: HIP matched the {label} oracle, not torch-CPU arithmetic")
 
 
-def check_spec(sd, tl, dl, ids, proc, seed, stops=(), skip=False):
+def check_spec(sd, tl, dl, ids, proc, seed, stops=(), skip=False, place=to_device):
     variants = []
     for label, pv, exact in oracle_variants(proc):
         g = torch.Generator().manual_seed(1000 + seed)
         variants.append((label, run_spec_oracle(tl, dl, ids, pv, g, list(stops), skip, exact), g.get_state()))
     g2 = torch.Generator().manual_seed(1000 + seed)
-    out = run_spec_hip(sd, tl, dl, ids, proc, g2, list(stops), skip)
+    out = run_spec_hip(sd, tl, dl, ids, proc, g2, list(stops), skip, place)
     n = out.n_accepted.cpu().tolist()
     x = out.next_token.cpu().tolist()
     st = out.row_status.cpu().tolist()
@@ -328,7 +334,7 @@ def test_engine_verify_chunked_window(sd, B, gamma, V, dtype, seed):
     _engine_case(sd, B, gamma, V, dtype, seed, sigma=0.05, late_stop=True)
 
 
-def _engine_case(sd, B, gamma, V, dtype, seed, sigma=1.0, late_stop=False):
+def _engine_case(sd, B, gamma, V, dtype, seed, sigma=1.0, late_stop=False, place=to_device):
     plain = ref.Processor("multinomial", 1.0)
     tl, dl, ids = draft_case(B, gamma, V, dtype, seed, plain, sigma=sigma)
     tl = tl[:, :gamma]
@@ -353,7 +359,7 @@ def _engine_case(sd, B, gamma, V, dtype, seed, sigma=1.0, late_stop=False):
     # HIP
     g2 = torch.Generator().manual_seed(2000 + seed)
     gen_d, fin_d, acc_d = generated.to(DEV), finished.to(torch.uint8).to(DEV), acc.to(DEV)
-    tld, dld = tl.to(DEV), dl.to(DEV)
+    tld, dld = place(tl), place(dl)
     plain_spec = sd.ops.PLAIN_SOFTMAX
     out = sd.ops.verify([tld[:, t, :] for t in range(gamma)], [dld[:, d, :] for d in range(gamma)], ids.to(DEV),
                         sd.lib.SD_RULE_ENGINE, plain_spec, plain_spec, sd.StreamNoise(g2),
