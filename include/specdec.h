@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SD_ABI_VERSION 11
+#define SD_ABI_VERSION 12
 #define SD_MAX_GAMMA 32          /* drafts per call; specdec_amd.ops chunks longer windows */
 #define SD_NGRAM_MAX_FILLER 64   /* sd_ngram_verify filler ids per pass; filler_k itself may be
                                     anything up to vocab (ABI 11: one more launch pair per 64)  */
@@ -480,6 +480,84 @@ size_t sd_mt19937_generate_workspace_size(int64_t n_words, int64_t stride_words)
 int32_t sd_mt19937_generate(const sd_mt_generate_args* args, void* stream);
 int32_t sd_mt19937_commit(sd_mt_state* state, const uint32_t* words, int64_t n_words, const int64_t* used_dev,
                           int64_t used, int32_t* status, void* stream);
+
+/* ---- Beam search step (ABI 12; csrc/beam.hip) ----------------------------------------------------
+ * One step of sampling/base_decoding.py:68-187 (beam_search_generate) on the device:
+ *   row pass   (k_beam_topk)    log_softmax + topk of the logit rows (:127-128, :136-137): every row is
+ *                               read once; per row the K best log-probs, in the logits dtype (fp32
+ *                               internally, the value rounded to bf16 / fp16 when the rows are), VALUE
+ *                               DESCENDING, INDEX ASCENDING among equal values (torch.topk leaves the
+ *                               order of equal values undefined; see DESIGN.md, beam step).
+ *   selection  (k_beam_select)  the candidate loop, dedupe, stable sort and state update (:138-178),
+ *                               including the reference's aliasing of a finished beam's score and last
+ *                               index (0-dim views, updated in beam order); one workgroup, a second
+ *                               launch.  SD_BEAM_PREFILL applies :129-131 instead.
+ * No workgroup waits on another (arrival counters only), so a step may be captured into a hipGraph
+ * and may share the GPU.  State is ping-pong: the step reads the `_in` buffers and writes the `_out`
+ * buffers (rows are permuted), which must not overlap.  NaN logits are out of scope (the order of
+ * NaN candidates is unspecified).  vocab <= SD_BEAM_MAX_VOCAB.                                        */
+#define SD_BEAM_MAX_BEAMS 64
+#define SD_BEAM_MAX_TOPK 64
+#define SD_BEAM_MAX_CANDIDATES 1024   /* num_beams * top_k of a SD_BEAM_STEP (the selection's entries) */
+#define SD_BEAM_MAX_VOCAB 524288      /* 256 spans of 2048 elements per row */
+
+typedef enum {
+    SD_BEAM_PREFILL = 0,   /* one logit row, K = num_beams: the first generated position (:123-131)   */
+    SD_BEAM_STEP = 1,      /* num_beams logit rows, K = top_k: one loop iteration (:133-183)           */
+    SD_BEAM_TOPK_ONLY = 2, /* row pass alone over num_beams rows, K = top_k: no state is read or written */
+} sd_beam_mode;
+
+#define SD_BEAM_TOPK_GIVEN 0x1   /* flags: skip the row pass; top_logprob / top_token hold the caller's */
+
+typedef struct {
+    int32_t mode;                /* sd_beam_mode                                                   */
+    int32_t flags;               /* SD_BEAM_*                                                      */
+    int32_t num_beams;           /* 1..SD_BEAM_MAX_BEAMS (TOPK_ONLY: the number of rows)            */
+    int32_t top_k;               /* 1..SD_BEAM_MAX_TOPK (ignored by PREFILL)                        */
+    int32_t vocab;
+    int32_t curr;                /* the position written this step (PREFILL: the prompt length)     */
+    int32_t total_len;           /* row length of input_ids / probs                                */
+    float lp;                    /* the step's length penalty, (float) of the host's double; the
+                                    caller passes 1 where the reference's `lp if lp != 0 else 1` does */
+    const void* logits;          /* row r at logits + r * stride_r (PREFILL: one row)               */
+    int64_t stride_r;
+    int32_t dtype;               /* sd_dtype                                                       */
+    int32_t n_stop;
+    const int64_t* stop_tokens;  /* [n_stop]                                                       */
+    int64_t pad_token;
+    /* state in (read) and out (written); rows of input_ids / probs at * stride elements           */
+    const int64_t* input_ids_in;
+    int64_t* input_ids_out;
+    int64_t input_ids_stride;
+    const float* probs_in;
+    float* probs_out;
+    int64_t probs_stride;
+    const float* beams_probs_in; /* [num_beams]                                                    */
+    float* beams_probs_out;
+    const int64_t* last_index_in;/* [num_beams], -1 = live                                         */
+    int64_t* last_index_out;
+    /* the rows' top-K: [R, K] contiguous (R = 1, K = num_beams under PREFILL; else R = num_beams,
+       K = top_k); written by the row pass, read by the selection (SD_BEAM_TOPK_GIVEN: only read)   */
+    float* top_logprob;          /* fp32 holding the dtype-rounded value                            */
+    int64_t* top_token;
+    int32_t* all_finished;       /* [1]: 1 when every last_index_out != -1, else 0; -1 when fewer
+                                    candidates than beams survived the dedupe (the reference raises) */
+    int32_t* parent;             /* nullable [num_beams, 2]: per output slot the source beam and the
+                                    candidate index (-1 for a finished beam carried over)           */
+    /* device memory of at least sd_beam_workspace_size bytes, ZERO-FILLED ONCE when allocated; not
+       read under SD_BEAM_TOPK_GIVEN (nullable then).  It follows the workspace convention of the
+       other entry points: the row pass's arrival counters lie inside the common counter block at
+       the front (sequence counters 0..rows-1) and are zero again when the call's kernels end, its
+       partials lie behind that block.  One workspace may therefore serve any sequence of
+       sd_beam_step / sd_verify / sd_sample / sd_probs / sd_ngram_verify calls on one stream (not
+       concurrent calls).                                                                          */
+    void* workspace;
+    size_t workspace_bytes;
+} sd_beam_args;
+
+/* rows / k as the row pass sees them (PREFILL: 1, num_beams).  0 for a bad shape.                    */
+size_t sd_beam_workspace_size(int32_t rows, int32_t vocab, int32_t k);
+int32_t sd_beam_step(const sd_beam_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-SD_ABI_VERSION = 11
+SD_ABI_VERSION = 12
 SD_MAX_GAMMA = 32           # drafts per call (ops.verify / ngram_verify chunk longer windows)
 SD_NGRAM_MAX_FILLER = 64
 
@@ -58,7 +58,13 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_mt19937_state_from_torch", "sd_mt19937_state_to_torch", "sd_mt19937_jump_table",
            "sd_mt19937_char_poly", "sd_mt19937_fill_substreams", "sd_mt19937_generate_workspace_size",
            "sd_mt19937_generate", "sd_mt19937_commit", "sd_set_poll_policy", "sd_get_poll_policy",
-           "sd_set_option", "sd_get_option", "sd_last_verify_path", "sd_last_sample_path")
+           "sd_set_option", "sd_get_option", "sd_last_verify_path", "sd_last_sample_path",
+           "sd_beam_workspace_size", "sd_beam_step")
+
+# beam step (ABI 12)
+SD_BEAM_MAX_BEAMS, SD_BEAM_MAX_TOPK, SD_BEAM_MAX_CANDIDATES, SD_BEAM_MAX_VOCAB = 64, 64, 1024, 524288
+SD_BEAM_PREFILL, SD_BEAM_STEP, SD_BEAM_TOPK_ONLY = 0, 1, 2
+SD_BEAM_TOPK_GIVEN = 0x1
 
 SD_MT_JUMP_WORDS = 320
 SD_MT_JUMP_CHUNKS = 16
@@ -158,6 +164,22 @@ class sd_ngram_args(C.Structure):
     ]
 
 
+class sd_beam_args(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("flags", C.c_int32), ("num_beams", C.c_int32), ("top_k", C.c_int32),
+        ("vocab", C.c_int32), ("curr", C.c_int32), ("total_len", C.c_int32), ("lp", C.c_float),
+        ("logits", C.c_void_p), ("stride_r", C.c_int64), ("dtype", C.c_int32), ("n_stop", C.c_int32),
+        ("stop_tokens", C.c_void_p), ("pad_token", C.c_int64),
+        ("input_ids_in", C.c_void_p), ("input_ids_out", C.c_void_p), ("input_ids_stride", C.c_int64),
+        ("probs_in", C.c_void_p), ("probs_out", C.c_void_p), ("probs_stride", C.c_int64),
+        ("beams_probs_in", C.c_void_p), ("beams_probs_out", C.c_void_p),
+        ("last_index_in", C.c_void_p), ("last_index_out", C.c_void_p),
+        ("top_logprob", C.c_void_p), ("top_token", C.c_void_p),
+        ("all_finished", C.c_void_p), ("parent", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 def _share_torch_hip_runtime():
     """Load PyTorch-ROCm's bundled HIP runtime first, so libspecdec.so (NEEDED libamdhip64.so.7,
     which that copy's SONAME satisfies) binds to the SAME runtime torch uses instead of loading
@@ -194,6 +216,10 @@ def _load():
     for ws in ("sd_sample_workspace_size", "sd_probs_workspace_size"):
         getattr(lib, ws).restype = C.c_size_t
         getattr(lib, ws).argtypes = [C.c_int32, C.c_int32]
+    lib.sd_beam_workspace_size.restype = C.c_size_t
+    lib.sd_beam_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.sd_beam_step.restype = C.c_int32
+    lib.sd_beam_step.argtypes = [C.POINTER(sd_beam_args), C.c_void_p]
     lib.sd_verify.restype = C.c_int32
     lib.sd_verify.argtypes = [C.POINTER(sd_verify_args), C.c_void_p]
     lib.sd_sample.restype = C.c_int32

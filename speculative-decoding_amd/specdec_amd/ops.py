@@ -551,3 +551,147 @@ def ngram_verify(target_rows: Sequence[torch.Tensor], draft_tokens: Optional[tor
         noise.consumed(used_dev=out.words_used)
     del keep
     return out
+
+
+# --------------------------------------------------------------------------- beam step (ABI 12)
+def beam_length_penalty(length, alpha: float, min_length: float) -> float:
+    """The reference's per-step divisor (sampling/base_decoding.py:106-107,165): the penalty in double,
+    1 where it is 0, as the C float the kernel divides by."""
+    lp = ((min_length + length) / (min_length + 1)) ** alpha
+    return C.c_float(lp if lp != 0 else 1).value
+
+
+def _beam_check_k(k: int, V: int) -> None:
+    if not 1 <= k <= V:   # torch.topk's error, as the reference raises it (:128, :137)
+        raise RuntimeError("selected index k out of range")
+
+
+def beam_topk(logits: torch.Tensor, k: int, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """topk(log_softmax(logits, -1), k) of every row of logits [R, V] in one pass over the rows
+    (k_beam_topk): (logprob fp32 [R, k] holding the value rounded to the logits dtype, token int64
+    [R, k]), value descending, lowest index first among equal values.  R <= 64, k <= 64."""
+    if logits.dim() != 2:
+        raise ValueError(f"logits: expected [rows, vocab], got {tuple(logits.shape)}")
+    R, V = logits.shape
+    _require_rows(logits, "logits", V)
+    _beam_check_k(int(k), V)
+    dev = logits.device
+    lp, tok = out if out is not None else (torch.empty(R, k, dtype=torch.float32, device=dev),
+                                           torch.empty(R, k, dtype=torch.long, device=dev))
+    ws = _workspace(lib.sd_beam_workspace_size(R, V, k), dev)
+    a = _lib.sd_beam_args()
+    a.mode, a.num_beams, a.top_k, a.vocab = _lib.SD_BEAM_TOPK_ONLY, R, int(k), V
+    a.logits, a.stride_r, a.dtype = logits.data_ptr(), logits.stride(0), _DT[logits.dtype]
+    a.top_logprob, a.top_token = lp.data_ptr(), tok.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _lib.check(lib.sd_beam_step(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_beam_step")
+    return lp, tok
+
+
+class BeamState:
+    """The beam loop's state (sampling/base_decoding.py:115-119) as two device copies: a step reads
+    one and writes the other (rows are permuted), then they swap.  ``input_ids`` / ``probs`` /
+    ``beams_probs`` / ``last_indexes`` are the current copy; ``all_finished`` (int32 [1]) and ``parent``
+    (int32 [num_beams, 2]: source beam, candidate index or -1) are what the last step wrote."""
+
+    def __init__(self, input_ids: torch.Tensor, probs: torch.Tensor, beams_probs: torch.Tensor,
+                 last_indexes: torch.Tensor):
+        n, L = input_ids.shape
+        dev = input_ids.device
+        if not input_ids.is_cuda or input_ids.dtype != torch.long or probs.dtype != torch.float32 \
+                or tuple(probs.shape) != (n, L) or beams_probs.dtype != torch.float32 or beams_probs.numel() != n \
+                or last_indexes.dtype != torch.long or last_indexes.numel() != n \
+                or any(t.device != dev for t in (probs, beams_probs, last_indexes)):
+            raise ValueError("BeamState: input_ids int64 [n, L], probs fp32 [n, L], beams_probs fp32 [n], "
+                             "last_indexes int64 [n], all on one GPU")
+        cur = (input_ids.contiguous(), probs.contiguous(), beams_probs.contiguous(), last_indexes.contiguous())
+        self._bufs = [cur, tuple(torch.empty_like(t) for t in cur)]
+        self._cur = 0
+        self.num_beams, self.total_len, self.device = n, L, dev
+        self.all_finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.parent = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+        self.top_logprob = self.top_token = None
+
+    @classmethod
+    def start(cls, inputs: Sequence[int], num_beams: int, total_len: int, pad_token_id: int, device) -> "BeamState":
+        """The reference's initial state (:115-125) for a prompt."""
+        P = len(inputs)
+        ids = torch.full((num_beams, total_len), pad_token_id, dtype=torch.long, device=device)
+        ids[:, :P] = torch.tensor(inputs, dtype=torch.long, device=device)
+        fmin = torch.finfo(torch.float).min
+        probs = torch.full((num_beams, total_len), fmin, dtype=torch.float, device=device)
+        probs[:, :P] = 1.0
+        return cls(ids, probs, torch.full((num_beams,), 1.0, dtype=torch.float, device=device),
+                   torch.full((num_beams,), -1, dtype=torch.long, device=device))
+
+    input_ids = property(lambda self: self._bufs[self._cur][0])
+    probs = property(lambda self: self._bufs[self._cur][1])
+    beams_probs = property(lambda self: self._bufs[self._cur][2])
+    last_indexes = property(lambda self: self._bufs[self._cur][3])
+
+
+def beam_step(state: BeamState, logits: Optional[torch.Tensor], curr: int, *, top_k: int = 1, prefill: bool = False,
+              length=None, alpha: float = 1.2, min_length: float = 5.0,
+              stop_tokens: Optional[torch.Tensor] = None, pad_token_id: int = 0,
+              topk: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+    """One step of beam_search_generate on the device (sd_beam_step): log_softmax + topk of the logit
+    rows, the candidate loop, dedupe, stable sort and state update of sampling/base_decoding.py:
+    136-178 (prefill=True: :127-131 on one row), written into ``state``'s other copy, which becomes
+    current.  Returns the device word ``state.all_finished`` (1: every beam has finished; -1: fewer
+    candidates than beams survived the dedupe, where the reference raises IndexError); nothing is read
+    back here.  length: the penalty's length (default: 1 in the prefill).  topk=(logprob fp32 [R, K],
+    token int64 [R, K]): select from these instead of reading ``logits`` (SD_BEAM_TOPK_GIVEN)."""
+    n, L, dev = state.num_beams, state.total_len, state.device
+    rows, K = (1, n) if prefill else (n, int(top_k))
+    a = _lib.sd_beam_args()
+    a.mode = _lib.SD_BEAM_PREFILL if prefill else _lib.SD_BEAM_STEP
+    a.num_beams, a.top_k, a.curr, a.total_len = n, int(top_k), int(curr), L
+    if not 1 <= curr < L:
+        raise IndexError(f"index {curr} is out of bounds for dimension 1 with size {L}")
+    if length is None:
+        length = 1
+    a.lp = beam_length_penalty(length, alpha, min_length)
+    keep = None
+    if topk is not None:
+        lpv, tok = topk
+        if lpv.dtype != torch.float32 or tok.dtype != torch.long or tuple(lpv.shape) != (rows, K) \
+                or tuple(tok.shape) != (rows, K) or not lpv.is_contiguous() or not tok.is_contiguous() \
+                or lpv.device != dev or tok.device != dev:
+            raise ValueError(f"topk must be (fp32 [{rows}, {K}], int64 [{rows}, {K}]) contiguous on {dev}")
+        a.flags = _lib.SD_BEAM_TOPK_GIVEN
+        a.vocab = max(K, 1)
+        state.top_logprob, state.top_token = lpv, tok
+    else:
+        if logits is None:
+            raise ValueError("beam_step needs logits, or topk=(logprob, token) to select from")
+        if logits.dim() != 2 or logits.shape[0] != rows:
+            raise ValueError(f"logits: expected [{rows}, vocab], got {tuple(logits.shape)}")
+        V = logits.shape[1]
+        _require_rows(logits, "logits", V)
+        _beam_check_k(K, V)
+        if logits.device != dev:
+            raise ValueError("logits and the beam state must share a device")
+        a.vocab = V
+        a.logits, a.stride_r, a.dtype = logits.data_ptr(), logits.stride(0), _DT[logits.dtype]
+        if state.top_logprob is None or tuple(state.top_logprob.shape) != (rows, K):
+            state.top_logprob = torch.empty(rows, K, dtype=torch.float32, device=dev)
+            state.top_token = torch.empty(rows, K, dtype=torch.long, device=dev)
+        nbytes = lib.sd_beam_workspace_size(rows, V, K)
+        if nbytes:   # 0: a shape the library refuses; sd_beam_step reports which limit
+            keep = _workspace(nbytes, dev)
+            a.workspace, a.workspace_bytes = keep.data_ptr(), keep.numel()
+    a.top_logprob, a.top_token = state.top_logprob.data_ptr(), state.top_token.data_ptr()
+    stops = stop_tokens if stop_tokens is not None else torch.empty(0, dtype=torch.long, device=dev)
+    if stops.dtype != torch.long or stops.device != dev or not stops.is_contiguous():
+        raise ValueError("stop_tokens must be a contiguous int64 tensor on the state's device")
+    a.stop_tokens, a.n_stop, a.pad_token = (stops.data_ptr() if stops.numel() else None), stops.numel(), int(pad_token_id)
+    src, dst = state._bufs[state._cur], state._bufs[1 - state._cur]
+    a.input_ids_in, a.input_ids_out, a.input_ids_stride = src[0].data_ptr(), dst[0].data_ptr(), L
+    a.probs_in, a.probs_out, a.probs_stride = src[1].data_ptr(), dst[1].data_ptr(), L
+    a.beams_probs_in, a.beams_probs_out = src[2].data_ptr(), dst[2].data_ptr()
+    a.last_index_in, a.last_index_out = src[3].data_ptr(), dst[3].data_ptr()
+    a.all_finished, a.parent = state.all_finished.data_ptr(), state.parent.data_ptr()
+    _lib.check(lib.sd_beam_step(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_beam_step")
+    state._cur = 1 - state._cur
+    del keep
+    return state.all_finished

@@ -13,7 +13,11 @@ GPU), and callable as ``torch.ops.specdec.*``.
         One verify step: rule 0 = sampling/speculative_decoding.py:129-187 (T = γ+1 target rows),
         rule 1 = engine/infer_engine.py:276-336 (T = γ, plain softmax), Philox noise.
 
-Both run the same C-ABI calls as ``specdec_amd.ops`` (libspecdec.so); the parity STREAM noise
+    torch.ops.specdec.beam_topk(logits [R, V], k) -> (logprob fp32 [R, k], token int64 [R, k])
+        The beam step's row pass: topk(log_softmax(logits), k), lowest index first among equal values
+        (sampling/base_decoding.py:136-137).
+
+All run the same C-ABI calls as ``specdec_amd.ops`` (libspecdec.so); the parity STREAM noise
 mode keeps generator state on the host side and stays on the Python API.
 """
 from __future__ import annotations
@@ -72,3 +76,17 @@ def _(target, draft, draft_tokens, stop_tokens, rule, kind, temperature, top_k, 
     return (target.new_empty(B, **i32), target.new_empty(B, dtype=torch.long),
             target.new_empty(B, dtype=torch.float32), target.new_empty(B, **i32), target.new_empty(B, **i32),
             target.new_empty(B, **i32), target.new_empty(B, **i32))
+
+
+@torch.library.custom_op("specdec::beam_topk", mutates_args=())
+def beam_topk(logits: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """topk(log_softmax(logits [R, V], -1), k) in one pass over the rows (sampling/base_decoding.py:
+    136-137): (logprob fp32 [R, k] holding the value rounded to the logits dtype, token int64 [R, k]),
+    value descending, lowest index first among equal values."""
+    return ops.beam_topk(logits, k)
+
+
+@beam_topk.register_fake
+def _(logits, k):
+    R = logits.shape[0]
+    return logits.new_empty(R, k, dtype=torch.float32), logits.new_empty(R, k, dtype=torch.long)

@@ -1,0 +1,106 @@
+// Host-side AddressSanitizer driver for the beam step's C ABI (csrc/beam.hip).  Built by
+// `make -C speculative-decoding_amd asan-beam` from the host-instrumented object (no GPU needed):
+// every argument-validation path of sd_beam_step and sd_beam_workspace_size over many shapes.  No
+// call here reaches a launch — each is refused first — and the fake pointers are never dereferenced.
+// Any ASan report aborts the run.
+#include <cstdio>
+#include <cstring>
+#include <initializer_list>
+
+#include "specdec.h"
+
+static int g_checks = 0, g_fail = 0;
+#define CHECK(cond)                                                                  \
+    do {                                                                             \
+        ++g_checks;                                                                  \
+        if (!(cond)) { ++g_fail; std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); } \
+    } while (0)
+
+static void* fake(uintptr_t k) { return reinterpret_cast<void*>(0x100000 + 0x1000 * k); }   // never dereferenced
+
+static sd_beam_args valid_step() {
+    sd_beam_args a;
+    std::memset(&a, 0, sizeof a);
+    a.mode = SD_BEAM_STEP; a.num_beams = 4; a.top_k = 3; a.vocab = 4096; a.curr = 5; a.total_len = 16; a.lp = 1.25f;
+    a.logits = fake(1); a.stride_r = 4096; a.dtype = SD_BF16;
+    a.input_ids_in = static_cast<const int64_t*>(fake(2)); a.input_ids_out = static_cast<int64_t*>(fake(3));
+    a.probs_in = static_cast<const float*>(fake(4)); a.probs_out = static_cast<float*>(fake(5));
+    a.input_ids_stride = a.probs_stride = 16;
+    a.beams_probs_in = static_cast<const float*>(fake(6)); a.beams_probs_out = static_cast<float*>(fake(7));
+    a.last_index_in = static_cast<const int64_t*>(fake(8)); a.last_index_out = static_cast<int64_t*>(fake(9));
+    a.top_logprob = static_cast<float*>(fake(10)); a.top_token = static_cast<int64_t*>(fake(11));
+    a.all_finished = static_cast<int32_t*>(fake(12));
+    return a;   // everything valid but the workspace
+}
+
+static void step_rejections() {
+    CHECK(sd_beam_step(nullptr, nullptr) == SD_ERR_INVALID);
+    sd_beam_args z;
+    std::memset(&z, 0, sizeof z);
+    CHECK(sd_beam_step(&z, nullptr) == SD_ERR_INVALID);
+    const sd_beam_args a = valid_step();
+    CHECK(sd_beam_step(&a, nullptr) == SD_ERR_WORKSPACE);
+    sd_beam_args b = a;
+    b.workspace = fake(20); b.workspace_bytes = sd_beam_workspace_size(4, 4096, 3) - 1;
+    CHECK(sd_beam_step(&b, nullptr) == SD_ERR_WORKSPACE);
+    b = a; b.mode = 7; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.flags = 0x10; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.num_beams = 0; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.top_k = 0; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.vocab = 0; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.num_beams = SD_BEAM_MAX_BEAMS + 1; b.top_k = 1; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_UNSUPPORTED);
+    b = a; b.top_k = SD_BEAM_MAX_TOPK + 1; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_UNSUPPORTED);
+    b = a; b.num_beams = 64; b.top_k = 17; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_UNSUPPORTED);   // 1088 candidates
+    b = a; b.vocab = SD_BEAM_MAX_VOCAB + 1; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_UNSUPPORTED);
+    b = a; b.vocab = 2; b.stride_r = 2; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);       // top_k > vocab
+    b = a; b.mode = SD_BEAM_PREFILL; b.vocab = 3; b.stride_r = 3; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.dtype = 9; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.logits = nullptr; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.stride_r = 100; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.top_logprob = nullptr; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.top_token = nullptr; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.curr = 0; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.curr = 16; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.lp = 0.f; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.input_ids_stride = 8; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.n_stop = 2; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);                       // stop list missing
+    b = a; b.n_stop = -1; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.all_finished = nullptr; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.last_index_out = nullptr; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.probs_in = nullptr; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    b = a; b.mode = SD_BEAM_TOPK_ONLY; b.flags = SD_BEAM_TOPK_GIVEN; CHECK(sd_beam_step(&b, nullptr) == SD_ERR_INVALID);
+    // the row pass alone needs no state, but its workspace
+    std::memset(&b, 0, sizeof b);
+    b.mode = SD_BEAM_TOPK_ONLY; b.num_beams = 5; b.top_k = 8; b.vocab = 128256; b.logits = fake(1); b.stride_r = 128256;
+    b.dtype = SD_F32; b.top_logprob = static_cast<float*>(fake(10)); b.top_token = static_cast<int64_t*>(fake(11));
+    CHECK(sd_beam_step(&b, nullptr) == SD_ERR_WORKSPACE);
+}
+
+static void workspace_shapes() {
+    CHECK(sd_beam_workspace_size(0, 4096, 3) == 0);
+    CHECK(sd_beam_workspace_size(4, 0, 3) == 0);
+    CHECK(sd_beam_workspace_size(4, 4096, 0) == 0);
+    CHECK(sd_beam_workspace_size(SD_BEAM_MAX_BEAMS + 1, 4096, 3) == 0);
+    CHECK(sd_beam_workspace_size(4, 4096, SD_BEAM_MAX_TOPK + 1) == 0);
+    CHECK(sd_beam_workspace_size(4, SD_BEAM_MAX_VOCAB + 1, 3) == 0);
+    CHECK(sd_beam_workspace_size(4, 2, 3) == 0);   // k > vocab
+    size_t prev = 0;
+    for (int rows : {1, 2, 4, 5, 8, 64})
+        for (int vocab : {1, 64, 2047, 2048, 2049, 4104, 50257, 128256, SD_BEAM_MAX_VOCAB})
+            for (int k : {1, 3, 8, 64}) {
+                if (k > vocab) continue;
+                const size_t n = sd_beam_workspace_size(rows, vocab, k);
+                const size_t chunks = ((size_t)vocab + 2047) / 2048;
+                CHECK(n >= ((size_t)8 << 20) + (size_t)rows * (2 + 2 * (size_t)k) * chunks * 4);   // counter block, then partials
+                CHECK(n % 256 == 0);
+                prev = n > prev ? n : prev;
+            }
+    CHECK(prev == sd_beam_workspace_size(64, SD_BEAM_MAX_VOCAB, 64));   // the largest shape is the largest size
+}
+
+int main() {
+    step_rejections();
+    workspace_shapes();
+    std::printf("%d checks, %d failed\n", g_checks, g_fail);
+    return g_fail ? 1 : 0;
+}
