@@ -318,6 +318,7 @@ typedef enum {
     SD_PATH_VERIFY_TWO_LAUNCH = 3,  /* k_stats (+ decider) then k_sample                          */
     SD_PATH_VERIFY_STREAM = 4,      /* STREAM: k_stats, k_decide, k_walk, k_resample, k_finalize  */
     SD_PATH_VERIFY_FUSED_TICKET = 5,/* k_verify_fused in ticket order (ABI 11): one launch, any B  */
+    SD_PATH_VERIFY_MULTI = 6,       /* sd_verify_multi: k_stats, k_multi_mass x (K+1), k_multi_walk */
     SD_PATH_SAMPLE_DRAW_LEAN = 16,  /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
@@ -558,6 +559,88 @@ typedef struct {
 /* rows / k as the row pass sees them (PREFILL: 1, num_beams).  0 for a bad shape.                    */
 size_t sd_beam_workspace_size(int32_t rows, int32_t vocab, int32_t k);
 int32_t sd_beam_step(const sd_beam_args* args, void* stream);
+
+/* ---- Multi-draft speculative verification (csrc/sd_verify_multi.inc; additive, ABI 12) -----------
+ * One verify step over K independently drafted chains per sequence (SpecInfer's multi-step
+ * speculative sampling / recursive rejection sampling): the walk over the prefix tree of the chains
+ * that keeps the emitted tokens distributed exactly as the target's.  Chain k of sequence b is row
+ * b*K + k of every row set.  Probabilities are SD_RULE_SPEC's (processor, temperature, rounded to
+ * the rows' dtype); target and drafter rows share ONE processor and one dtype.  Per sequence:
+ *
+ *   A = {0..K-1}                                   alive chains (they share the accepted prefix)
+ *   for d in 0..γ'-1:
+ *       k0 = min A;  p = P(target row d of chain k0);  q = P(drafter row d of chain k0);  r = p
+ *       for k in A ascending:
+ *           x = tok[k, d];  u = accept uniform d*K + k
+ *           if not (u > r[x] / q[x]): hit = x, stop testing          (fp32, as SD_RULE_SPEC)
+ *           m = Σ_v max(r[v] - q[v], 0);  r = max(r - q, 0) / m      (one more sibling rejected)
+ *       no hit: n = d, x ~ r, SD_ROW_RESIDUAL, winner = k0, done
+ *       A = {k in A : tok[k, d] == hit}
+ *   n = γ', x ~ P(bonus row of chain min A), SD_ROW_BONUS, winner = min A
+ *
+ * then the stop scan over tok[winner, :n] (SD_ROW_STOP_IN_DRAFTS, stop_index, no token drawn) and the
+ * prune lengths, as sd_verify.  Noise is SD_NOISE_PHILOX only (SD_NOISE_STREAM: SD_ERR_UNSUPPORTED):
+ * sequence b is row row_base + b, the accept uniform of (d, k) is the row's accept uniform number
+ * d*K + k, the sample is drawn by inverse CDF on the row's cdf uniform; one call consumes one offset,
+ * so K = 1 tests and walks exactly as sd_verify(SD_RULE_SPEC) does.
+ * Kernels: the row statistics of all K(2γ'+1) rows per sequence, then K + 1 launches that form the
+ * residual masses m_1..m_K of every (chain, depth) row pair, then one launch that walks and samples.
+ * No workgroup waits on another (launch boundaries only): capturable, safe on a shared GPU.       */
+#define SD_MULTI_MAX_DRAFTS 8      /* K                                                              */
+#define SD_MULTI_MAX_NODES 64      /* K * γ'                                                         */
+#define SD_MULTI_MAX_ROWS 16384    /* B * K                                                          */
+
+typedef struct {
+    int32_t batch;               /* B                                                              */
+    int32_t num_drafts;          /* K, 1..SD_MULTI_MAX_DRAFTS                                       */
+    int32_t gamma;               /* γ', 1..SD_MAX_GAMMA, K * γ' <= SD_MULTI_MAX_NODES               */
+    int32_t vocab;
+    /* rows over the chain axis r = b*K + k: target row t at target_rows[t] + r * target_stride_r
+       (t = γ' is the bonus row), drafter row d at draft_rows[d] + r * draft_stride_r               */
+    const void* target_rows[SD_MAX_GAMMA + 1];
+    int64_t target_stride_r;
+    int32_t target_dtype;        /* sd_dtype                                                       */
+    const void* draft_rows[SD_MAX_GAMMA];
+    int64_t draft_stride_r;
+    int32_t draft_dtype;         /* must equal target_dtype (SD_ERR_UNSUPPORTED otherwise)          */
+    const int64_t* draft_tokens; /* [B*K, >=γ'] drafted ids                                         */
+    int64_t draft_tokens_stride_r;
+    sd_processor proc;           /* the loop's logits_processor, for target and drafter rows       */
+    const int64_t* stop_tokens;  /* device [n_stop]                                                */
+    int32_t n_stop;
+    int64_t pad_token;           /* fills tokens_out past the emitted tokens                        */
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+
+    /* outputs, device, [B] */
+    int32_t* n_accepted;         /* accepted depth n                                               */
+    int32_t* winner;             /* the chain whose first n drafts were accepted (see above)        */
+    int64_t* next_token;         /* x, -1 if none (stop token among the accepted drafts)            */
+    float* resample_mass;        /* mass m of the last residual formed, NaN if none (nullable)      */
+    int32_t* n_sibling_rejects;  /* accept tests that failed (nullable)                             */
+    int32_t* prune_drafter;      /* γ'-n on a residual exit, else 0 (nullable)                      */
+    int32_t* prune_target;       /* γ'-n+1 on a residual exit, else 0 (nullable)                    */
+    int32_t* stop_index;         /* position of the stop token in tok[winner, :n], -1 (nullable)    */
+    int32_t* row_status;         /* SD_ROW_* bits                                                  */
+    /* optional (nullable): int64 [B, >=γ'+1] at tokens_out + b * tokens_out_stride_b: tok[winner, :n],
+       then x (when one was drawn), then pad_token up to γ'+1 entries                               */
+    int64_t* tokens_out;
+    int64_t tokens_out_stride_b;
+
+    void* workspace;             /* sd_verify_multi_workspace_size bytes, zero-filled once; shares
+                                    the other entry points' convention (counter block left at zero) */
+    size_t workspace_bytes;
+    /* optional hints (nullable), as sd_verify's: (max, Σexp) and keep predicates of the drafter rows
+       as sd_sample returned them for the B*K rows of each depth: row d of chain r at
+       draft_row_stats + 2 * (d * draft_row_stats_stride + r), stride >= B*K; draft_row_keep at the
+       same layout, needed with the stats under a top-k / nucleus processor                         */
+    const float* draft_row_stats;
+    int64_t draft_row_stats_stride;
+    const struct sd_row_keep* draft_row_keep;
+    int32_t* status_or;          /* nullable: every sequence's SD_ROW_ERROR_MASK bits ORed in       */
+} sd_multi_args;
+
+size_t sd_verify_multi_workspace_size(int32_t batch, int32_t num_drafts, int32_t gamma, int32_t vocab);
+int32_t sd_verify_multi(const sd_multi_args* args, void* stream);
 
 #ifdef __cplusplus
 }

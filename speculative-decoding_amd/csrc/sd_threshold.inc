@@ -1090,7 +1090,10 @@ bool thr_poll_ok(int64_t wgs) {
     return cap > 0 && wgs <= cap && wgs <= sd::kThrShistSlots;
 }
 
-int32_t launch_threshold(const sd::Plan& P, const sd_processor& tproc, const sd_processor& dproc, void* stream) {
+// allow_poll = false: the launch-per-phase design whatever the option says (sd_verify_multi, whose
+// kernels never wait on another workgroup)
+int32_t launch_threshold(const sd::Plan& P, const sd_processor& tproc, const sd_processor& dproc, void* stream,
+                         bool allow_poll = true) {
     const sd::ThreshRowParams tt{tproc.kind, tproc.top_k, tproc.top_p};
     const sd::ThreshRowParams td{dproc.kind, dproc.top_k, dproc.top_p};
     const bool d_rows = P.slots > P.n_tslots;
@@ -1103,7 +1106,7 @@ int32_t launch_threshold(const sd::Plan& P, const sd_processor& tproc, const sd_
         // the slice maxima exchanged inside k_thr_hist (polled records) when its whole grid is
         // resident; otherwise k_thr_max computes them in a launch of its own
         sd::Plan Q = P;
-        Q.thr_poll = thr_poll_ok((int64_t)nsl * rows);
+        Q.thr_poll = allow_poll && thr_poll_ok((int64_t)nsl * rows);
         if (!Q.thr_poll)
             if (int32_t st = launch(sd::k_thr_max, grid, block, 0, stream, Q, tt, td)) return st;
         if (int32_t st = launch(sd::k_thr_hist, grid, block, 0, stream, Q, tt, td)) return st;

@@ -23,6 +23,9 @@
 // k_draw_lean / k_draw, STREAM k_draw_stream, greedy k_draw_lean<GREEDY>, then the three launches
 // k_stats + k_rowsample + k_sample_finalize.
 //
+// The multi-draft verify (sd_verify_multi, sd_verify_multi.inc): k_stats, then K + 1 mass launches over
+// every (chain, depth) row pair and one walk-and-draw launch; launch boundaries only.
+//
 // Every logit row is read once by the statistics pass (the algorithmic bytes); the sampling pass
 // re-reads at most two rows per sequence (served from the 256 MiB Infinity Cache).  See DESIGN.md.
 #include <hip/hip_runtime.h>
@@ -4439,3 +4442,4 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
 }  // extern "C"
 
 #include "sd_ngram.inc"
+#include "sd_verify_multi.inc"

@@ -38,11 +38,13 @@ SD_OPT_FUSED_TICKET, SD_OPT_DRAW_SPAN, SD_OPT_TICKET_LAG, SD_OPT_SAMP_CHUNKS = 5
 SD_PATH_NONE = 0
 SD_PATH_VERIFY_LEAN, SD_PATH_VERIFY_FUSED, SD_PATH_VERIFY_TWO_LAUNCH, SD_PATH_VERIFY_STREAM = 1, 2, 3, 4
 SD_PATH_VERIFY_FUSED_TICKET = 5
+SD_PATH_VERIFY_MULTI = 6
 SD_PATH_SAMPLE_DRAW_LEAN, SD_PATH_SAMPLE_DRAW, SD_PATH_SAMPLE_NUCLEUS, SD_PATH_SAMPLE_STREAM = 16, 17, 18, 19
 SD_PATH_SAMPLE_GREEDY_LEAN, SD_PATH_SAMPLE_MULTI = 20, 21
 PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PATH_VERIFY_FUSED: "k_verify_fused",
               SD_PATH_VERIFY_FUSED_TICKET: "k_verify_fused(ticket)",
               SD_PATH_VERIFY_TWO_LAUNCH: "k_stats+k_sample", SD_PATH_VERIFY_STREAM: "stream",
+              SD_PATH_VERIFY_MULTI: "k_stats+k_multi_mass+k_multi_walk",
               SD_PATH_SAMPLE_DRAW_LEAN: "k_draw_lean", SD_PATH_SAMPLE_DRAW: "k_draw", SD_PATH_SAMPLE_NUCLEUS: "k_draw_nuc",
               SD_PATH_SAMPLE_STREAM: "k_draw_stream", SD_PATH_SAMPLE_GREEDY_LEAN: "k_draw_lean<greedy>",
               SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize"}
@@ -59,7 +61,11 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_mt19937_char_poly", "sd_mt19937_fill_substreams", "sd_mt19937_generate_workspace_size",
            "sd_mt19937_generate", "sd_mt19937_commit", "sd_set_poll_policy", "sd_get_poll_policy",
            "sd_set_option", "sd_get_option", "sd_last_verify_path", "sd_last_sample_path",
-           "sd_beam_workspace_size", "sd_beam_step")
+           "sd_beam_workspace_size", "sd_beam_step",
+           "sd_verify_multi_workspace_size", "sd_verify_multi")
+
+# multi-draft verify
+SD_MULTI_MAX_DRAFTS, SD_MULTI_MAX_NODES, SD_MULTI_MAX_ROWS = 8, 64, 16384
 
 # beam step (ABI 12)
 SD_BEAM_MAX_BEAMS, SD_BEAM_MAX_TOPK, SD_BEAM_MAX_CANDIDATES, SD_BEAM_MAX_VOCAB = 64, 64, 1024, 524288
@@ -180,6 +186,25 @@ class sd_beam_args(C.Structure):
     ]
 
 
+class sd_multi_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("num_drafts", C.c_int32), ("gamma", C.c_int32), ("vocab", C.c_int32),
+        ("target_rows", C.c_void_p * (SD_MAX_GAMMA + 1)), ("target_stride_r", C.c_int64),
+        ("target_dtype", C.c_int32),
+        ("draft_rows", C.c_void_p * SD_MAX_GAMMA), ("draft_stride_r", C.c_int64), ("draft_dtype", C.c_int32),
+        ("draft_tokens", C.c_void_p), ("draft_tokens_stride_r", C.c_int64),
+        ("proc", sd_processor), ("stop_tokens", C.c_void_p), ("n_stop", C.c_int32), ("pad_token", C.c_int64),
+        ("noise", sd_noise),
+        ("n_accepted", C.c_void_p), ("winner", C.c_void_p), ("next_token", C.c_void_p),
+        ("resample_mass", C.c_void_p), ("n_sibling_rejects", C.c_void_p), ("prune_drafter", C.c_void_p),
+        ("prune_target", C.c_void_p), ("stop_index", C.c_void_p), ("row_status", C.c_void_p),
+        ("tokens_out", C.c_void_p), ("tokens_out_stride_b", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("draft_row_stats", C.c_void_p), ("draft_row_stats_stride", C.c_int64), ("draft_row_keep", C.c_void_p),
+        ("status_or", C.c_void_p),
+    ]
+
+
 def _share_torch_hip_runtime():
     """Load PyTorch-ROCm's bundled HIP runtime first, so libspecdec.so (NEEDED libamdhip64.so.7,
     which that copy's SONAME satisfies) binds to the SAME runtime torch uses instead of loading
@@ -222,6 +247,10 @@ def _load():
     lib.sd_beam_step.argtypes = [C.POINTER(sd_beam_args), C.c_void_p]
     lib.sd_verify.restype = C.c_int32
     lib.sd_verify.argtypes = [C.POINTER(sd_verify_args), C.c_void_p]
+    lib.sd_verify_multi_workspace_size.restype = C.c_size_t
+    lib.sd_verify_multi_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.sd_verify_multi.restype = C.c_int32
+    lib.sd_verify_multi.argtypes = [C.POINTER(sd_multi_args), C.c_void_p]
     lib.sd_sample.restype = C.c_int32
     lib.sd_sample.argtypes = [C.POINTER(sd_sample_args), C.c_void_p]
     lib.sd_probs.restype = C.c_int32

@@ -474,6 +474,130 @@ def verify(target_rows: Sequence[torch.Tensor], draft_rows: Sequence[torch.Tenso
     return out
 
 
+# --------------------------------------------------------------------------- multi-draft verify
+MULTI_FIELDS = ("n_accepted", "winner", "next_token", "resample_mass", "n_sibling_rejects", "prune_drafter",
+                "prune_target", "stop_index", "row_status")
+
+
+def _chain_rows(x, name: str, n_rows: int):
+    """Per-depth row tensors [B*K, V] of a [B, K, n_rows, V] tensor (views), or the sequence given."""
+    if torch.is_tensor(x):
+        if x.dim() != 4 or x.shape[2] != n_rows:
+            raise ValueError(f"{name}: expected [B, K, {n_rows}, V], got {tuple(x.shape)}")
+        B, K, _, V = x.shape
+        if B > 1 and x.stride(0) != K * x.stride(1):
+            x = x.contiguous()
+        return [x[:, :, t, :].as_strided((B * K, V), (x.stride(1), x.stride(3)), x[:, :, t, :].storage_offset())
+                for t in range(n_rows)]
+    return list(x)
+
+
+def verify_multi(target, draft, draft_tokens: torch.Tensor, proc, noise, num_drafts: Optional[int] = None,
+                 stop_tokens: Optional[torch.Tensor] = None, row_base: int = 0,
+                 draft_row_stats: Optional[torch.Tensor] = None, draft_row_keep: Optional[torch.Tensor] = None,
+                 status_or: Optional[torch.Tensor] = None, pad_token_id: int = 0, want_tokens: bool = True):
+    """One multi-draft verify step (sd_verify_multi): K independently drafted chains of γ tokens per
+    sequence, walked as a prefix tree by recursive rejection sampling, so the emitted tokens keep the
+    target's distribution exactly.
+
+    target: [B, K, γ+1, V] logits (or γ+1 tensors [B*K, V], chain k of sequence b at row b*K + k);
+    draft: [B, K, γ, V] (or γ tensors [B*K, V]); draft_tokens: int64 [B, K, >=γ] or [B*K, >=γ].
+    proc: one of the five processors, used for target and drafter rows alike.  noise: PhiloxNoise
+    (one offset per call).  draft_row_stats fp32 [γ, S>=B*K, 2] / draft_row_keep int32 [γ, S, 4]: the
+    drafter rows' statistics as ``sample_rows`` returned them with the draws (hints, as ``verify``'s).
+    Returns a namespace of the [B] outputs n_accepted, winner, next_token, resample_mass,
+    n_sibling_rejects, prune_drafter, prune_target, stop_index, row_status, and tokens_out int64
+    [B, γ+1] (tok[winner, :n], then x, then pad_token_id; None without want_tokens)."""
+    from types import SimpleNamespace
+    if _user_process(proc) is not None:
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: verify_multi fuses the processing "
+                        "of target and drafter rows and cannot run a user _process")
+    spec = proc_spec(proc)
+    if not isinstance(noise, PhiloxNoise):
+        raise TypeError("verify_multi needs PhiloxNoise (the reference defines no stream order for this step)")
+    if torch.is_tensor(target) and num_drafts is None:
+        num_drafts = target.shape[1]
+    K = int(num_drafts) if num_drafts is not None else (draft_tokens.shape[1] if draft_tokens.dim() == 3 else 0)
+    if draft_tokens.dim() == 3:
+        if draft_tokens.shape[1] != K:
+            raise ValueError(f"draft_tokens: expected [B, {K}, >=gamma], got {tuple(draft_tokens.shape)}")
+        draft_tokens = draft_tokens.reshape(-1, draft_tokens.shape[-1])
+    draft_rows = _chain_rows(draft, "draft", draft.shape[2] if torch.is_tensor(draft) else len(draft))
+    gamma = len(draft_rows)
+    target_rows = _chain_rows(target, "target", gamma + 1)
+    if len(target_rows) != gamma + 1:
+        raise ValueError(f"expected {gamma + 1} target rows, got {len(target_rows)}")
+    R, V = target_rows[0].shape
+    if not 1 <= K <= _lib.SD_MULTI_MAX_DRAFTS or R % K or not 1 <= gamma <= _lib.SD_MAX_GAMMA \
+            or K * gamma > _lib.SD_MULTI_MAX_NODES or R > _lib.SD_MULTI_MAX_ROWS:
+        raise ValueError(f"verify_multi: unsupported shape (rows {R}, num_drafts {K}, gamma {gamma}): K in 1..8, "
+                         f"gamma in 1..{_lib.SD_MAX_GAMMA}, K * gamma <= 64, B * K <= 16384")
+    B = R // K
+    dev, tdt = target_rows[0].device, target_rows[0].dtype
+    t_stride = target_rows[0].stride(0) if R > 1 else 0
+    d_stride = draft_rows[0].stride(0) if R > 1 else 0
+    for name, rows, stride in (("target", target_rows, t_stride), ("draft", draft_rows, d_stride)):
+        for i, t in enumerate(rows):
+            _require_rows(t, f"{name}_rows[{i}]", V)
+            if t.shape[0] != R or t.dtype != tdt or (R > 1 and t.stride(0) != stride) or t.device != dev:
+                raise ValueError("target and draft rows must share rows, dtype, row stride and device")
+    if draft_tokens.dtype != torch.long or draft_tokens.dim() != 2 or draft_tokens.shape[0] != R \
+            or draft_tokens.shape[1] < gamma or draft_tokens.stride(1) != 1 or draft_tokens.device != dev:
+        raise ValueError(f"draft_tokens must be int64 [B*K, >={gamma}] on {dev}")
+    stops = stop_tokens if stop_tokens is not None else torch.empty(0, dtype=torch.long, device=dev)
+    if stops.dtype != torch.long or stops.device != dev or not stops.is_contiguous():
+        raise ValueError("stop_tokens must be a contiguous int64 device tensor")
+    if draft_row_stats is not None:
+        ds = draft_row_stats
+        if ds.dtype != torch.float32 or ds.dim() != 3 or ds.shape[0] < gamma or ds.shape[1] < R \
+                or ds.shape[2] != 2 or ds.stride(2) != 1 or ds.stride(1) != 2 or ds.device != dev:
+            raise ValueError(f"draft_row_stats must be fp32 [>={gamma}, >={R}, 2] with (max, sum) pairs on {dev}")
+    if draft_row_keep is not None:
+        dk = draft_row_keep
+        if draft_row_stats is None or dk.dtype != torch.int32 or dk.dim() != 3 or dk.shape[0] < gamma \
+                or dk.shape[1] < R or dk.shape[2] != 4 or dk.stride(2) != 1 or dk.stride(1) != 4 \
+                or dk.stride(0) // 4 != draft_row_stats.stride(0) // 2 or dk.device != dev:
+            raise ValueError("draft_row_keep must be int32 [>=gamma, >=B*K, 4] at draft_row_stats' row stride, "
+                             "and comes with draft_row_stats")
+    # one allocation: next_token (int64) first, then the eight 4-byte fields
+    buf = torch.empty(8 * B + 4 * 8 * B, dtype=torch.uint8, device=dev)
+    nxt = buf[:8 * B].view(torch.long)
+    f4 = buf[8 * B:].view(torch.int32)
+    i32 = [f4[k * B:(k + 1) * B] for k in range(8)]
+    out = SimpleNamespace(n_accepted=i32[0], winner=i32[1], next_token=nxt, resample_mass=i32[2].view(torch.float32),
+                          n_sibling_rejects=i32[3], prune_drafter=i32[4], prune_target=i32[5], stop_index=i32[6],
+                          row_status=i32[7],
+                          tokens_out=torch.empty(B, gamma + 1, dtype=torch.long, device=dev) if want_tokens else None)
+    nz, keep = _noise_struct(noise, 0, dev, row_base)
+    ws = _workspace(lib.sd_verify_multi_workspace_size(B, K, gamma, V), dev)
+    a = _lib.sd_multi_args()
+    a.batch, a.num_drafts, a.gamma, a.vocab = B, K, gamma, V
+    for i, t in enumerate(target_rows):
+        a.target_rows[i] = t.data_ptr()
+    for i, d in enumerate(draft_rows):
+        a.draft_rows[i] = d.data_ptr()
+    a.target_stride_r, a.draft_stride_r = t_stride, d_stride
+    a.target_dtype = a.draft_dtype = _DT[tdt]
+    a.draft_tokens, a.draft_tokens_stride_r = draft_tokens.data_ptr(), draft_tokens.stride(0)
+    a.proc = spec.struct()
+    a.stop_tokens, a.n_stop = (stops.data_ptr() if stops.numel() else None), stops.numel()
+    a.pad_token = int(pad_token_id)
+    a.noise = nz
+    for f in MULTI_FIELDS:
+        setattr(a, f, getattr(out, f).data_ptr())
+    if want_tokens:
+        a.tokens_out, a.tokens_out_stride_b = out.tokens_out.data_ptr(), gamma + 1
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if draft_row_stats is not None:
+        a.draft_row_stats, a.draft_row_stats_stride = draft_row_stats.data_ptr(), draft_row_stats.stride(0) // 2
+    if draft_row_keep is not None:
+        a.draft_row_keep = draft_row_keep.data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_verify_multi(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_verify_multi")
+    del keep
+    return out
+
+
 # --------------------------------------------------------------------------- n-gram verify (A11)
 @dataclass
 class NgramOut:

@@ -1,2 +1,3 @@
 from .base_decoding import autoregressive_generate, beam_search_generate  # noqa: F401
 from .speculative_decoding import max_fn, speculative_generate  # noqa: F401
+from .multidraft_decoding import multidraft_speculative_generate  # noqa: F401

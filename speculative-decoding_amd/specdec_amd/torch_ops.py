@@ -13,6 +13,12 @@ GPU), and callable as ``torch.ops.specdec.*``.
         One verify step: rule 0 = sampling/speculative_decoding.py:129-187 (T = γ+1 target rows),
         rule 1 = engine/infer_engine.py:276-336 (T = γ, plain softmax), Philox noise.
 
+    torch.ops.specdec.verify_multi(target [B, K, γ+1, V], draft [B, K, γ, V], draft_tokens int64 [B, K, >=γ],
+                                   stop_tokens int64 [n], kind, temperature, top_k, top_p, seed, offset, row_base)
+        -> (n_accepted, winner int32 [B], next_token int64 [B], resample_mass fp32 [B], n_sibling_rejects,
+            prune_drafter, prune_target, stop_index, row_status int32 [B])
+        One multi-draft verify step over K chains per sequence (sd_verify_multi), Philox noise.
+
     torch.ops.specdec.beam_topk(logits [R, V], k) -> (logprob fp32 [R, k], token int64 [R, k])
         The beam step's row pass: topk(log_softmax(logits), k), lowest index first among equal values
         (sampling/base_decoding.py:136-137).
@@ -76,6 +82,24 @@ def _(target, draft, draft_tokens, stop_tokens, rule, kind, temperature, top_k, 
     return (target.new_empty(B, **i32), target.new_empty(B, dtype=torch.long),
             target.new_empty(B, dtype=torch.float32), target.new_empty(B, **i32), target.new_empty(B, **i32),
             target.new_empty(B, **i32), target.new_empty(B, **i32))
+
+
+@torch.library.custom_op("specdec::verify_multi", mutates_args=())
+def verify_multi(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens: Tensor, kind: int,
+                 temperature: float, top_k: int, top_p: float, seed: int, offset: int,
+                 row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """One multi-draft verify step (ops.verify_multi): target [B, K, γ+1, V], draft [B, K, γ, V],
+    draft_tokens int64 [B, K, >=γ]; the nine [B] outputs in ops.MULTI_FIELDS' order."""
+    out = ops.verify_multi(target, draft, draft_tokens, _spec(kind, temperature, top_k, top_p),
+                           PhiloxNoise(seed, offset), stop_tokens=stop_tokens, row_base=row_base, want_tokens=False)
+    return tuple(getattr(out, f).clone() for f in ops.MULTI_FIELDS)   # views of one buffer: outputs may not alias
+
+
+@verify_multi.register_fake
+def _(target, draft, draft_tokens, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
+    B = target.shape[0]
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.MULTI_FIELDS)
 
 
 @torch.library.custom_op("specdec::beam_topk", mutates_args=())

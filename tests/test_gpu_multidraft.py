@@ -1,0 +1,398 @@
+"""sd_verify_multi on the GPU: K drafted chains per sequence verified in one step.
+
+* walks against the host model (tests/multidraft_ref.py over the exact-arithmetic oracle and the
+  numpy Philox) on cases whose drafts the test chooses (tests/multi_walk.py; their coverage is proved
+  on the CPU by tests/test_multidraft_cpu.py);
+* K = 1 against sd_verify(SD_RULE_SPEC) on the same inputs, seed and offset;
+* losslessness on the device: the emitted tokens of 4096 sequences against the exact target;
+* stop lists, workspace reuse across entry points, and the decode loop with its trace.
+
+A sequence whose host walk had an accept test within the device's fp32 tolerance of its threshold
+(`close`) may legitimately differ; at most one per case does (as tests/test_gpu_perfmode.py).
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import multi_walk as mw
+import multidraft_ref as mref
+from oracle import specdec_ref as ref
+from test_gpu_perfmode import chi2_check
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+PAD = -7
+
+
+@pytest.fixture(scope="module")
+def sd():
+    from specdec_amd import _lib, ops
+    from specdec_amd.noise import PhiloxNoise
+    return SimpleNamespace(lib=_lib, ops=ops, PhiloxNoise=PhiloxNoise)
+
+
+def spec_of(sd, p):
+    return sd.ops.ProcSpec(p.kind, p.temperature, p.top_k, p.top_p)
+
+
+def draw_hints(sd, dl, proc):
+    """(stats [γ, B*K, 2], keeps [γ, B*K, 4] or None) of the drafter rows dl [B, K, γ, V] as sd_sample
+    returns them with its draws; the drawn tokens are discarded — the tests choose the drafts."""
+    B, K, g, V = dl.shape
+    spec = spec_of(sd, proc)
+    stats = torch.empty(g, B * K, 2, device=DEV)
+    keeps = torch.empty(g, B * K, 4, dtype=torch.int32, device=DEV) if spec.keeps else None
+    noise = sd.PhiloxNoise(seed=4242)
+    for d in range(g):
+        sd.ops.sample_rows(dl[:, :, d, :].reshape(B * K, V).contiguous(), spec, noise, row_stats_out=stats[d],
+                           row_keep_out=keeps[d] if keeps is not None else None)
+    return stats, keeps
+
+
+def run_multi(sd, tl, dl, tok, proc, seed, off, row_base=0, stops=(), hints=False):
+    kw = {}
+    if hints:
+        kw["draft_row_stats"], kw["draft_row_keep"] = draw_hints(sd, dl, proc)
+    out = sd.ops.verify_multi(tl, dl, tok, spec_of(sd, proc), sd.PhiloxNoise(seed=seed, offset=off),
+                              stop_tokens=torch.tensor(list(stops), dtype=torch.long, device=DEV), row_base=row_base,
+                              pad_token_id=PAD, **kw)
+    assert sd.lib.last_verify_path() == sd.lib.SD_PATH_VERIFY_MULTI
+    return SimpleNamespace(**{f: getattr(out, f).cpu() for f in sd.ops.MULTI_FIELDS}, tokens_out=out.tokens_out.cpu())
+
+
+def mass_tolerance(c, b, r):
+    """The bound on |device mass - host mass| of the last residual formed: 1e-5 (the project's mass
+    tolerance) plus flip_slack summed over the row pair the residual was formed from — how far the
+    rounded probabilities of the target and the drafter row can move when their softmax normalisers
+    are off by 1e-6.  The same bound whatever the number of rejected siblings."""
+    k0, d = r.mass_at
+    proc_l = lambda x: ref.processed_logits(x, c.proc, exact=True) / c.proc.temperature   # noqa: E731
+    return 1e-5 + mw.flip_slack(proc_l(c.tl[b, k0, d]), c.dtype) + mw.flip_slack(proc_l(c.dl[b, k0, d]), c.dtype)
+
+
+def check_case(sd, c, got, rows):
+    L, g, K = sd.lib, c.gamma, c.K
+    close_rows = 0
+    for b, r in enumerate(rows):
+        n, win = int(got.n_accepted[b]), int(got.winner[b])
+        st, x = int(got.row_status[b]), int(got.next_token[b])
+        ints = (n, win, int(got.n_sibling_rejects[b]), int(got.prune_drafter[b]), int(got.prune_target[b]),
+                int(got.stop_index[b]))
+        want = (r.n, r.winner, r.rejects, r.prune_drafter, r.prune_target, r.stop_index)
+        print(f"[multi] b={b} got={ints} want={want} close={r.close} status=0x{st:x} x={x} "
+              f"mass={float(got.resample_mass[b]):.6g}/{r.mass:.6g}")
+        assert st & L.SD_ROW_DONE and not st & L.SD_ROW_ERROR_MASK
+        if ints != want:
+            assert r.close, (b, ints, want)
+            close_rows += 1
+            continue
+        want_bit = {mref.RESIDUAL: L.SD_ROW_RESIDUAL, mref.BONUS: L.SD_ROW_BONUS, mref.STOP: L.SD_ROW_STOP_IN_DRAFTS}
+        assert st & (L.SD_ROW_RESIDUAL | L.SD_ROW_BONUS | L.SD_ROW_STOP_IN_DRAFTS) == want_bit[r.status], (b, hex(st))
+        if r.rejects:
+            tol = mass_tolerance(c, b, r)
+            print(f"[multi-mass] b={b} rejects_at_node={len(r.masses)} dev={abs(float(got.resample_mass[b]) - r.mass):.3g} "
+                  f"bound={tol:.3g} mass={r.mass:.6g}")
+            assert abs(float(got.resample_mass[b]) - r.mass) <= tol, (b, float(got.resample_mass[b]), r.mass, tol)
+        else:
+            assert np.isnan(float(got.resample_mass[b]))
+        row = got.tokens_out[b].tolist()
+        assert row[:n] == c.tok[b, win, :n].tolist()
+        if r.status == mref.STOP:
+            assert x == -1 and row[n:] == [PAD] * (g + 1 - n)
+            continue
+        assert 0 <= x < c.V and row[n] == x and row[n + 1:] == [PAD] * (g - n)
+        if c.proc.stochastic:
+            assert r.weights[x] > 0, (b, x)          # positive weight in the final residual / bonus row
+        else:
+            assert r.weights[x] >= r.weights.max() * (1 - 1e-4), (b, x, r.x)
+    assert close_rows <= 1
+
+
+# ---------------------------------------------------------------- walks against the host model
+def _id(case):
+    B, K, g, V, dt, name = case
+    return f"B{B}-K{K}-g{g}-V{V}-{str(dt).split('.')[-1]}-{name}"
+
+
+@pytest.mark.parametrize("hints", [False, True], ids=["stats-in-verify", "stats-from-draws"])
+@pytest.mark.parametrize("case", mw.grid(), ids=_id)
+def test_walks_equal_the_host_model(sd, case, hints):
+    c = mw.case(*case)
+    rows = mw.host_results(c)
+    got = run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE,
+                    hints=hints)
+    check_case(sd, c, got, rows)
+
+
+# ---------------------------------------------------------------- K = 1 is sd_verify
+@pytest.mark.parametrize("name,V,dtype", [("multinomial", 4096, torch.bfloat16), ("topk50", 1000, torch.float32),
+                                          ("greedy", 50257, torch.float16)])
+def test_one_chain_equals_sd_verify(sd, name, V, dtype):
+    """Every integer output but next_token (whose draw uses one uniform here, two in sd_verify)."""
+    c = mw.case(16, 1, 4, V, dtype, name)
+    stops = [int(c.tok[3, 0, 0])]
+    got = run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE, stops)
+    tl, dl = c.tl[:, 0].to(DEV), c.dl[:, 0].to(DEV)
+    spec = spec_of(sd, c.proc)
+    one = sd.ops.verify([tl[:, t] for t in range(5)], [dl[:, t] for t in range(4)], c.tok[:, 0].to(DEV),
+                        sd.lib.SD_RULE_SPEC, spec, spec, sd.PhiloxNoise(seed=mw.SEED, offset=mw.OFFSET),
+                        torch.tensor(stops, dtype=torch.long, device=DEV), row_base=mw.ROW_BASE)
+    for f in ("n_accepted", "prune_drafter", "prune_target", "stop_index", "row_status"):
+        assert torch.equal(getattr(got, f), getattr(one, f).cpu()), f
+    assert torch.equal(got.winner, torch.zeros(16, dtype=torch.int32))
+    assert torch.equal(got.n_sibling_rejects, (one.n_accepted.cpu() < 4).int())   # one failed test ends a chain
+    assert int((one.row_status.cpu() & sd.lib.SD_ROW_STOP_IN_DRAFTS != 0).sum()) >= 1
+
+
+# ---------------------------------------------------------------- losslessness on the device
+def _context_free(V, dtype, seed):
+    g = torch.Generator().manual_seed(seed)
+    tl = (torch.randn(2, V, generator=g) * 2).to(dtype)               # depth-0 row, depth-1 / bonus row
+    dl = (tl.float() + 0.8 * torch.randn(2, V, generator=g)).to(dtype)
+    proc = mw.PROCS["multinomial"]
+    return tl, dl, ref.process(tl, proc, exact=True).double().numpy(), ref.process(dl, proc, exact=True).double().numpy()
+
+
+@pytest.mark.parametrize("K", [2, 4])
+@pytest.mark.parametrize("V", [64, 1000])
+def test_first_token_keeps_the_target_distribution(sd, V, K):
+    """γ = 1: 4096 sequences with identical rows, chain tokens iid from the exact q on the host; the
+    first emitted token over the batch against the exact processed p."""
+    B = 4096
+    tl, dl, p, q = _context_free(V, torch.bfloat16, 5)
+    rng = np.random.default_rng(100 + K)
+    tok = torch.from_numpy(rng.choice(V, size=(B, K, 1), p=q[0] / q[0].sum()))
+    T = torch.stack([tl[0], tl[1]]).to(DEV).expand(B, K, 2, V)
+    D = dl[:1].to(DEV).expand(B, K, 1, V)
+    got = run_multi(sd, T.contiguous(), D.contiguous(), tok.to(DEV), mw.PROCS["multinomial"], 99, 3)
+    first = got.tokens_out[:, 0].numpy()
+    assert first.min() >= 0
+    chi2_check(first, p[0], f"first token V={V} K={K}")
+
+
+@pytest.mark.parametrize("K", [2, 4])
+@pytest.mark.parametrize("V", [64, 1000])
+def test_token_pairs_keep_the_exact_pair_distribution(sd, V, K):
+    """γ = 2 with depth-context rows (depth 1 has its own target and drafter rows, shared by every
+    chain): the pair (t0, t1) of the sequences that emitted two tokens from those rows (n >= 1: t1 is
+    an accepted depth-1 draft or the depth-1 residual's token), against the host model's exact pair
+    distribution multi_walk.pair_distribution (proved against the enumeration on the CPU)."""
+    B = 4096
+    g = torch.Generator().manual_seed(17)
+    tl = (torch.randn(3, V, generator=g) * 2).to(torch.bfloat16)      # depths 0, 1 and the bonus row
+    dl = (tl[:2].float() + 0.8 * torch.randn(2, V, generator=g)).to(torch.bfloat16)
+    proc = mw.PROCS["multinomial"]
+    p = ref.process(tl, proc, exact=True).double().numpy()
+    q = ref.process(dl, proc, exact=True).double().numpy()
+    rng = np.random.default_rng(200 + K)
+    tok = np.stack([rng.choice(V, size=(B, K), p=q[d] / q[d].sum()) for d in range(2)], axis=-1)
+    T = tl.to(DEV).expand(B, K, 3, V).contiguous()
+    D = dl.to(DEV).expand(B, K, 2, V).contiguous()
+    got = run_multi(sd, T, D, torch.from_numpy(tok).to(DEV), proc, 77, 9)
+    two = got.n_accepted.numpy() >= 1
+    assert two.sum() > B // 8
+    t0, t1 = got.tokens_out[:, 0].numpy()[two], got.tokens_out[:, 1].numpy()[two]
+    w0, w1 = mw.pair_distribution(p[0], q[0], p[1], K)
+    chi2_check(t0 * V + t1, np.outer(w0, w1).reshape(-1), f"pairs V={V} K={K}")
+    chi2_check(t0, w0, f"pairs' first token V={V} K={K}")
+    chi2_check(t1, w1, f"pairs' second token V={V} K={K}")
+
+
+# ---------------------------------------------------------------- stop lists
+@pytest.mark.parametrize("n_stop", [1, 64])
+def test_stop_in_the_winners_accepted_drafts(sd, n_stop):
+    c = mw.case(16, 4, 4, 4096, torch.bfloat16, "multinomial")
+    free = mw.host_results(c)
+    b_hit = next(b for b, r in enumerate(free) if r.n >= 2 and r.winner != 0)
+    r = free[b_hit]
+    stop = int(c.tok[b_hit, r.winner, r.n - 1])
+    filler = [c.V + 10 + i for i in range(n_stop - 1)]                # ids no draft holds
+    stops = filler + [stop]
+    rows = mw.host_results(c, stops)
+    assert rows[b_hit].status == mref.STOP and rows[b_hit].stop_index >= 0
+    got = run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE, stops)
+    check_case(sd, c, got, rows)
+    assert int(got.row_status[b_hit]) & sd.lib.SD_ROW_STOP_IN_DRAFTS
+
+
+# ---------------------------------------------------------------- one workspace, many entry points
+def test_one_workspace_serves_changing_shapes_and_entry_points(sd):
+    shapes = [(16, 4, 4, 4096, torch.bfloat16, "multinomial"), (3, 3, 5, 1000, torch.bfloat16, "topk50"),
+              (1, 8, 8, 4096, torch.float32, "multinomial_T0.7")]
+    cases = [mw.case(*s) for s in shapes]
+    first = [run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE)
+             for c in cases]
+    spec = sd.ops.ProcSpec("multinomial", 1.0)
+    blogits = (torch.randn(4, 4096, generator=torch.Generator().manual_seed(3)) * 3).to(torch.bfloat16).to(DEV)
+    for rnd in range(2):
+        for c, want in zip(cases, first):
+            x = c.tl[:, 0].to(DEV)
+            sd.ops.verify([x[:, t] for t in range(c.gamma + 1)], [c.dl[:, 0, t].to(DEV) for t in range(c.gamma)],
+                          c.tok[:, 0].to(DEV), sd.lib.SD_RULE_SPEC, spec, spec, sd.PhiloxNoise(seed=1, offset=rnd))
+            sd.ops.sample_rows(x[:, 0].contiguous(), spec, sd.PhiloxNoise(seed=2, offset=rnd))
+            sd.ops.beam_topk(x[:, 0].contiguous(), 4)
+            beam = sd.ops.BeamState.start([3, 4, 5, 6], 4, 16, 0, DEV)          # a whole beam step: row pass + selection
+            beam.probs[:, 4:6] = -1.0
+            sd.ops.beam_step(beam, blogits[:, :c.V].contiguous(), 6, top_k=3, length=2, pad_token_id=0)
+            again = run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE)
+            for f in sd.ops.MULTI_FIELDS:
+                assert torch.equal(getattr(again, f), getattr(want, f), ) or f == "resample_mass", f
+            assert torch.equal(torch.nan_to_num(again.resample_mass, nan=-1.0),
+                               torch.nan_to_num(want.resample_mass, nan=-1.0))
+            assert torch.equal(again.tokens_out, want.tokens_out)
+
+
+# ---------------------------------------------------------------- the decode loop
+LOOP_V, LOOP_G, LOOP_TOKENS = 4096, 4, 48
+PROMPT = [5, 17, 101, 9, 2000, 77]
+
+
+def _loop_seed(s):
+    """The PhiloxNoise seed the loop draws from torch's generator after torch.manual_seed(s)."""
+    torch.manual_seed(s)
+    return int(torch.randint(0, 2 ** 62, (1,)).item()) & 0xFFFFFFFFFFFFFFFF
+
+
+@pytest.fixture(scope="module")
+def pair():
+    import fakelm
+    return fakelm.make_pair(LOOP_V, sigma=1.0, device=DEV)
+
+
+def _generate(pair, K, seed, **kw):
+    from specdec_amd.sampling import multidraft_speculative_generate
+    from specdec_amd.utils.logits_processor import MultinomialProcessor
+    target, drafter = pair
+    torch.manual_seed(seed)
+    return multidraft_speculative_generate(PROMPT, drafter, target, gamma=LOOP_G, logits_processor=MultinomialProcessor(1.0),
+                                           max_gen_len=LOOP_TOKENS, eos_tokens_id=[LOOP_V + 5], num_drafts=K, **kw)
+
+
+def test_loop_steps_equal_the_host_model(sd, pair):
+    """Every traced step recomputed from the FakeLM banks by the host model; every row of input_ids
+    the models were handed equals the emitted sequence."""
+    import fakelm
+    target, drafter = pair
+    calls = []
+
+    class Recording(fakelm.FakeLM):
+        def __call__(self, input_ids=None, **kw):
+            calls.append(input_ids.cpu().clone())
+            return super().__call__(input_ids=input_ids, **kw)
+
+    K, s = 4, 3
+    trace = []
+    toks, rate = _generate((Recording(target.bank), drafter), K, s, trace=trace)
+    seq = PROMPT + toks
+    assert len(toks) == LOOP_TOKENS and 0 < rate < 1 and len(trace) >= LOOP_TOKENS // (LOOP_G + 1)
+    seed, proc = _loop_seed(s), mw.PROCS["multinomial"]
+    close = 0
+    for st in trace:
+        cur, g, tok = st["cur"], st["g"], st["draft_tokens"].numpy()
+        assert tok.shape == (K, g)
+        P, Q = mw.step_rows(target, drafter, seq[cur - 1], cur, tok, proc)
+        r = mref.philox_step(P, Q, tok, seed, st["offset"], 0)
+        got, want = (st["n"], st["winner"], st["sibling_rejects"]), (r.n, r.winner, r.rejects)
+        print(f"[multi] step cur={cur} g={g} got={got} want={want} close={r.close}")
+        if got != want:
+            assert r.close, (cur, got, want)
+            close += 1
+        assert seq[cur:cur + st["n"]] == tok[st["winner"], :st["n"]].tolist() and seq[cur + st["n"]] == st["x"]
+        assert r.weights[st["x"]] > 0 or got != want
+    assert close <= 1
+    assert sum(st["n"] for st in trace) / sum(st["g"] for st in trace) == pytest.approx(rate)
+    # the target saw, at every step, K identical rows of the sequence emitted so far
+    # (the target's forwards after the first are the steps, in order)
+    for st, ids in zip(trace, calls[1:]):
+        cur = st["cur"]
+        assert tuple(ids.shape) == (K, cur + st["g"])
+        assert all(ids[k, :cur].tolist() == seq[:cur] for k in range(K))
+        assert torch.equal(ids[:, cur:], st["draft_tokens"])
+
+
+def test_loop_with_one_draft_is_speculative_generate(sd, pair):
+    import specdec_amd
+    from specdec_amd.sampling import speculative_generate
+    from specdec_amd.utils.logits_processor import MultinomialProcessor
+    target, drafter = pair
+    toks, rate = _generate(pair, 1, 11)
+    specdec_amd.set_noise_mode("philox", _loop_seed(11))
+    try:
+        want = speculative_generate(PROMPT, drafter, target, gamma=LOOP_G, logits_processor=MultinomialProcessor(1.0),
+                                    max_gen_len=LOOP_TOKENS, eos_tokens_id=[LOOP_V + 5])
+    finally:
+        specdec_amd.set_noise_mode("stream")
+    assert (toks, rate) == want
+
+
+def test_loop_with_a_cache_emits_the_same_tokens(sd, pair):
+    """use_cache=True on a model whose cache records each row's ids, offers batch_select_indices and
+    crop, and asserts on every forward that the cached ids equal that row's prefix."""
+    import fakelm
+    target, drafter = pair
+    forwards = []
+
+    class IdCache:
+        def __init__(self, ids):
+            self.ids = ids
+
+        def get_seq_length(self):
+            return self.ids.shape[1]
+
+        def crop(self, max_length):
+            self.ids = self.ids[:, :max_length]      # negative: drop the last -max_length positions
+
+        def batch_select_indices(self, idx):
+            self.ids = self.ids[idx]
+
+    class Cached(fakelm.FakeLM):
+        def __call__(self, input_ids=None, past_key_values=None, use_cache=False, **kw):
+            assert use_cache
+            off = past_key_values.get_seq_length() if past_key_values is not None else 0
+            full = input_ids._base if input_ids._base is not None else input_ids   # the loop's [K, total_len] ids
+            assert input_ids.storage_offset() % full.stride(0) == off
+            if past_key_values is not None:
+                assert torch.equal(past_key_values.ids, full[:, :off]), "cached ids differ from the row's prefix"
+            forwards.append(off)
+            pos = torch.arange(off, off + input_ids.shape[1], device=input_ids.device)
+            logits = self.bank[(input_ids * 31 + pos * self.pos_mult) % self.bank.shape[0]]
+            return SimpleNamespace(logits=logits, past_key_values=IdCache(full[:, :off + input_ids.shape[1]].clone()))
+
+    plain = _generate(pair, 4, 5)
+    cached = _generate((Cached(target.bank), Cached(drafter.bank)), 4, 5, use_cache=True)
+    assert cached == plain
+    assert sum(1 for off in forwards if off > 0) > len(forwards) // 2      # the cache was really used
+
+    # FakeLM's own cache has crop but no batch_select_indices
+    with pytest.raises(ValueError, match="Unsupported cache type"):
+        _generate((fakelm.FakeLM(target.bank), fakelm.FakeLM(drafter.bank)), 4, 5, use_cache=True)
+
+
+def test_four_drafts_accept_at_least_as_many_as_one(sd, pair):
+    """Summed over 8 seeds.  The host model's simulation of this pair (tests/test_multidraft_cpu.py)
+    puts the gain at about +26 % accepted drafts per step, so the inequality is no coin flip.  Steps
+    and speculated drafts are counted from the models' forwards (one target forward per step after
+    the first, one drafter forward per speculated depth)."""
+    import fakelm
+    target, drafter = pair
+
+    class Counting(fakelm.FakeLM):
+        calls = 0
+
+        def __call__(self, **kw):
+            self.calls += 1
+            return super().__call__(**kw)
+
+    per_step = {}
+    for K in (1, 4):
+        acc = steps = 0
+        for s in range(8):
+            t, d = Counting(target.bank), Counting(drafter.bank)
+            toks, rate = _generate((t, d), K, 100 + s)
+            acc += round(rate * d.calls)
+            steps += t.calls - 1
+        per_step[K] = acc / steps
+    print(f"[multi] accepted drafts per step: K=1 {per_step[1]:.3f}, K=4 {per_step[4]:.3f}")
+    assert per_step[4] >= per_step[1]
