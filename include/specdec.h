@@ -319,6 +319,7 @@ typedef enum {
     SD_PATH_VERIFY_STREAM = 4,      /* STREAM: k_stats, k_decide, k_walk, k_resample, k_finalize  */
     SD_PATH_VERIFY_FUSED_TICKET = 5,/* k_verify_fused in ticket order (ABI 11): one launch, any B  */
     SD_PATH_VERIFY_MULTI = 6,       /* sd_verify_multi: k_stats, k_multi_mass x (K+1), k_multi_walk */
+    SD_PATH_VERIFY_VP = 7,          /* sd_vp_finish: the vocabulary-parallel step's last phase    */
     SD_PATH_SAMPLE_DRAW_LEAN = 16,  /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
@@ -641,6 +642,128 @@ typedef struct {
 
 size_t sd_verify_multi_workspace_size(int32_t batch, int32_t num_drafts, int32_t gamma, int32_t vocab);
 int32_t sd_verify_multi(const sd_multi_args* args, void* stream);
+
+/* ---- Vocabulary-parallel verify (csrc/vocab_parallel.hip; additive, ABI 12) -----------------------
+ * One SD_RULE_SPEC verify step on the logits as a tensor-parallel forward leaves them: S ranks
+ * ("shards") 0..S-1, shard s holding columns [off_s, off_s + V_s) of every row, off_0 = 0,
+ * off_{s+1} = off_s + V_s, Σ V_s = V, V_s >= 1 (slices may be uneven and may start at any element).
+ * γ' is 0..SD_MAX_GAMMA; γ' = 0 samples the one target row.  Probabilities are SPEC's
+ * (round_dt(softmax(round_dt(l / T)))); processors SD_PROC_GREEDY and SD_PROC_MULTINOMIAL at any
+ * temperature (top-k / nucleus: SD_ERR_UNSUPPORTED); noise SD_NOISE_PHILOX only (STREAM:
+ * SD_ERR_UNSUPPORTED); target and drafter rows share one dtype.  Three calls per step, with one
+ * all-gather of a few hundred bytes per sequence after each of the first two; logit rows never move:
+ *
+ *   sd_vp_stats    (m, S = Σ exp(y - m)) over the slice of each of the 2γ'+1 rows of a sequence
+ *                  (target rows 0..γ', then drafter rows 0..γ'-1), and the processed logit y of
+ *                  tok[d] in target row d and drafter row d where the slice owns tok[d]
+ *                  -> stats_local: an sd_vp_header, then sd_vp_stat[B][2γ'+1]
+ *   (exchange 1)   all-gather of the S blocks into stats_all, shard-major
+ *   sd_vp_decide   every shard alike: the partials of each row merged IN ASCENDING SHARD ORDER by one
+ *                  fixed online merge (so all ranks hold bit-identical normalisers and decide alike),
+ *                  p(x_d), q(x_d) from the owner's y, SPEC's test on accept uniform d of global row
+ *                  row_base + b (sd_verify's uniform: n, the status bits, the stop scan and the prune
+ *                  lengths equal sd_verify(SD_RULE_SPEC) on the whole rows up to the rounding of the
+ *                  normalisers).  Then, over the shard's own slice, the weights w = (p_n - q_n)+ on a
+ *                  reject (p_n with skip_sample_adjustment, the bonus row on full accept): the local
+ *                  mass M_s = Σ w (fp32 totals of 2048-element chunks, summed in fp64 in chunk order)
+ *                  and the local candidate — stochastic: inverse CDF over the slice on
+ *                  u2 = cdf uniform idx 1 of the row; greedy: (max w, lowest global index)
+ *                  -> cand_local: an sd_vp_header, then sd_vp_cand[B]
+ *   (exchange 2)   all-gather of the S blocks into cand_all
+ *   sd_vp_finish   every shard alike.  Stochastic: M = Σ M_s (fp64, shard order; M <= 0 or not finite:
+ *                  SD_ROW_INVALID_DIST), the first shard s* with Σ_{s<=s*} M_s > u1 M (u1 = cdf uniform
+ *                  idx 0; the last shard with positive mass if rounding runs past the end), x = its
+ *                  candidate.  Greedy: the candidate of largest weight, lowest global index among
+ *                  equals.  resample_mass = (float)M when a residual was formed, else NaN.
+ *
+ * P(x = j) = (M_s/M)(w_j/M_s) = w_j/M as u1, u2 are independent Philox blocks: exact.  next_token
+ * depends on the sharding; n and the status do not.  One step consumes one Philox offset.  A layout
+ * that does not partition [0, V) (a block whose header names another shard, gaps, Σ V_s != V) flags
+ * every row SD_ROW_INVALID_DIST.  Launch boundaries are the only synchronisation: capturable, safe
+ * on a GPU that collective kernels share.                                                          */
+#define SD_VP_MAX_SHARDS 64
+#define SD_VP_MAX_BATCH 1024
+#define SD_VP_MAX_VOCAB_LOCAL 2097152   /* 1024 chunks of 2048 elements per slice                   */
+#define SD_VP_MAGIC 0x53445650          /* "SDVP"                                                   */
+#define SD_VP_STAT_OWNS 0x1             /* sd_vp_stat.flags: this slice holds the row's drafted id   */
+
+typedef struct sd_vp_header {           /* 32 bytes: the front of every exchanged block              */
+    int32_t magic;                      /* SD_VP_MAGIC                                              */
+    int32_t shard, num_shards;
+    int32_t vocab_offset, vocab_local, vocab;
+    int32_t batch, gamma;
+} sd_vp_header;
+
+typedef struct sd_vp_stat {             /* 16 bytes: one per (sequence, row)                         */
+    float m;                            /* max of the processed slice (-inf: nothing finite)         */
+    float s;                            /* Σ exp(y - m) over the slice                               */
+    float y_tok;                        /* processed logit of the row's drafted id (SD_VP_STAT_OWNS) */
+    int32_t flags;
+} sd_vp_stat;
+
+typedef struct sd_vp_cand {             /* 32 bytes: one per sequence                                */
+    double mass;                        /* M_s                                                      */
+    int64_t token;                      /* the shard's candidate, a GLOBAL id; -1: none              */
+    float weight;                       /* w of the candidate                                        */
+    int32_t status;                     /* the decision's SD_ROW_* bits (the same on every shard)    */
+    int32_t n_accepted;
+    int32_t stop_index;
+} sd_vp_cand;
+
+typedef struct {
+    int32_t batch;               /* B, 1..SD_VP_MAX_BATCH                                          */
+    int32_t gamma;               /* γ', 0..SD_MAX_GAMMA                                            */
+    int32_t vocab;               /* V, the whole vocabulary                                        */
+    int32_t vocab_offset;        /* off_s                                                          */
+    int32_t vocab_local;         /* V_s                                                            */
+    int32_t shard;               /* s                                                              */
+    int32_t num_shards;          /* S, 1..SD_VP_MAX_SHARDS                                         */
+    int32_t dtype;               /* sd_dtype of target and drafter rows                            */
+    /* row t of sequence b: element 0 OF THE SLICE at target_rows[t] + b * target_stride_b          */
+    const void* target_rows[SD_MAX_GAMMA + 1];
+    int64_t target_stride_b;
+    const void* draft_rows[SD_MAX_GAMMA];
+    int64_t draft_stride_b;
+    const int64_t* draft_tokens; /* [B, >=γ'] drafted ids (global); nullable when γ' = 0            */
+    int64_t draft_tokens_stride_b;
+    sd_processor proc;           /* the loop's logits_processor, for target and drafter rows       */
+    int32_t skip_sample_adjustment;
+    int32_t n_stop;
+    const int64_t* stop_tokens;  /* device [n_stop]                                                */
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+    /* exchange buffers, device: one block is sd_vp_stats_bytes / sd_vp_cand_bytes bytes; the _all
+       buffers hold S blocks, shard-major                                                          */
+    void* stats_local;           /* written by sd_vp_stats                                         */
+    const void* stats_all;       /* read by sd_vp_decide                                           */
+    void* cand_local;            /* written by sd_vp_decide                                        */
+    const void* cand_all;        /* read by sd_vp_finish                                           */
+    /* outputs of sd_vp_finish, device, [B], as sd_verify's                                        */
+    int32_t* n_accepted;
+    int64_t* next_token;
+    float* resample_mass;        /* nullable                                                       */
+    int32_t* prune_drafter;      /* nullable                                                       */
+    int32_t* prune_target;       /* nullable                                                       */
+    int32_t* stop_index;         /* nullable                                                       */
+    int32_t* row_status;
+    int32_t* owner_shard;        /* nullable: s*, or the winning shard under greedy; -1: no token  */
+    int32_t* status_or;          /* nullable: every row's SD_ROW_ERROR_MASK bits ORed in           */
+    void* workspace;             /* sd_vp_workspace_size bytes, zero-filled once; the common counter
+                                    block at its front is never written, so one workspace may serve
+                                    sd_vp_*, sd_verify, sd_sample, sd_verify_multi and sd_beam_step
+                                    calls in any order on one stream                               */
+    size_t workspace_bytes;
+} sd_vp_args;
+
+/* bytes of ONE shard's block, header included; 0 for a bad shape                                   */
+size_t sd_vp_stats_bytes(int32_t batch, int32_t gamma);
+size_t sd_vp_cand_bytes(int32_t batch);
+size_t sd_vp_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local);
+/* Each call reads only what its phase needs: sd_vp_stats the rows, draft_tokens, stats_local;
+ * sd_vp_decide those and stats_all, cand_local, the stop list, the noise; sd_vp_finish cand_all, the
+ * noise and the outputs (the rows may be gone).  All three take the workspace.                     */
+int32_t sd_vp_stats(const sd_vp_args* args, void* stream);
+int32_t sd_vp_decide(const sd_vp_args* args, void* stream);
+int32_t sd_vp_finish(const sd_vp_args* args, void* stream);
 
 #ifdef __cplusplus
 }

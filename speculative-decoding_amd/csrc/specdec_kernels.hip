@@ -4186,6 +4186,8 @@ int32_t sd_get_option(int32_t option, int32_t* value) {
 }
 
 int32_t sd_last_verify_path(void) { return g_verify_path; }
+// the library's other translation units (csrc/vocab_parallel.hip) report their path here; not exported
+__attribute__((visibility("hidden"))) void sd_internal_set_verify_path(int32_t path) { g_verify_path = path; }
 int32_t sd_last_sample_path(void) { return g_sample_path; }
 
 const char* sd_status_string(int32_t s) {

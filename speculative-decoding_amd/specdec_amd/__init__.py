@@ -6,7 +6,10 @@ Module layout mirrors the reference's import paths for the hot path:
     specdec_amd.utils.logits_processor   <- utils/logits_processor.py
     specdec_amd.utils.caching            <- utils/caching.py
     specdec_amd.sampling                 <- sampling/speculative_decoding.py (speculative_generate, max_fn);
-                                            multidraft_speculative_generate (K draft chains per step)
+                                            multidraft_speculative_generate (K draft chains per step);
+                                            vocab_parallel_speculative_generate (tensor-parallel target)
+    specdec_amd.vocab_parallel           verify on vocabulary slices (VocabShard, verify_vocab_parallel,
+                                            GroupExchange, LocalShards)
     specdec_amd.engine.infer_engine      <- engine/infer_engine.py (infer_batch, run_batch_speculative,
                                             batch_speculative_generate)
     specdec_amd.engine.metrics           <- engine/metrics.py (the bookkeeping dataclasses it feeds)
@@ -17,7 +20,9 @@ from . import _lib  # noqa: F401  (loads libspecdec.so or raises)
 from ._lib import RowError, get_poll_policy, set_poll_policy  # noqa: F401
 from .noise import PhiloxNoise, StreamNoise, default_noise, set_noise_mode  # noqa: F401
 from .ops import ProcSpec, proc_spec, probs_rows, sample_rows, verify, verify_multi  # noqa: F401
+from .vocab_parallel import GroupExchange, LocalShards, VocabShard, verify_vocab_parallel  # noqa: F401
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.specdec.sample / .verify)
 
 __all__ = ["RowError", "get_poll_policy", "set_poll_policy", "PhiloxNoise", "StreamNoise", "default_noise", "set_noise_mode", "ProcSpec", "proc_spec",
-           "probs_rows", "sample_rows", "verify", "verify_multi"]
+           "probs_rows", "sample_rows", "verify", "verify_multi", "GroupExchange", "LocalShards", "VocabShard",
+           "verify_vocab_parallel"]

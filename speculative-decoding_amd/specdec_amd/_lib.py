@@ -39,12 +39,14 @@ SD_PATH_NONE = 0
 SD_PATH_VERIFY_LEAN, SD_PATH_VERIFY_FUSED, SD_PATH_VERIFY_TWO_LAUNCH, SD_PATH_VERIFY_STREAM = 1, 2, 3, 4
 SD_PATH_VERIFY_FUSED_TICKET = 5
 SD_PATH_VERIFY_MULTI = 6
+SD_PATH_VERIFY_VP = 7
 SD_PATH_SAMPLE_DRAW_LEAN, SD_PATH_SAMPLE_DRAW, SD_PATH_SAMPLE_NUCLEUS, SD_PATH_SAMPLE_STREAM = 16, 17, 18, 19
 SD_PATH_SAMPLE_GREEDY_LEAN, SD_PATH_SAMPLE_MULTI = 20, 21
 PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PATH_VERIFY_FUSED: "k_verify_fused",
               SD_PATH_VERIFY_FUSED_TICKET: "k_verify_fused(ticket)",
               SD_PATH_VERIFY_TWO_LAUNCH: "k_stats+k_sample", SD_PATH_VERIFY_STREAM: "stream",
               SD_PATH_VERIFY_MULTI: "k_stats+k_multi_mass+k_multi_walk",
+              SD_PATH_VERIFY_VP: "k_vp_stats+k_vp_decide+k_vp_finish",
               SD_PATH_SAMPLE_DRAW_LEAN: "k_draw_lean", SD_PATH_SAMPLE_DRAW: "k_draw", SD_PATH_SAMPLE_NUCLEUS: "k_draw_nuc",
               SD_PATH_SAMPLE_STREAM: "k_draw_stream", SD_PATH_SAMPLE_GREEDY_LEAN: "k_draw_lean<greedy>",
               SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize"}
@@ -62,7 +64,14 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_mt19937_generate", "sd_mt19937_commit", "sd_set_poll_policy", "sd_get_poll_policy",
            "sd_set_option", "sd_get_option", "sd_last_verify_path", "sd_last_sample_path",
            "sd_beam_workspace_size", "sd_beam_step",
-           "sd_verify_multi_workspace_size", "sd_verify_multi")
+           "sd_verify_multi_workspace_size", "sd_verify_multi",
+           "sd_vp_stats_bytes", "sd_vp_cand_bytes", "sd_vp_workspace_size", "sd_vp_stats", "sd_vp_decide",
+           "sd_vp_finish")
+
+# vocabulary-parallel verify
+SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
+SD_VP_MAGIC = 0x53445650
+SD_VP_STAT_OWNS = 0x1
 
 # multi-draft verify
 SD_MULTI_MAX_DRAFTS, SD_MULTI_MAX_NODES, SD_MULTI_MAX_ROWS = 8, 64, 16384
@@ -205,6 +214,37 @@ class sd_multi_args(C.Structure):
     ]
 
 
+class sd_vp_header(C.Structure):
+    _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
+                ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
+
+
+class sd_vp_stat(C.Structure):
+    _fields_ = [("m", C.c_float), ("s", C.c_float), ("y_tok", C.c_float), ("flags", C.c_int32)]
+
+
+class sd_vp_cand(C.Structure):
+    _fields_ = [("mass", C.c_double), ("token", C.c_int64), ("weight", C.c_float), ("status", C.c_int32),
+                ("n_accepted", C.c_int32), ("stop_index", C.c_int32)]
+
+
+class sd_vp_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("gamma", C.c_int32), ("vocab", C.c_int32), ("vocab_offset", C.c_int32),
+        ("vocab_local", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("dtype", C.c_int32),
+        ("target_rows", C.c_void_p * (SD_MAX_GAMMA + 1)), ("target_stride_b", C.c_int64),
+        ("draft_rows", C.c_void_p * SD_MAX_GAMMA), ("draft_stride_b", C.c_int64),
+        ("draft_tokens", C.c_void_p), ("draft_tokens_stride_b", C.c_int64),
+        ("proc", sd_processor), ("skip_sample_adjustment", C.c_int32), ("n_stop", C.c_int32),
+        ("stop_tokens", C.c_void_p), ("noise", sd_noise),
+        ("stats_local", C.c_void_p), ("stats_all", C.c_void_p), ("cand_local", C.c_void_p), ("cand_all", C.c_void_p),
+        ("n_accepted", C.c_void_p), ("next_token", C.c_void_p), ("resample_mass", C.c_void_p),
+        ("prune_drafter", C.c_void_p), ("prune_target", C.c_void_p), ("stop_index", C.c_void_p),
+        ("row_status", C.c_void_p), ("owner_shard", C.c_void_p), ("status_or", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 def _share_torch_hip_runtime():
     """Load PyTorch-ROCm's bundled HIP runtime first, so libspecdec.so (NEEDED libamdhip64.so.7,
     which that copy's SONAME satisfies) binds to the SAME runtime torch uses instead of loading
@@ -251,6 +291,15 @@ def _load():
     lib.sd_verify_multi_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.sd_verify_multi.restype = C.c_int32
     lib.sd_verify_multi.argtypes = [C.POINTER(sd_multi_args), C.c_void_p]
+    lib.sd_vp_stats_bytes.restype = C.c_size_t
+    lib.sd_vp_stats_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.sd_vp_cand_bytes.restype = C.c_size_t
+    lib.sd_vp_cand_bytes.argtypes = [C.c_int32]
+    lib.sd_vp_workspace_size.restype = C.c_size_t
+    lib.sd_vp_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    for name in ("sd_vp_stats", "sd_vp_decide", "sd_vp_finish"):
+        getattr(lib, name).restype = C.c_int32
+        getattr(lib, name).argtypes = [C.POINTER(sd_vp_args), C.c_void_p]
     lib.sd_sample.restype = C.c_int32
     lib.sd_sample.argtypes = [C.POINTER(sd_sample_args), C.c_void_p]
     lib.sd_probs.restype = C.c_int32

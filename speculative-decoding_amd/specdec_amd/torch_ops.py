@@ -23,6 +23,18 @@ GPU), and callable as ``torch.ops.specdec.*``.
         The beam step's row pass: topk(log_softmax(logits), k), lowest index first among equal values
         (sampling/base_decoding.py:136-137).
 
+    torch.ops.specdec.vp_stats(target [B, γ+1, V_s], draft [B, γ, V_s], draft_tokens int64 [B, >=γ], shard,
+                               num_shards, vocab_offset, vocab, kind, temperature) -> stats block uint8 [n]
+    torch.ops.specdec.vp_decide(target, draft, draft_tokens, stop_tokens, stats_all uint8 [S, n], shard, num_shards,
+                                vocab_offset, vocab, kind, temperature, skip_sample_adjustment, seed, offset,
+                                row_base) -> candidate block uint8 [m]
+    torch.ops.specdec.vp_finish(cand_all uint8 [S, m], gamma, shard, num_shards, vocab_offset, vocab_local, vocab,
+                                kind, seed, offset, row_base)
+        -> (n_accepted int32 [B], next_token int64 [B], resample_mass fp32 [B], prune_drafter, prune_target,
+            stop_index, row_status, owner_shard int32 [B])
+        The three phases of the vocabulary-parallel verify on one rank's slices (sd_vp_stats / sd_vp_decide /
+        sd_vp_finish; specdec_amd.vocab_parallel); the caller all-gathers the blocks between them.
+
 All run the same C-ABI calls as ``specdec_amd.ops`` (libspecdec.so); the parity STREAM noise
 mode keeps generator state on the host side and stays on the Python API.
 """
@@ -34,6 +46,7 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
+from . import vocab_parallel as vp
 from .noise import PhiloxNoise
 
 _KINDS = {v: k for k, v in ops.KIND.items()}
@@ -100,6 +113,64 @@ def _(target, draft, draft_tokens, stop_tokens, kind, temperature, top_k, top_p,
     B = target.shape[0]
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
     return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.MULTI_FIELDS)
+
+
+def _vp_step(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens, shard: int, num_shards: int,
+             vocab_offset: int, vocab: int, kind: int, temperature: float, skip: bool, seed: int, offset: int,
+             row_base: int) -> vp._Step:
+    sh = vp.VocabShard(shard, num_shards, vocab_offset, target.shape[-1], vocab)
+    nz, _ = ops._noise_struct(PhiloxNoise(seed, offset), 0, target.device, row_base)
+    return vp._step_of(target, draft if draft.shape[1] else None, draft_tokens, vp._vp_spec(_spec(kind, temperature, 0, 1.0)),
+                       nz, sh, stop_tokens, skip)
+
+
+@torch.library.custom_op("specdec::vp_stats", mutates_args=())
+def vp_stats(target: Tensor, draft: Tensor, draft_tokens: Tensor, shard: int, num_shards: int, vocab_offset: int,
+             vocab: int, kind: int, temperature: float) -> Tensor:
+    """Phase 1 of the vocabulary-parallel verify on this rank's slices: its statistics block."""
+    return _vp_step(target, draft, draft_tokens, None, shard, num_shards, vocab_offset, vocab, kind, temperature, False,
+                    0, 0, 0).stats()
+
+
+@vp_stats.register_fake
+def _(target, draft, draft_tokens, shard, num_shards, vocab_offset, vocab, kind, temperature):
+    B, g = target.shape[0], target.shape[1] - 1
+    return target.new_empty(32 + B * (2 * g + 1) * 16, dtype=torch.uint8)
+
+
+@torch.library.custom_op("specdec::vp_decide", mutates_args=())
+def vp_decide(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens: Tensor, stats_all: Tensor, shard: int,
+              num_shards: int, vocab_offset: int, vocab: int, kind: int, temperature: float,
+              skip_sample_adjustment: bool, seed: int, offset: int, row_base: int) -> Tensor:
+    """Phase 3: the decision (the same on every rank) and this rank's candidate block."""
+    return _vp_step(target, draft, draft_tokens, stop_tokens, shard, num_shards, vocab_offset, vocab, kind, temperature,
+                    skip_sample_adjustment, seed, offset, row_base).decide(stats_all)
+
+
+@vp_decide.register_fake
+def _(target, draft, draft_tokens, stop_tokens, stats_all, shard, num_shards, vocab_offset, vocab, kind, temperature,
+      skip_sample_adjustment, seed, offset, row_base):
+    return target.new_empty(32 + target.shape[0] * 32, dtype=torch.uint8)
+
+
+@torch.library.custom_op("specdec::vp_finish", mutates_args=())
+def vp_finish(cand_all: Tensor, gamma: int, shard: int, num_shards: int, vocab_offset: int, vocab_local: int,
+              vocab: int, kind: int, seed: int, offset: int,
+              row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Phase 5: the shard pick and the step's outputs, in vocab_parallel.VP_FIELDS' order."""
+    B = (cand_all.shape[1] - 32) // 32
+    sh = vp.VocabShard(shard, num_shards, vocab_offset, vocab_local, vocab)
+    nz, _ = ops._noise_struct(PhiloxNoise(seed, offset), 0, cand_all.device, row_base)
+    st = vp._Step(B, gamma, cand_all.device, torch.float32, sh, vp._vp_spec(_spec(kind, 1.0, 0, 1.0)), nz)
+    out = st.finish(cand_all)
+    return tuple(getattr(out, f).clone() for f in vp.VP_FIELDS)   # views of one buffer: outputs may not alias
+
+
+@vp_finish.register_fake
+def _(cand_all, gamma, shard, num_shards, vocab_offset, vocab_local, vocab, kind, seed, offset, row_base):
+    B = (cand_all.shape[1] - 32) // 32
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(cand_all.new_empty(B, dtype=dt.get(f, torch.int32)) for f in vp.VP_FIELDS)
 
 
 @torch.library.custom_op("specdec::beam_topk", mutates_args=())
