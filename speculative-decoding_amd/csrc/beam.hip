@@ -18,23 +18,20 @@
 // The score arithmetic is one correctly rounded fp32 add and one IEEE fp32 division per candidate
 // (__fadd_rn / __fdiv_rn: never contracted, never a reciprocal multiply), as torch does on the CPU.
 #include "sd_device.h"
+#include "sd_host.h"
 
 namespace sd {
 
 constexpr int kBeamSpan = kThreads * 8;   // elements per k_beam_topk workgroup
-// The workspace convention of every sd_* layout (specdec_kernels.hip, carve()): a fixed block of
-// 4 sets x 16384 counters, one per 128-byte line, at the front — so calls of different entry points
-// and shapes sharing one workspace never write data over each other's counters.  The beam rows use
-// arrival counters 0..rows-1 of set 0 (zero between calls, as every user of that set leaves them);
-// the partials start behind the block.
-constexpr int kBeamCntStride = 32;                                                   // int32 words per counter
-constexpr size_t kBeamCntBlockBytes = (size_t)4 * 16384 * kBeamCntStride * sizeof(uint32_t);   // 8 MiB
+// The workspace starts with the common counter block (sd_device.h, kCntBlockBytes).  The beam rows
+// use arrival counters 0..rows-1 of set 0 (zero between calls, as every user of that set leaves
+// them); the partials start behind the block.
 
 struct BeamTopk {
     const void* logits;
     int64_t stride_r;
     int32_t V, K, n_chunks;
-    int32_t* cnt;        // row r's arrival counter at cnt[r * kBeamCntStride], zero between calls
+    int32_t* cnt;        // row r's arrival counter at cnt[r * kCntStride], zero between calls
     uint32_t* part;      // [rows][2 + 2K fields][n_chunks]: field-major, as sd_ngram.inc's partials
     float* top_lp;       // [rows, K]
     int64_t* top_tok;    // [rows, K]
@@ -42,32 +39,6 @@ struct BeamTopk {
 
 __device__ __forceinline__ uint32_t* bt_field(const BeamTopk& P, int r, int f) {
     return P.part + ((int64_t)r * (2 + 2 * P.K) + f) * P.n_chunks;
-}
-
-// block reductions over the 4 waves, fixed order (deterministic); lds: 4 words
-__device__ __forceinline__ float beam_block_max(float v, float* lds) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(lds[0], lds[1]), fmaxf(lds[2], lds[3]));
-}
-__device__ __forceinline__ float beam_block_sum(float v, float* lds) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-__device__ __forceinline__ void beam_block_argmax(float& v, int32_t& i, float* ldsv, int32_t* ldsi) {
-    wave_argmax(v, i);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { ldsv[threadIdx.x >> 6] = v; ldsi[threadIdx.x >> 6] = i; }
-    __syncthreads();
-    v = ldsv[0]; i = ldsi[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-        if (arg_better(ldsv[k], ldsi[k], v, i)) { v = ldsv[k]; i = ldsi[k]; }
 }
 
 // one span's elements as its workgroup holds them: 8 per thread, out-of-range ones (-inf, INT_MAX)
@@ -107,13 +78,13 @@ __global__ void __launch_bounds__(kThreads) k_beam_topk(BeamTopk P) {
 #pragma unroll
     for (int k = 0; k < EPT; ++k) m = fmaxf(m, x[k]);
     // the span's (max, Σexp): an all -inf span contributes (−inf, 0)
-    m = beam_block_max(m, ldsf);
+    m = block_reduce(m, FMax{}, ldsf, kWaves);
     const float ms = m == -INFINITY ? 0.f : m;
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < EPT; ++k)
         if (idx[k] != INT_MAX) s += sd_exp(x[k] - ms);
-    s = beam_block_sum(s, ldsf);
+    s = block_reduce(s, FSum{}, ldsf, kWaves);
     if (threadIdx.x == 0) {
         st_coh(reinterpret_cast<float*>(bt_field(P, r, 0)) + c, m);
         st_coh(reinterpret_cast<float*>(bt_field(P, r, 1)) + c, s);
@@ -126,7 +97,7 @@ __global__ void __launch_bounds__(kThreads) k_beam_topk(BeamTopk P) {
 #pragma unroll
         for (int k = 0; k < EPT; ++k)
             if (arg_better(x[k], idx[k], bv, bi)) { bv = x[k]; bi = idx[k]; }
-        beam_block_argmax(bv, bi, ldsf, ldsi);
+        block_argmax(bv, bi, ldsf, ldsi, kWaves);
         if (threadIdx.x == 0) {
             st_coh(reinterpret_cast<float*>(bt_field(P, r, 2 + t)) + c, bv);
             st_coh(reinterpret_cast<int32_t*>(bt_field(P, r, 2 + P.K + t)) + c, bi);
@@ -139,7 +110,7 @@ __global__ void __launch_bounds__(kThreads) k_beam_topk(BeamTopk P) {
     coh_wait();
     __syncthreads();
     if (threadIdx.x == 0) {
-        llast = __hip_atomic_fetch_add(P.cnt + (size_t)r * kBeamCntStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == P.n_chunks - 1;
+        llast = __hip_atomic_fetch_add(P.cnt + (size_t)r * kCntStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == P.n_chunks - 1;
         s_nsat = 0;
     }
     __syncthreads();
@@ -152,9 +123,9 @@ __global__ void __launch_bounds__(kThreads) k_beam_topk(BeamTopk P) {
     const int32_t* li = reinterpret_cast<const int32_t*>(bt_field(P, r, 2 + K)) + t_;
     const float mc = own ? ld_coh(reinterpret_cast<const float*>(bt_field(P, r, 0)) + t_) : -INFINITY;
     const float sc = own ? ld_coh(reinterpret_cast<const float*>(bt_field(P, r, 1)) + t_) : 0.f;
-    const float M = beam_block_max(mc, ldsf);
+    const float M = block_reduce(mc, FMax{}, ldsf, kWaves);
     const float Ms = M == -INFINITY ? 0.f : M;
-    const float S = beam_block_sum(sc > 0.f ? sc * sd_exp(mc - Ms) : 0.f, ldsf);
+    const float S = block_reduce(sc > 0.f ? sc * sd_exp(mc - Ms) : 0.f, FSum{}, ldsf, kWaves);
     const float logS = logf(S);
     // the log-prob as the reference's dtype holds it: monotone in the logit, so the candidates below
     // are ordered by the logit first and regrouped by this value where it ties
@@ -166,7 +137,7 @@ __global__ void __launch_bounds__(kThreads) k_beam_topk(BeamTopk P) {
     for (int t = 0; t < K; ++t) {
         float bv = hv;
         int32_t bi = hi;
-        beam_block_argmax(bv, bi, ldsf, ldsi);
+        block_argmax(bv, bi, ldsf, ldsi, kWaves);
         if (threadIdx.x == 0) { s_pv[t] = bv; s_pi[t] = bi; }
         if (own && hi == bi && bi != INT_MAX) {   // the winner's owner moves to its list's next entry
             ++h;
@@ -224,14 +195,14 @@ __global__ void __launch_bounds__(kThreads) k_beam_topk(BeamTopk P) {
                 if (idx[k] > prev && idx[k] < best && keyf(x[k]) == vK) best = idx[k];
         }
         float bv = best == INT_MAX ? -INFINITY : 0.f;
-        beam_block_argmax(bv, best, ldsf, ldsi);
+        block_argmax(bv, best, ldsf, ldsi, kWaves);
         if (threadIdx.x == 0) {
             P.top_lp[(int64_t)r * K + q] = vK;
             P.top_tok[(int64_t)r * K + q] = best == INT_MAX ? -1 : (int64_t)best;
         }
         prev = best;
     }
-    if (threadIdx.x == 0) st_coh(P.cnt + (size_t)r * kBeamCntStride, 0);   // counters are zero again at exit
+    if (threadIdx.x == 0) st_coh(P.cnt + (size_t)r * kCntStride, 0);   // counters are zero again at exit
 }
 
 struct BeamSel {
@@ -383,28 +354,19 @@ __global__ void __launch_bounds__(kThreads) k_beam_select(BeamSel P) {
 }  // namespace sd
 
 namespace {
-
-bool beam_valid_dtype(int dt) { return dt == SD_F32 || dt == SD_BF16 || dt == SD_F16; }
+using namespace sd_host;
 
 int32_t beam_chunks(int32_t vocab) { return (vocab + sd::kBeamSpan - 1) / sd::kBeamSpan; }
 
-size_t beam_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // workspace: the common counter block, then the partials
-size_t beam_counter_bytes(int32_t) { return sd::kBeamCntBlockBytes; }
-size_t beam_part_bytes(int32_t rows, int32_t vocab, int32_t k) {
-    return beam_align((size_t)rows * (2 + 2 * (size_t)k) * beam_chunks(vocab) * sizeof(uint32_t));
+void beam_carve(sd::BeamTopk& T, Carve& c, int32_t rows, int32_t vocab, int32_t k) {
+    T.cnt = c.take<int32_t>(sd::kCntBlockBytes / sizeof(int32_t));
+    T.part = c.take<uint32_t>((size_t)rows * (2 + 2 * (size_t)k) * beam_chunks(vocab));
 }
 
 bool beam_shape_ok(int32_t rows, int32_t vocab, int32_t k) {
     return rows >= 1 && rows <= SD_BEAM_MAX_BEAMS && k >= 1 && k <= SD_BEAM_MAX_TOPK && vocab >= 1 &&
            vocab <= SD_BEAM_MAX_VOCAB && k <= vocab;
-}
-
-template <typename K, typename A>
-int32_t beam_launch(K kern, dim3 grid, void* stream, const A& arg) {
-    hipLaunchKernelGGL(kern, grid, dim3(sd::kThreads), 0, (hipStream_t)stream, arg);
-    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_LAUNCH;
 }
 
 }  // namespace
@@ -413,7 +375,10 @@ extern "C" {
 
 size_t sd_beam_workspace_size(int32_t rows, int32_t vocab, int32_t k) {
     if (!beam_shape_ok(rows, vocab, k)) return 0;
-    return beam_counter_bytes(rows) + beam_part_bytes(rows, vocab, k);
+    sd::BeamTopk T{};
+    Carve c{nullptr};
+    beam_carve(T, c, rows, vocab, k);
+    return c.used;
 }
 
 int32_t sd_beam_step(const sd_beam_args* a, void* stream) {
@@ -429,7 +394,7 @@ int32_t sd_beam_step(const sd_beam_args* a, void* stream) {
         return SD_ERR_UNSUPPORTED;
     if (K > a->vocab) return SD_ERR_INVALID;   // torch.topk raises
     if (!a->top_logprob || !a->top_token) return SD_ERR_INVALID;
-    if (!given && (!a->logits || !beam_valid_dtype(a->dtype) || (rows > 1 && a->stride_r < a->vocab)))
+    if (!given && (!a->logits || !valid_dtype(a->dtype) || (rows > 1 && a->stride_r < a->vocab)))
         return SD_ERR_INVALID;
     if (!topk_only) {
         if (a->curr < 1 || a->curr >= a->total_len || !(a->lp == a->lp) || a->lp == 0.f) return SD_ERR_INVALID;
@@ -441,18 +406,18 @@ int32_t sd_beam_step(const sd_beam_args* a, void* stream) {
     }
     if (!given && (!a->workspace || a->workspace_bytes < sd_beam_workspace_size(rows, a->vocab, K)))
         return SD_ERR_WORKSPACE;
-    (void)hipGetLastError();
+    clear_stale_error();
     if (!given) {
         sd::BeamTopk T{};
         T.logits = a->logits; T.stride_r = a->stride_r;
         T.V = a->vocab; T.K = K; T.n_chunks = beam_chunks(a->vocab);
-        T.cnt = static_cast<int32_t*>(a->workspace);
-        T.part = reinterpret_cast<uint32_t*>(static_cast<char*>(a->workspace) + beam_counter_bytes(rows));
+        Carve c{static_cast<char*>(a->workspace)};
+        beam_carve(T, c, rows, a->vocab, K);
         T.top_lp = a->top_logprob; T.top_tok = a->top_token;
         const dim3 grid(T.n_chunks, rows);
-        const int32_t st = a->dtype == SD_BF16  ? beam_launch(sd::k_beam_topk<SD_BF16>, grid, stream, T)
-                           : a->dtype == SD_F16 ? beam_launch(sd::k_beam_topk<SD_F16>, grid, stream, T)
-                                                : beam_launch(sd::k_beam_topk<SD_F32>, grid, stream, T);
+        const int32_t st = dispatch_dtype(a->dtype, [&](auto dt_) {
+            return launch(sd::k_beam_topk<decltype(dt_)::value>, grid, dim3(sd::kThreads), 0, stream, T);
+        });
         if (st != SD_OK) return st;
     }
     if (topk_only) return SD_OK;
@@ -465,7 +430,7 @@ int32_t sd_beam_step(const sd_beam_args* a, void* stream) {
     S.li_in = a->last_index_in; S.li_out = a->last_index_out;
     S.top_lp = a->top_logprob; S.top_tok = a->top_token;
     S.all_finished = a->all_finished; S.parent = a->parent;
-    return beam_launch(sd::k_beam_select, dim3(1), stream, S);
+    return launch(sd::k_beam_select, dim3(1), dim3(sd::kThreads), 0, stream, S);
 }
 
 }  // extern "C"

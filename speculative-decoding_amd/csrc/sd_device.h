@@ -18,6 +18,7 @@ namespace sd {
 
 constexpr int kWave = 64;
 constexpr int kThreads = 256;            // 4 waves per workgroup
+constexpr int kWaves = kThreads / kWave;
 constexpr float kNegFill = -1e20f;       // utils/logits_processor.py:62,79
 
 // ---------------------------------------------------------------- dtype handling
@@ -541,6 +542,69 @@ __device__ __forceinline__ void wave_argmax(float& v, int32_t& i) {
     v = lane63_f(v);
     i = lane63_i(i);
 }
+
+// ---------------------------------------------------------------- block helpers
+struct FMax {
+    static constexpr float kId = -INFINITY;
+    __device__ float operator()(float a, float b) const { return fmaxf(a, b); }
+};
+struct FSum {
+    static constexpr float kId = 0.f;
+    __device__ float operator()(float a, float b) const { return a + b; }
+};
+
+// Block reductions over the workgroup's waves: nw > 0 names the waves that take part (the
+// sampling bodies run in k_verify_lean's four data waves after its helper wave has exited, so
+// blockDim would count one wave too many), else every wave of the launch.
+template <typename F>
+__device__ __forceinline__ float block_reduce(float v, F op, float* lds, int nw = 0) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    v = wave_reduce(v, F::kId, op);
+    __syncthreads();
+    if (lane == 0) lds[w] = v;
+    __syncthreads();
+    float r = lds[0];
+    const int n = nw > 0 ? nw : (int)(blockDim.x >> 6);
+    for (int k = 1; k < n; ++k) r = op(r, lds[k]);
+    return r;
+}
+
+// two sums at once (fixed order)
+__device__ __forceinline__ float2 block_reduce2(float2 v, float* lds) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    v.x = wave_sum(v.x);
+    v.y = wave_sum(v.y);
+    __syncthreads();
+    if (lane == 0) { lds[2 * w] = v.x; lds[2 * w + 1] = v.y; }
+    __syncthreads();
+    float2 r = make_float2(lds[0], lds[1]);
+    for (int k = 1; k < (int)(blockDim.x >> 6); ++k) { r.x += lds[2 * k]; r.y += lds[2 * k + 1]; }
+    return r;
+}
+
+__device__ __forceinline__ void block_argmax(float& v, int32_t& i, float* ldsv, int32_t* ldsi, int nw = 0) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    wave_argmax(v, i);
+    __syncthreads();
+    if (lane == 0) { ldsv[w] = v; ldsi[w] = i; }
+    __syncthreads();
+    v = ldsv[0]; i = ldsi[0];
+    const int n = nw > 0 ? nw : (int)(blockDim.x >> 6);
+    for (int k = 1; k < n; ++k)
+        if (arg_better(ldsv[k], ldsi[k], v, i)) { v = ldsv[k]; i = ldsi[k]; }
+}
+
+// ---------------------------------------------------------------- workspace counter block
+// Arrival counters live in a fixed block at the front of EVERY entry point's workspace layout
+// (DESIGN.md §4), so calls of different entry points and shapes sharing one workspace never write
+// data over each other's counters.  They are zero between calls (the last arriving workgroup resets
+// its counter); the workspace must be zero-filled once.  One counter per 128-byte line:
+// device-scope atomics execute beyond the per-XCD L2, and counters sharing a line would serialise
+// every sequence's arrivals on it.
+constexpr int kCntMax = 16384;   // counters per set
+constexpr int kCntStride = 32;   // uint32 words per counter (128 B)
+constexpr int kCntSets = 4;      // 0 / 1 arrivals, 2 k_draw_lean row epochs, 3 k_sample poll-mode sequence epochs
+constexpr size_t kCntBlockBytes = (size_t)kCntSets * kCntMax * kCntStride * sizeof(uint32_t);   // 8 MiB
 
 // ---------------------------------------------------------------- noise
 __device__ __forceinline__ float uniform_from_word(uint32_t w) {   // torch.rand fp32 (1 word)

@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "sd_device.h"
+#include "sd_host.h"
 
 namespace sd {
 
@@ -188,15 +189,9 @@ struct Plan {
     } while (0)
 #endif
 
-// Arrival counters live in a fixed block at the front of every workspace layout, so calls with
-// different shapes sharing one workspace never overwrite them.  They are zero between calls
-// (the last arriving workgroup resets its counter); the workspace must be zero-filled once.
-// One counter per 128-byte line: device-scope atomics execute beyond the per-XCD L2, and
-// counters sharing a line would serialise every sequence's arrivals on it.
-constexpr int kCntMax = 16384;
 constexpr int kTailChunks = 1024;   // perf-mode sampling: chunk partials staged in LDS (V <= 2 Mi)
 constexpr int32_t kLostDecision = -2;   // fused verify: a sampler's record when the decision never arrived
-constexpr int kCntStride = 32;   // uint32 words per counter (128 B)
+// counter b of a set of the workspace's counter block (sd_device.h, kCntMax)
 __device__ __forceinline__ uint32_t* seq_counter(const uint32_t* base, int set, int b) {
     return const_cast<uint32_t*>(base) + ((size_t)set * kCntMax + b) * kCntStride;
 }
@@ -279,58 +274,6 @@ __device__ __forceinline__ bool is_stop_l(const Plan& P, int64_t tok, const int6
 #else
 #define SD_SGPR_CAP
 #endif
-
-// ------------------------------------------------------------------ block helpers
-struct FMax {
-    static constexpr float kId = -INFINITY;
-    __device__ float operator()(float a, float b) const { return fmaxf(a, b); }
-};
-struct FSum {
-    static constexpr float kId = 0.f;
-    __device__ float operator()(float a, float b) const { return a + b; }
-};
-
-// Block reductions over the workgroup's waves: nw > 0 names the waves that take part (the
-// sampling bodies run in k_verify_lean's four data waves after its helper wave has exited, so
-// blockDim would count one wave too many), else every wave of the launch.
-template <typename F>
-__device__ __forceinline__ float block_reduce(float v, F op, float* lds, int nw = 0) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v = wave_reduce(v, F::kId, op);
-    __syncthreads();
-    if (lane == 0) lds[w] = v;
-    __syncthreads();
-    float r = lds[0];
-    const int n = nw > 0 ? nw : (int)(blockDim.x >> 6);
-    for (int k = 1; k < n; ++k) r = op(r, lds[k]);
-    return r;
-}
-
-// two sums at once (fixed order)
-__device__ __forceinline__ float2 block_reduce2(float2 v, float* lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v.x = wave_sum(v.x);
-    v.y = wave_sum(v.y);
-    __syncthreads();
-    if (lane == 0) { lds[2 * w] = v.x; lds[2 * w + 1] = v.y; }
-    __syncthreads();
-    float2 r = make_float2(lds[0], lds[1]);
-    for (int k = 1; k < (int)(blockDim.x >> 6); ++k) { r.x += lds[2 * k]; r.y += lds[2 * k + 1]; }
-    return r;
-}
-
-__device__ __forceinline__ void block_argmax(float& v, int32_t& i, float* ldsv, int32_t* ldsi, int nw = 0) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    wave_argmax(v, i);
-    __syncthreads();
-    if (lane == 0) { ldsv[w] = v; ldsi[w] = i; }
-    __syncthreads();
-    v = ldsv[0]; i = ldsi[0];
-    const int n = nw > 0 ? nw : (int)(blockDim.x >> 6);
-    for (int k = 1; k < n; ++k)
-        if (arg_better(ldsv[k], ldsi[k], v, i)) { v = ldsv[k]; i = ldsi[k]; }
-}
-
 
 // ------------------------------------------------------------------ k_stats
 // grid (span, row-of-group): running max / Σexp of y = round_dt(_process(x)/T) over one span of a
@@ -3572,7 +3515,7 @@ __global__ void __launch_bounds__(kThreads) k_writeprobs(Plan P, void* out, int6
 
 // ====================================================================== host side
 namespace {
-thread_local hipError_t g_last_error = hipSuccess;
+using namespace sd_host;
 
 // In-launch exchange policy (sd_set_poll_policy): whether poll-mode exchanges may be chosen at all,
 // and the bound of every poll.  Process-wide; SD_POLL / SD_POLL_SPIN_LIMIT set the initial values.
@@ -3616,9 +3559,6 @@ std::atomic<int>* option_slot(int32_t opt) {
 }
 inline int opt(const std::atomic<int>& o) { return o.load(std::memory_order_relaxed); }
 
-// the path of this thread's last sd_verify / sd_sample (sd_last_*_path)
-thread_local int32_t g_verify_path = SD_PATH_NONE;
-thread_local int32_t g_sample_path = SD_PATH_NONE;
 bool poll_allowed() {
     policy_init();
     return g_allow_poll.load(std::memory_order_relaxed) > 0;
@@ -3628,31 +3568,6 @@ int spin_limit() {
     return g_spin_limit.load(std::memory_order_relaxed);
 }
 int resident_cap(const void* kern, int threads = sd::kThreads, size_t dyn = 0);
-
-// Every launch of the library: SD_OK, or SD_ERR_LAUNCH with the error recorded — the caller returns
-// it at once and starts nothing after it.
-template <typename K, typename... A>
-int32_t launch(K kern, dim3 grid, dim3 block, size_t dyn_lds, void* stream, const A&... args) {
-    hipLaunchKernelGGL(kern, grid, block, (unsigned)dyn_lds, (hipStream_t)stream, args...);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_error = e; return SD_ERR_LAUNCH; }
-    return SD_OK;
-}
-
-// Runtime value -> template argument: f(std::integral_constant<int, V>{}) for the V of the pack
-// that equals v; the last of the pack takes every other value (the else branch of a ladder).
-template <int V0, int... VS, typename F>
-auto dispatch_int(int v, F&& f) {
-    if constexpr (sizeof...(VS) == 0) return f(std::integral_constant<int, V0>{});
-    else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<VS...>(v, f);
-}
-template <typename F>
-auto dispatch_dtype(int dt, F&& f) { return dispatch_int<SD_BF16, SD_F32, SD_F16>(dt, f); }
-// the kernels without fp32 variants (the caller has excluded SD_F32)
-template <typename F>
-auto dispatch_dtype16(int dt, F&& f) { return dispatch_int<SD_BF16, SD_F16>(dt, f); }
-template <typename F>
-auto dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 }  // namespace
 
 #include "sd_threshold.inc"
@@ -3666,26 +3581,11 @@ using namespace sd;
 
 constexpr int kEptSmall = 8;
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-struct Carve {
-    char* p;
-    size_t used = 0;
-    template <typename T>
-    T* take(size_t n) {
-        T* r = reinterpret_cast<T*>(p ? p + used : nullptr);
-        used += align256(n * sizeof(T));
-        return r;
-    }
-};
-
 int max_chunks(int vocab) { return (vocab + kThreads * kEptSmall - 1) / (kThreads * kEptSmall); }
 
 void carve(Plan& P, Carve& c, int rows_total, int B, int gamma, int vocab) {
     const int nc = max_chunks(vocab);
-    // first, at a fixed offset (see kCntMax): sets 0 / 1 arrivals, 2 k_draw_lean row epochs,
-    // 3 k_sample poll-mode sequence epochs
-    P.cnt = c.take<uint32_t>(4 * (size_t)kCntMax * kCntStride);
+    P.cnt = c.take<uint32_t>(kCntBlockBytes / sizeof(uint32_t));   // first, at a fixed offset (sd_device.h)
     P.part = c.take<float2>((size_t)rows_total * nc);
     P.rowstat = c.take<float2>(rows_total);
     P.keep = c.take<RowKeep>(rows_total);
@@ -3708,7 +3608,6 @@ void carve(Plan& P, Carve& c, int rows_total, int B, int gamma, int vocab) {
     P.thr = c.take<ThrRow>(rows_total);
 }
 
-bool valid_dtype(int dt) { return dt == SD_F32 || dt == SD_BF16 || dt == SD_F16; }
 bool valid_proc(const sd_processor& p) {
     if (p.kind < SD_PROC_GREEDY || p.kind > SD_PROC_TOPK_NUCLEUS) return false;
     if ((p.kind == SD_PROC_TOPK || p.kind == SD_PROC_TOPK_NUCLEUS) && p.top_k <= 0) return false;
@@ -3751,9 +3650,6 @@ void plan_rows(sd::Plan& P, int B, int slots, int vocab, int dtype, const sd_pro
 }
 
 int32_t launch_stats(const sd::Plan& P, void* stream, bool tail = false);
-
-// errors left behind by earlier, unrelated runtime calls must not be blamed on our launches
-inline void clear_stale_error() { (void)hipGetLastError(); }
 
 bool sample_poll_ok(int B, const void* kern);
 
@@ -4186,8 +4082,6 @@ int32_t sd_get_option(int32_t option, int32_t* value) {
 }
 
 int32_t sd_last_verify_path(void) { return g_verify_path; }
-// the library's other translation units (csrc/vocab_parallel.hip) report their path here; not exported
-__attribute__((visibility("hidden"))) void sd_internal_set_verify_path(int32_t path) { g_verify_path = path; }
 int32_t sd_last_sample_path(void) { return g_sample_path; }
 
 const char* sd_status_string(int32_t s) {

@@ -24,9 +24,8 @@
 // counter is touched (the workspace's common counter block at its front is skipped, never written).
 // The decision travels inside the candidate record, so the three calls of one rank keep no state in
 // the workspace between them: ranks emulated in one process may share one workspace.
-#include <type_traits>
-
 #include "sd_device.h"
+#include "sd_host.h"
 
 namespace sd {
 
@@ -34,9 +33,6 @@ constexpr int kVpEpt = 8;
 constexpr int kVpChunk = kThreads * kVpEpt;                       // 2048 elements per workgroup
 constexpr int kVpMaxChunks = SD_VP_MAX_VOCAB_LOCAL / kVpChunk;   // 1024 (staged in LDS by k_vp_pick)
 constexpr int kVpMaxRows = 2 * SD_MAX_GAMMA + 1;
-// the workspace convention of every entry point (specdec_kernels.hip, carve()): 4 sets x 16384
-// arrival counters, one per 128-byte line, at the front.  This unit leaves them alone.
-constexpr size_t kVpCntBlockBytes = (size_t)4 * 16384 * 32 * sizeof(uint32_t);
 
 enum { kVpNone = 0, kVpBonus = 1, kVpResid = 2, kVpPRow = 3 };
 
@@ -77,32 +73,6 @@ struct Vp {
     int32_t* owner_shard;
     int32_t* status_or;
 };
-
-// block reductions over the 4 waves, fixed order; lds: 4 words
-__device__ __forceinline__ float vp_block_max(float v, float* lds) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(lds[0], lds[1]), fmaxf(lds[2], lds[3]));
-}
-__device__ __forceinline__ float vp_block_sum(float v, float* lds) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-__device__ __forceinline__ void vp_block_argmax(float& v, int32_t& i, float* ldsv, int32_t* ldsi) {
-    wave_argmax(v, i);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { ldsv[threadIdx.x >> 6] = v; ldsi[threadIdx.x >> 6] = i; }
-    __syncthreads();
-    v = ldsv[0]; i = ldsi[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-        if (arg_better(ldsv[k], ldsi[k], v, i)) { v = ldsv[k]; i = ldsi[k]; }
-}
 
 // row r of sequence b, element 0 of the slice: r = 0..γ' target rows, then the drafter rows
 template <int DT>
@@ -164,13 +134,13 @@ __global__ void __launch_bounds__(kThreads) k_vp_stats(Vp P) {
 #pragma unroll
     for (int e = 0; e < kVpEpt; ++e)
         if (e0 + e < P.Vs) { x[e] = vp_y<DT>(x[e], P.T); m = fmaxf(m, x[e]); }
-    m = vp_block_max(m, lds);
+    m = block_reduce(m, FMax{}, lds, kWaves);
     const float ms = m == -INFINITY ? 0.f : m;      // an all -inf chunk contributes (-inf, 0)
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < kVpEpt; ++e)
         if (e0 + e < P.Vs) s += sd_exp(x[e] - ms);
-    s = vp_block_sum(s, lds);
+    s = block_reduce(s, FSum{}, lds, kWaves);
     if (threadIdx.x == 0) P.part[(int64_t)rr * P.n_chunks + c] = make_float2(m, s);
 }
 
@@ -323,7 +293,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_mass(Vp P) {
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < kVpEpt; ++e) s += wv[e];
-    s = vp_block_sum(s, lds);
+    s = block_reduce(s, FSum{}, lds, kWaves);
     if (threadIdx.x == 0) P.mpart[(int64_t)b * P.n_chunks + c] = s;
     if (!P.stoch) {                                   // greedy: the chunk's argmax (NaN first, lowest index)
         float bv = -INFINITY;
@@ -331,7 +301,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_mass(Vp P) {
 #pragma unroll
         for (int e = 0; e < kVpEpt; ++e)
             if (e0 + e < P.Vs && arg_better(wv[e], (int32_t)(e0 + e), bv, bi)) { bv = wv[e]; bi = (int32_t)(e0 + e); }
-        vp_block_argmax(bv, bi, lds, ldi);
+        block_argmax(bv, bi, lds, ldi, kWaves);
         if (threadIdx.x == 0) P.mbest[(int64_t)b * P.n_chunks + c] = make_float2(bv, __int_as_float(bi));
     }
 }
@@ -383,7 +353,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_pick(Vp P) {
                 const float2 v = P.mbest[(int64_t)b * nc + c];
                 if (arg_better(v.x, __float_as_int(v.y), bv, bi)) { bv = v.x; bi = __float_as_int(v.y); }
             }
-            vp_block_argmax(bv, bi, ldv, ldi);
+            block_argmax(bv, bi, ldv, ldi, kWaves);
             if (tid == 0 && bi != INT_MAX) { s_x = (int64_t)P.off + bi; s_w = bv; }
         } else if (s_pick >= 0) {                     // the element inside the chunk, weights recomputed
             const int pick = s_pick;
@@ -496,14 +466,9 @@ __global__ void __launch_bounds__(kThreads) k_vp_finish(Vp P) {
 
 }  // namespace sd
 
-// the verify path of the calling thread's last call lives in specdec_kernels.hip; a stand-alone link
-// of this unit (the host-side sanitizer driver) has no such symbol
-extern "C" __attribute__((weak)) void sd_internal_set_verify_path(int32_t path);
-
 namespace {
+using namespace sd_host;
 
-inline size_t vp_align(size_t v) { return (v + 255) & ~(size_t)255; }
-bool vp_valid_dtype(int dt) { return dt == SD_F32 || dt == SD_BF16 || dt == SD_F16; }
 int32_t vp_chunks(int64_t vocab_local) { return (int32_t)((vocab_local + sd::kVpChunk - 1) / sd::kVpChunk); }
 
 // 0: a shape the step takes; else the status the entry points return for it
@@ -513,31 +478,16 @@ int32_t vp_shape_status(int64_t B, int64_t gamma, int64_t vocab_local) {
     return SD_OK;
 }
 
-struct VpCarve {
-    char* p;
-    size_t used = 0;
-    template <typename T>
-    T* take(size_t n) {
-        T* r = reinterpret_cast<T*>(p ? p + used : nullptr);
-        used += vp_align(n * sizeof(T));
-        return r;
-    }
-};
-
-void vp_carve(sd::Vp& P, VpCarve& c, int B, int gamma, int vocab_local) {
+void vp_carve(sd::Vp& P, Carve& c, int B, int gamma, int vocab_local) {
     const size_t nc = (size_t)vp_chunks(vocab_local);
-    c.take<char>(sd::kVpCntBlockBytes);              // the common counter block: skipped, never written
+    c.take<char>(sd::kCntBlockBytes);                // the common counter block: skipped, never written
     P.part = c.take<float2>((size_t)B * (2 * gamma + 1) * nc);
     P.dec = c.take<sd::VpDecision>(B);
     P.mpart = c.take<float>((size_t)B * nc);
     P.mbest = c.take<float2>((size_t)B * nc);
 }
 
-template <typename K>
-int32_t vp_launch(K kern, int64_t grid, void* stream, const sd::Vp& arg) {
-    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(sd::kThreads), 0, (hipStream_t)stream, arg);
-    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_LAUNCH;
-}
+const dim3 kVpBlock(sd::kThreads);   // every kernel of this unit: 1-D grids of kThreads-wide workgroups
 
 enum VpPhase { kPhaseStats, kPhaseDecide, kPhaseFinish };
 
@@ -548,7 +498,7 @@ int32_t vp_plan(const sd_vp_args* a, VpPhase phase, sd::Vp& P) {
     if (shape == SD_ERR_INVALID) return SD_ERR_INVALID;
     if (a->num_shards < 1 || a->shard < 0 || a->shard >= a->num_shards) return SD_ERR_INVALID;
     if (a->vocab < 1 || a->vocab_offset < 0 || (int64_t)a->vocab_offset + a->vocab_local > a->vocab) return SD_ERR_INVALID;
-    if (!vp_valid_dtype(a->dtype)) return SD_ERR_INVALID;
+    if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
     if (a->proc.kind < SD_PROC_GREEDY || a->proc.kind > SD_PROC_TOPK_NUCLEUS || !(a->proc.temperature > 0.f))
         return SD_ERR_INVALID;
     if (a->noise.mode != SD_NOISE_STREAM && a->noise.mode != SD_NOISE_PHILOX) return SD_ERR_INVALID;
@@ -587,16 +537,9 @@ int32_t vp_plan(const sd_vp_args* a, VpPhase phase, sd::Vp& P) {
     P.n_accepted = a->n_accepted; P.next_token = a->next_token; P.resample_mass = a->resample_mass;
     P.prune_drafter = a->prune_drafter; P.prune_target = a->prune_target; P.stop_index = a->stop_index;
     P.row_status = a->row_status; P.owner_shard = a->owner_shard; P.status_or = a->status_or;
-    VpCarve c{static_cast<char*>(a->workspace)};
+    Carve c{static_cast<char*>(a->workspace)};
     vp_carve(P, c, a->batch, a->gamma, a->vocab_local);
     return SD_OK;
-}
-
-template <typename F>
-int32_t vp_dispatch(int dt, F&& f) {
-    if (dt == SD_BF16) return f(std::integral_constant<int, SD_BF16>{});
-    if (dt == SD_F16) return f(std::integral_constant<int, SD_F16>{});
-    return f(std::integral_constant<int, SD_F32>{});
 }
 
 }  // namespace
@@ -616,7 +559,7 @@ size_t sd_vp_cand_bytes(int32_t batch) {
 size_t sd_vp_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local) {
     if (vp_shape_status(batch, gamma, vocab_local) != SD_OK) return 0;
     sd::Vp P{};
-    VpCarve c{nullptr};
+    Carve c{nullptr};
     vp_carve(P, c, batch, gamma, vocab_local);
     return c.used;
 }
@@ -624,33 +567,33 @@ size_t sd_vp_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local) {
 int32_t sd_vp_stats(const sd_vp_args* a, void* stream) {
     sd::Vp P{};
     if (int32_t st = vp_plan(a, kPhaseStats, P)) return st;
-    (void)hipGetLastError();
+    clear_stale_error();
     const int rows = P.B * (2 * P.gamma + 1), wpb = sd::kThreads / sd::kWave;
-    return vp_dispatch(a->dtype, [&](auto dt_) -> int32_t {
+    return dispatch_dtype(a->dtype, [&](auto dt_) -> int32_t {
         constexpr int DT = decltype(dt_)::value;
-        if (int32_t st = vp_launch(sd::k_vp_stats<DT>, (int64_t)rows * P.n_chunks, stream, P)) return st;
-        return vp_launch(sd::k_vp_rowstat<DT>, (rows + wpb - 1) / wpb, stream, P);
+        if (int32_t st = launch(sd::k_vp_stats<DT>, dim3((uint32_t)((int64_t)rows * P.n_chunks)), kVpBlock, 0, stream, P)) return st;
+        return launch(sd::k_vp_rowstat<DT>, dim3((rows + wpb - 1) / wpb), kVpBlock, 0, stream, P);
     });
 }
 
 int32_t sd_vp_decide(const sd_vp_args* a, void* stream) {
     sd::Vp P{};
     if (int32_t st = vp_plan(a, kPhaseDecide, P)) return st;
-    (void)hipGetLastError();
-    return vp_dispatch(a->dtype, [&](auto dt_) -> int32_t {
+    clear_stale_error();
+    return dispatch_dtype(a->dtype, [&](auto dt_) -> int32_t {
         constexpr int DT = decltype(dt_)::value;
-        if (int32_t st = vp_launch(sd::k_vp_decide<DT>, P.B, stream, P)) return st;
-        if (int32_t st = vp_launch(sd::k_vp_mass<DT>, (int64_t)P.B * P.n_chunks, stream, P)) return st;
-        return vp_launch(sd::k_vp_pick<DT>, P.B, stream, P);
+        if (int32_t st = launch(sd::k_vp_decide<DT>, dim3(P.B), kVpBlock, 0, stream, P)) return st;
+        if (int32_t st = launch(sd::k_vp_mass<DT>, dim3((uint32_t)((int64_t)P.B * P.n_chunks)), kVpBlock, 0, stream, P)) return st;
+        return launch(sd::k_vp_pick<DT>, dim3(P.B), kVpBlock, 0, stream, P);
     });
 }
 
 int32_t sd_vp_finish(const sd_vp_args* a, void* stream) {
     sd::Vp P{};
     if (int32_t st = vp_plan(a, kPhaseFinish, P)) return st;
-    (void)hipGetLastError();
-    if (int32_t st = vp_launch(sd::k_vp_finish, (P.B + sd::kThreads - 1) / sd::kThreads, stream, P)) return st;
-    if (sd_internal_set_verify_path) sd_internal_set_verify_path(SD_PATH_VERIFY_VP);
+    clear_stale_error();
+    if (int32_t st = launch(sd::k_vp_finish, dim3((P.B + sd::kThreads - 1) / sd::kThreads), kVpBlock, 0, stream, P)) return st;
+    g_verify_path = SD_PATH_VERIFY_VP;
     return SD_OK;
 }
 

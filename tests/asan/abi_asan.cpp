@@ -6,18 +6,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <thread>
 #include <vector>
 
+#include "asan_check.h"
 #include "specdec.h"
-
-static int g_checks = 0, g_fail = 0;
-#define CHECK(cond)                                                                  \
-    do {                                                                             \
-        ++g_checks;                                                                  \
-        if (!(cond)) { ++g_fail; std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
-
-static void* fake(uintptr_t k) { return reinterpret_cast<void*>(0x100000 + 0x1000 * k); }   // never dereferenced
 
 static void verify_rejections() {
     sd_verify_args a;
@@ -107,6 +101,44 @@ static void launch_failure_without_device() {
     p.workspace = fake(50); p.workspace_bytes = sd_probs_workspace_size(p.rows, p.vocab);
     CHECK(sd_probs(&p, nullptr) == SD_ERR_LAUNCH);
     CHECK(std::strcmp(sd_last_hip_error(), "no error") != 0);
+    // The beam step and the vocabulary-parallel verify record their failed launches too.  The record
+    // is per thread, so each runs on a fresh thread, whose record is empty; a call refused by the
+    // argument checks leaves it as it was.
+    std::thread([] {
+        const std::string before = sd_last_hip_error();
+        CHECK(before == "no error");
+        CHECK(sd_beam_step(nullptr, nullptr) == SD_ERR_INVALID);
+        CHECK(before == sd_last_hip_error());
+        sd_beam_args b;
+        std::memset(&b, 0, sizeof b);
+        b.mode = SD_BEAM_TOPK_ONLY; b.num_beams = 4; b.top_k = 3; b.vocab = 5000;
+        b.logits = fake(1); b.stride_r = 5000; b.dtype = SD_BF16;
+        b.top_logprob = static_cast<float*>(fake(2)); b.top_token = static_cast<int64_t*>(fake(3));
+        b.workspace = fake(50); b.workspace_bytes = sd_beam_workspace_size(4, 5000, 3);
+        CHECK(b.workspace_bytes > 0);
+        CHECK(sd_beam_step(&b, nullptr) == SD_ERR_LAUNCH);
+        CHECK(std::strcmp(sd_last_hip_error(), "no error") != 0);
+    }).join();
+    std::thread([] {
+        const std::string before = sd_last_hip_error();
+        CHECK(before == "no error");
+        CHECK(sd_vp_stats(nullptr, nullptr) == SD_ERR_INVALID);
+        CHECK(before == sd_last_hip_error());
+        sd_vp_args v;
+        std::memset(&v, 0, sizeof v);
+        v.batch = 2; v.gamma = 1; v.vocab = 5000; v.vocab_offset = 0; v.vocab_local = 5000; v.shard = 0; v.num_shards = 1;
+        v.dtype = SD_BF16;
+        v.target_rows[0] = fake(1); v.target_rows[1] = fake(2); v.draft_rows[0] = fake(3);
+        v.target_stride_b = v.draft_stride_b = 5000;
+        v.draft_tokens = static_cast<const int64_t*>(fake(4)); v.draft_tokens_stride_b = 1;
+        v.proc = sd_processor{SD_PROC_MULTINOMIAL, 1.f, 0, 1.f};
+        v.noise.mode = SD_NOISE_PHILOX;
+        v.stats_local = fake(5);
+        v.workspace = fake(50); v.workspace_bytes = sd_vp_workspace_size(2, 1, 5000);
+        CHECK(v.workspace_bytes > 0);
+        CHECK(sd_vp_stats(&v, nullptr) == SD_ERR_LAUNCH);
+        CHECK(std::strcmp(sd_last_hip_error(), "no error") != 0);
+    }).join();
 }
 
 static void workspace_shapes() {
@@ -182,6 +214,5 @@ int main(int argc, char** argv) {
     workspace_shapes();
     launch_failure_without_device();
     if (argc >= 3) mt_host(argv[1], argv[2]);
-    std::printf("abi_asan: %d checks, %d failed\n", g_checks, g_fail);
-    return g_fail ? 1 : 0;
+    return report("abi_asan");
 }

@@ -7,16 +7,8 @@
 #include <cstring>
 #include <initializer_list>
 
+#include "asan_check.h"
 #include "specdec.h"
-
-static int g_checks = 0, g_fail = 0;
-#define CHECK(cond)                                                                  \
-    do {                                                                             \
-        ++g_checks;                                                                  \
-        if (!(cond)) { ++g_fail; std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
-
-static void* fake(uintptr_t k) { return reinterpret_cast<void*>(0x100000 + 0x1000 * k); }   // never dereferenced
 
 static sd_multi_args valid_args() {
     sd_multi_args a;
@@ -109,6 +101,5 @@ static void workspace_shapes() {
 int main() {
     rejections();
     workspace_shapes();
-    std::printf("%d checks, %d failed\n", g_checks, g_fail);
-    return g_fail ? 1 : 0;
+    return report("multi_asan");
 }

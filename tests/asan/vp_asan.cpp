@@ -8,16 +8,8 @@
 #include <cstring>
 #include <initializer_list>
 
+#include "asan_check.h"
 #include "specdec.h"
-
-static int g_checks = 0, g_fail = 0;
-#define CHECK(cond)                                                                  \
-    do {                                                                             \
-        ++g_checks;                                                                  \
-        if (!(cond)) { ++g_fail; std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
-
-static void* fake(uintptr_t k) { return reinterpret_cast<void*>(0x100000 + 0x1000 * k); }   // never dereferenced
 
 typedef int32_t (*entry_fn)(const sd_vp_args*, void*);
 static const entry_fn kEntries[3] = {sd_vp_stats, sd_vp_decide, sd_vp_finish};
@@ -146,6 +138,5 @@ static void size_functions() {
 int main() {
     rejections();
     size_functions();
-    std::printf("%d checks, %d failed\n", g_checks, g_fail);
-    return g_fail ? 1 : 0;
+    return report("vp_asan");
 }
