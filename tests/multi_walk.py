@@ -1,7 +1,8 @@
-"""Case builders of the multi-draft verify tests (tests/test_gpu_multidraft.py and the CPU test that
-proves their coverage): rows, drafts CHOSEN by the test so that the walks reach the branches of the
-rule (as tests/perf_walk.py does for the single-chain verify), and the host model's result of every
-sequence (tests/multidraft_ref.py over the exact-arithmetic oracle and the numpy Philox).
+"""Case builders of the multi-draft verify tests (tests/test_gpu_multidraft.py,
+tests/test_gpu_multidraft_edges.py and the CPU test that proves their coverage): rows, drafts CHOSEN
+by the test so that the walks reach the branches of the rule (as tests/perf_walk.py does for the
+single-chain verify), the host model's result of every sequence (tests/multidraft_ref.py over the
+exact-arithmetic oracle and the numpy Philox), and the bounds the device's mass and draw are held to.
 
 Everything here runs on the host; cases are cached and shared: callers must not modify them.
 """
@@ -15,6 +16,7 @@ import torch
 
 import multidraft_ref as mref
 import philox_ref as ph
+import row_edges as rowe
 from oracle import specdec_ref as ref
 
 PROCS = {
@@ -85,7 +87,8 @@ def _directive(scn, d, j, K=2):
 
 def _steer(P, Q, tok, scn, uni):
     """Overwrite tok [K, γ] along the walk so that it follows the scenario where the rows and the
-    uniforms allow it (a directive that cannot be met with MARGIN leaves the iid draft)."""
+    uniforms allow it (a directive that cannot be met with MARGIN leaves the iid draft; so does one
+    met after a residual whose mass is zero, as small vocabularies have: nothing is left to steer by)."""
     K, g = tok.shape
     A = list(range(K))
     for d in range(g):
@@ -98,6 +101,8 @@ def _steer(P, Q, tok, scn, uni):
             u = float(uni[d * K + k])
             with np.errstate(divide="ignore", invalid="ignore"):
                 ratio = np.where(ok, r / q, np.nan)
+            if np.isnan(ratio).all():
+                want = None
             if want == "A" and np.nanmax(ratio) > u + MARGIN:
                 tok[k, d] = int(np.nanargmax(ratio))
             elif want == "R" and np.nanmin(ratio) < u - MARGIN:
@@ -112,7 +117,8 @@ def _steer(P, Q, tok, scn, uni):
                         tok[k2, d] = x
                 break
             diff = np.maximum(r - q, 0.0)
-            r = diff / diff.sum()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = diff / diff.sum()
         if hit is None:
             return
         A = [k for k in A if int(tok[k, d]) == hit]
@@ -123,10 +129,16 @@ def case(B, K, g, V, dtype, proc_name, seed=11):
     """Rows tl [B, K, γ+1, V], dl [B, K, γ, V] (dl = tl + N(0, 0.7²), target logits randn * 3), the
     oracle's rounded probabilities P, Q (fp32 tensors holding dtype values), drafts tok [B, K, γ]
     drawn iid from Q and then steered by sequence b's scenario SCENARIOS[b % 5]."""
-    proc = PROCS[proc_name]
     gen = torch.Generator().manual_seed(seed * 1000003 + K * 101 + g * 7 + V)
     tl = (torch.randn(B, K, g + 1, V, generator=gen) * 3).to(dtype)
     dl = (tl[:, :, :g].float() + 0.7 * torch.randn(B, K, g, V, generator=gen)).to(dtype)
+    return _with_drafts(tl, dl, proc_name, gen)
+
+
+def _with_drafts(tl, dl, proc_name, gen, **extra):
+    """The case of rows tl, dl: the oracle's P, Q and the steered drafts (see case)."""
+    (B, K, g, V), dtype = dl.shape, tl.dtype
+    proc = PROCS[proc_name]
     P = ref.process(tl, proc, exact=True).float()
     Q = ref.process(dl, proc, exact=True).float()
     tok = torch.multinomial(Q.reshape(-1, V), 1, generator=gen).reshape(B, K, g)
@@ -136,7 +148,90 @@ def case(B, K, g, V, dtype, proc_name, seed=11):
         _steer(P[b].numpy(), Q[b].numpy(), t, SCENARIOS[b % len(SCENARIOS)], uni)
         tok[b] = torch.from_numpy(t)
     return SimpleNamespace(B=B, K=K, gamma=g, V=V, dtype=dtype, proc=proc, proc_name=proc_name, tl=tl, dl=dl, P=P, Q=Q,
-                           tok=tok)
+                           tok=tok, **extra)
+
+
+# ---------------------------------------------------------------- chunk edges of the draw
+CHUNK = 2048            # elements per mass workgroup: the draw picks a chunk, then an element in it
+EDGE_VOCABS = [2047, 2048, 2049, 4097, 6145]
+EDGE_PROCS = ["multinomial", "multinomial_T0.7", "greedy"]
+# input seeds of the edge cases for which 11 does not meet what tests/test_multidraft_cpu.py asks of
+# them (draws on both sides of the last chunk's edge by both exits, no close row, a draw interval
+# wider than its slack): the lowest seed above 11 that does.  Key: edge_grid()'s tuple
+EDGE_SEEDS = {
+    (16, 4, 2, 4097, torch.bfloat16, "greedy", True): 13,
+    (16, 8, 2, 4097, torch.bfloat16, "multinomial", True): 18,
+}
+
+
+def last_chunk_start(V):
+    return CHUNK * ((V - 1) // CHUNK)
+
+
+def edge_grid():
+    """The GPU cases at the chunk edges: V one below, at and above one chunk, and one above two and
+    three, with the short last chunk boosted (`tail`) or not; dtype and processor cycle so that
+    each dtype meets each processor.  The last case has 8 chains: draws after >= 2 rejections."""
+    cases = []
+    for V in EDGE_VOCABS:
+        for tail in ((False, True) if V > CHUNK else (False,)):
+            n = len(cases)
+            cases.append((16, 4, 2, V, DTYPES[(n + n // 3) % 3], EDGE_PROCS[n % 3], tail))
+    cases.append((16, 8, 2, 4097, torch.bfloat16, "multinomial", True))
+    return cases
+
+
+@functools.lru_cache(maxsize=4)
+def edge_case(B, K, g, V, dtype, proc_name, tail):
+    """As case; with `tail` the logits from last_chunk_start(V) on (the V - 2048 ((V-1) // 2048)
+    elements of the short last chunk) get +8 in every target row, the bonus row included, and +6 in
+    every drafter row: a large share of both the residual mass and the bonus mass lies in that chunk."""
+    seed = EDGE_SEEDS.get((B, K, g, V, dtype, proc_name, tail), 11)
+    gen = torch.Generator().manual_seed(seed * 1000003 + K * 101 + g * 7 + V)
+    base = torch.randn(B, K, g + 1, V, generator=gen) * 3
+    draft = base[:, :, :g] + 0.7 * torch.randn(B, K, g, V, generator=gen)
+    if tail:
+        base[..., last_chunk_start(V):] += 8
+        draft[..., last_chunk_start(V):] += 6
+    tl = base.to(dtype)
+    dl = (tl[:, :, :g].float() + (draft - base[:, :, :g])).to(dtype)
+    return _with_drafts(tl, dl, proc_name, gen, tail=tail)
+
+
+# ---------------------------------------------------------------- small vocabularies, row layouts
+SMALL_VOCABS = [1, 2, 3, 5, 7, 8, 9, 63, 65]
+SMALL_PROCS = ["multinomial", "multinomial_T0.7", "greedy", "topk50", "nucleus0.9"]
+
+
+def small_grid():
+    """(B, K, γ, V, dtype, processor, mask, layout, hinted) of tests/test_gpu_multidraft_edges.py:
+    every V with every layout and every dtype; mask, processor and the hinted variant cycle.  The
+    keep processors run on bf16 and fp32 only (the reference's mask value does not fit fp16)."""
+    cases = []
+    for i, V in enumerate(SMALL_VOCABS):
+        for j, layout in enumerate(rowe.LAYOUTS):
+            for t, dtype in enumerate(DTYPES):
+                n = len(cases)
+                name = SMALL_PROCS[(n + i) % len(SMALL_PROCS)]
+                if dtype == torch.float16 and ("topk" in name or "nucleus" in name):
+                    name = EDGE_PROCS[(i + j) % 3]
+                cases.append((16, 4, 2, V, dtype, name, rowe.MASKS[(i + j + t) % 3], layout, n % 3 == 0))
+    for n, (K, g) in enumerate([(1, 1), (8, 1)]):
+        for j, layout in enumerate(rowe.LAYOUTS):
+            cases.append((16, K, g, 3, DTYPES[(n + j) % 3], EDGE_PROCS[(n + j) % 3], rowe.MASKS[j], layout, j == 1))
+    return cases
+
+
+@functools.lru_cache(maxsize=4)
+def small_case(B, K, g, V, dtype, proc_name, mask):
+    """As case on tests/row_edges.py's rows: target rows logits(mask) (`-inf` entries), drafter rows
+    the target's plus N(0, 0.7²) — the same entries at `-inf`, so that the two rows' keeps agree and
+    q > 0 wherever a draft is drawn."""
+    seed = rowe.seed_of("multi", B, K, g, V, rowe.dt_name(dtype), proc_name, mask)
+    tl = rowe.logits((B, K, g + 1, V), dtype, seed, mask)
+    gen = torch.Generator().manual_seed(seed + 1)
+    dl = (tl[:, :, :g].float() + 0.7 * torch.randn(B, K, g, V, generator=gen)).to(dtype)
+    return _with_drafts(tl, dl, proc_name, gen, mask=mask)
 
 
 def host_results(c, stops=(), seed=SEED, off=OFFSET, row_base=ROW_BASE):
@@ -169,6 +264,52 @@ def flip_slack(logits_rows, dtype):
     normaliser is off by 1e-6 (relative), as tests/perf_walk.py's flip_slack, summed over rows."""
     v = torch.softmax(logits_rows.double(), dim=-1)
     return float(((v * (1 + 1e-6)).to(dtype).double() - (v * (1 - 1e-6)).to(dtype).double()).sum())
+
+
+def _slack_of(c, row):
+    y = ref.processed_logits(row, c.proc, exact=True) / c.proc.temperature
+    return flip_slack(y, c.dtype)
+
+
+def mass_tolerance(c, b, r):
+    """The bound on |device mass - host mass| of the last residual formed: 1e-5 (the project's mass
+    tolerance) plus flip_slack summed over the row pair the residual was formed from — how far the
+    rounded probabilities of the target and the drafter row can move when their softmax normalisers
+    are off by 1e-6.  The same bound whatever the number of rejected siblings."""
+    k0, d = r.mass_at
+    return 1e-5 + _slack_of(c, c.tl[b, k0, d]) + _slack_of(c, c.dl[b, k0, d])
+
+
+def draw_slack(c, b, r):
+    """The bound on how far any partial sum of the device's draw weights lies from the host's: the
+    draw weights are the very terms the mass sums, so a residual exit takes mass_tolerance (of the
+    row pair at r.mass_at); a bonus exit 1e-5 plus flip_slack of the winner's bonus row."""
+    if r.status == mref.BONUS:
+        return 1e-5 + _slack_of(c, c.tl[b, r.winner, c.gamma])
+    return mass_tolerance(c, b, r)
+
+
+def draw_excess(r, x, slack):
+    """How far the host's target u·Σ lies outside the running-total interval of the token x the
+    device returned, as a fraction of the allowed 2·slack (0 inside; the check passes up to 1): one
+    slack covers the device's total, the other its running sum."""
+    lo, hi = mref.draw_interval(r.weights, x)
+    t = r.u * r.total
+    return max(lo - t, t - hi, 0.0) / (2 * slack)
+
+
+def draw_margins(c, rows):
+    """[(b, slack, w[x], edge)] of the rows of a stochastic case that draw by inverse CDF on the host:
+    the row's draw_slack, the weight of the host's token and the distance of the host's target u·Σ
+    from the nearer end of that token's interval.  The GPU check's widened interval
+    [lo - 2 slack, hi + 2 slack] says something where 4 slack < w[x], and admits a neighbouring token
+    only where edge <= 2 slack."""
+    out = []
+    for b, r in enumerate(rows):
+        if c.proc.stochastic and r.x is not None:
+            t = r.u * r.total
+            out.append((b, draw_slack(c, b, r), float(r.weights[r.x]), min(t - r.lo, r.hi - t)))
+    return out
 
 
 def pair_distribution(p0, q0, p1, K):

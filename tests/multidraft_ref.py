@@ -100,11 +100,19 @@ def inverse_cdf(weights, u):
     return int(over[0]) if len(over) else int(pos[-1])
 
 
+def draw_interval(weights, x):
+    """(lo, hi): the fp64 running total of `weights` before and after element x — the inverse CDF
+    returns x for the targets u·Σ in [lo, hi)."""
+    c = np.cumsum(np.asarray(weights, dtype=np.float64))
+    return (float(c[x - 1]) if x > 0 else 0.0), float(c[x])
+
+
 def philox_step(P, Q, tok, seed, off, row, stops=(), greedy=False):
     """One sequence's step on the Philox noise of global row `row`: walk()'s namespace plus close
     (an accept test sat within the device's fp32 tolerance of its threshold), stop_index, x (fp64
     inverse CDF on the row's cdf uniform, argmax under greedy; None on a stop exit), prune_drafter,
-    prune_target, emitted (tok[winner, :n] + [x])."""
+    prune_target, emitted (tok[winner, :n] + [x]); and of the draw: u (the row's cdf uniform), total
+    (Σ weights) and lo, hi (draw_interval of x; NaN where no token was drawn by inverse CDF)."""
     K, g = tok.shape
     state = SimpleNamespace(close=False)
 
@@ -121,12 +129,16 @@ def philox_step(P, Q, tok, seed, off, row, stops=(), greedy=False):
     pruned = r.status == RESIDUAL and r.stop_index < 0
     r.prune_drafter, r.prune_target = (g - r.n, g - r.n + 1) if pruned else (0, 0)
     r.x = None
+    r.u = float(ph.cdf_uniform(seed, off, row))
+    r.total = float(np.sum(r.weights, dtype=np.float64))
+    r.lo = r.hi = math.nan
     if r.stop_index >= 0:
         r.status = STOP
     elif greedy:
         r.x = int(np.argmax(r.weights))
     elif r.final_mass > 0:
-        r.x = inverse_cdf(r.weights, ph.cdf_uniform(seed, off, row))
+        r.x = inverse_cdf(r.weights, r.u)
+        r.lo, r.hi = draw_interval(r.weights, r.x)
     r.emitted = r.accepted + ([r.x] if r.x is not None else [])
     return r
 

@@ -2,7 +2,11 @@
 
 * walks against the host model (tests/multidraft_ref.py over the exact-arithmetic oracle and the
   numpy Philox) on cases whose drafts the test chooses (tests/multi_walk.py; their coverage is proved
-  on the CPU by tests/test_multidraft_cpu.py);
+  on the CPU by tests/test_multidraft_cpu.py), the token of a stochastic row included: the host's
+  target u·Σ on the same Philox uniform lies in the running-total interval of the device's token,
+  widened by the mass bound (check_draw);
+* the same at the chunk edges of the draw (V around one 2048-element chunk of the mass launches, a
+  short last chunk that holds much of the mass);
 * K = 1 against sd_verify(SD_RULE_SPEC) on the same inputs, seed and offset;
 * losslessness on the device: the emitted tokens of 4096 sequences against the exact target;
 * stop lists, workspace reuse across entry points, and the decode loop with its trace.
@@ -62,14 +66,14 @@ def run_multi(sd, tl, dl, tok, proc, seed, off, row_base=0, stops=(), hints=Fals
     return SimpleNamespace(**{f: getattr(out, f).cpu() for f in sd.ops.MULTI_FIELDS}, tokens_out=out.tokens_out.cpu())
 
 
-def mass_tolerance(c, b, r):
-    """The bound on |device mass - host mass| of the last residual formed: 1e-5 (the project's mass
-    tolerance) plus flip_slack summed over the row pair the residual was formed from — how far the
-    rounded probabilities of the target and the drafter row can move when their softmax normalisers
-    are off by 1e-6.  The same bound whatever the number of rejected siblings."""
-    k0, d = r.mass_at
-    proc_l = lambda x: ref.processed_logits(x, c.proc, exact=True) / c.proc.temperature   # noqa: E731
-    return 1e-5 + mw.flip_slack(proc_l(c.tl[b, k0, d]), c.dtype) + mw.flip_slack(proc_l(c.dl[b, k0, d]), c.dtype)
+def check_draw(what, r, x, slack):
+    """The device's token x against the host model's inverse CDF on the same uniform: the host's
+    target u·Σ lies in the running-total interval of x, widened by 2·slack (multi_walk.draw_excess)."""
+    lo, hi = mref.draw_interval(r.weights, x)
+    used = mw.draw_excess(r, x, slack)
+    print(f"[multi-draw] {what} {r.status} nrej={len(r.masses) if r.status == mref.RESIDUAL else 0} x={x} host_x={r.x} "
+          f"chunk={x // mw.CHUNK} target={r.u * r.total:.9g} lo={lo:.9g} hi={hi:.9g} slack={slack:.3g} used={used:.3g}")
+    assert used <= 1.0, (what, x, r.x, r.u * r.total, lo, hi, slack)
 
 
 def check_case(sd, c, got, rows):
@@ -91,7 +95,7 @@ def check_case(sd, c, got, rows):
         want_bit = {mref.RESIDUAL: L.SD_ROW_RESIDUAL, mref.BONUS: L.SD_ROW_BONUS, mref.STOP: L.SD_ROW_STOP_IN_DRAFTS}
         assert st & (L.SD_ROW_RESIDUAL | L.SD_ROW_BONUS | L.SD_ROW_STOP_IN_DRAFTS) == want_bit[r.status], (b, hex(st))
         if r.rejects:
-            tol = mass_tolerance(c, b, r)
+            tol = mw.mass_tolerance(c, b, r)
             print(f"[multi-mass] b={b} rejects_at_node={len(r.masses)} dev={abs(float(got.resample_mass[b]) - r.mass):.3g} "
                   f"bound={tol:.3g} mass={r.mass:.6g}")
             assert abs(float(got.resample_mass[b]) - r.mass) <= tol, (b, float(got.resample_mass[b]), r.mass, tol)
@@ -105,6 +109,7 @@ def check_case(sd, c, got, rows):
         assert 0 <= x < c.V and row[n] == x and row[n + 1:] == [PAD] * (g - n)
         if c.proc.stochastic:
             assert r.weights[x] > 0, (b, x)          # positive weight in the final residual / bonus row
+            check_draw(f"b={b}", r, x, mw.draw_slack(c, b, r))
         else:
             assert r.weights[x] >= r.weights.max() * (1 - 1e-4), (b, x, r.x)
     assert close_rows <= 1
@@ -124,6 +129,29 @@ def test_walks_equal_the_host_model(sd, case, hints):
     got = run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE,
                     hints=hints)
     check_case(sd, c, got, rows)
+
+
+# ---------------------------------------------------------------- chunk edges of the draw
+def _edge_id(case):
+    return _id(case[:6]) + ("-tail" if case[6] else "")
+
+
+@pytest.mark.parametrize("hints", [False, True], ids=["stats-in-verify", "stats-from-draws"])
+@pytest.mark.parametrize("case", mw.edge_grid(), ids=_edge_id)
+def test_walks_at_the_chunk_edges_equal_the_host_model(sd, case, hints):
+    """V one below, at and above one 2048-element chunk of the mass launches, and one above two and
+    three: the draw's chunk pick, its hand-over of `target - before` to the element pick and the
+    one-element last chunk.  The boosted tail puts draws of both exits on both sides of the last
+    chunk's edge (tests/test_multidraft_cpu.py); greedy rows take the cross-chunk argmax, exact here
+    because the maximum is unique by check_case's margin."""
+    c = mw.edge_case(*case)
+    rows = mw.host_results(c)
+    got = run_multi(sd, c.tl.to(DEV), c.dl.to(DEV), c.tok.to(DEV), c.proc, mw.SEED, mw.OFFSET, mw.ROW_BASE,
+                    hints=hints)
+    check_case(sd, c, got, rows)
+    if not c.proc.stochastic:
+        same = [b for b, r in enumerate(rows) if int(got.n_accepted[b]) == r.n and int(got.winner[b]) == r.winner]
+        assert len(same) >= c.B - 1 and all(int(got.next_token[b]) == rows[b].x for b in same)
 
 
 # ---------------------------------------------------------------- K = 1 is sd_verify
@@ -147,10 +175,15 @@ def test_one_chain_equals_sd_verify(sd, name, V, dtype):
 
 
 # ---------------------------------------------------------------- losslessness on the device
-def _context_free(V, dtype, seed):
+def _context_free(V, dtype, seed, tail=False):
     g = torch.Generator().manual_seed(seed)
-    tl = (torch.randn(2, V, generator=g) * 2).to(dtype)               # depth-0 row, depth-1 / bonus row
-    dl = (tl.float() + 0.8 * torch.randn(2, V, generator=g)).to(dtype)
+    tl = torch.randn(2, V, generator=g) * 2                           # depth-0 row, depth-1 / bonus row
+    noise = 0.8 * torch.randn(2, V, generator=g)
+    if tail:                                                          # as multi_walk.edge_case: +8 / +6
+        tl[:, mw.last_chunk_start(V):] += 8
+        noise[:, mw.last_chunk_start(V):] -= 2
+    tl = tl.to(dtype)
+    dl = (tl.float() + noise).to(dtype)
     proc = mw.PROCS["multinomial"]
     return tl, dl, ref.process(tl, proc, exact=True).double().numpy(), ref.process(dl, proc, exact=True).double().numpy()
 
@@ -170,6 +203,34 @@ def test_first_token_keeps_the_target_distribution(sd, V, K):
     first = got.tokens_out[:, 0].numpy()
     assert first.min() >= 0
     chi2_check(first, p[0], f"first token V={V} K={K}")
+
+
+def test_first_token_keeps_the_target_distribution_across_chunks(sd):
+    """V = 4101 (three chunks of the mass launches, the last of 5 elements) with the boosted tail,
+    K = 2, γ = 1: the first emitted token against the exact p, and its chunk x // 2048 against the
+    chunk masses of p — a biased chunk pick or hand-over between the two levels of the draw shows in
+    either."""
+    B, V, K = 4096, 4101, 2
+    tl, dl, p, q = _context_free(V, torch.bfloat16, 5, tail=True)
+    rng = np.random.default_rng(100 + K)
+    tok = torch.from_numpy(rng.choice(V, size=(B, K, 1), p=q[0] / q[0].sum()))
+    T = torch.stack([tl[0], tl[1]]).to(DEV).expand(B, K, 2, V)
+    D = dl[:1].to(DEV).expand(B, K, 1, V)
+    got = run_multi(sd, T.contiguous(), D.contiguous(), tok.to(DEV), mw.PROCS["multinomial"], 99, 3)
+    first = got.tokens_out[:, 0].numpy()
+    assert first.min() >= 0
+    masses = np.add.reduceat(p[0], np.arange(0, V, mw.CHUNK))
+    assert len(masses) == 3 and masses.min() / masses.sum() > 0.02      # every chunk expects > 80 of 4096
+    # every exit is used: accepted drafts, residual draws and (n = 1) the bonus row's draws
+    st = got.row_status.numpy()
+    assert (st & sd.lib.SD_ROW_RESIDUAL != 0).sum() > B // 32 and (st & sd.lib.SD_ROW_BONUS != 0).sum() > B // 32
+    chi2_check(first, p[0], f"first token V={V} K={K}")
+    chi2_check(first // mw.CHUNK, masses, f"first token's chunk V={V} K={K}")
+    # the bonus row's draw (rows that accepted the draft): the second token against the exact p of row 1
+    full = got.n_accepted.numpy() == 1
+    second = got.tokens_out[:, 1].numpy()[full]
+    chi2_check(second, p[1], f"bonus token V={V} K={K}")
+    chi2_check(second // mw.CHUNK, np.add.reduceat(p[1], np.arange(0, V, mw.CHUNK)), f"bonus token's chunk V={V}")
 
 
 @pytest.mark.parametrize("K", [2, 4])
@@ -270,6 +331,11 @@ def _generate(pair, K, seed, **kw):
                                            max_gen_len=LOOP_TOKENS, eos_tokens_id=[LOOP_V + 5], num_drafts=K, **kw)
 
 
+def _bank_row(lm, token, position):
+    """A FakeLM's logit row at (token, position), as multi_walk.bank_rows picks it."""
+    return lm.bank[(int(token) * 31 + int(position) * lm.pos_mult) % lm.bank.shape[0]].cpu()
+
+
 def test_loop_steps_equal_the_host_model(sd, pair):
     """Every traced step recomputed from the FakeLM banks by the host model; every row of input_ids
     the models were handed equals the emitted sequence."""
@@ -301,6 +367,13 @@ def test_loop_steps_equal_the_host_model(sd, pair):
             close += 1
         assert seq[cur:cur + st["n"]] == tok[st["winner"], :st["n"]].tolist() and seq[cur + st["n"]] == st["x"]
         assert r.weights[st["x"]] > 0 or got != want
+        if got == want:
+            k0, d = r.mass_at if r.status == mref.RESIDUAL else (r.winner, g)
+            at = ([seq[cur - 1]] + tok[k0].tolist())[d]
+            slack = 1e-5 + mw.flip_slack(_bank_row(target, at, cur - 1 + d), target.bank.dtype)
+            if r.status == mref.RESIDUAL:
+                slack += mw.flip_slack(_bank_row(drafter, at, cur - 1 + d), drafter.bank.dtype)
+            check_draw(f"step cur={cur}", r, st["x"], slack)
     assert close <= 1
     assert sum(st["n"] for st in trace) / sum(st["g"] for st in trace) == pytest.approx(rate)
     # the target saw, at every step, K identical rows of the sequence emitted so far

@@ -1,7 +1,8 @@
 """CPU checks of the multi-draft verify: the rule itself (exact enumeration against the target's
 distribution), the host model against the single-chain host walk, the coverage of the GPU cases
-(tests/test_gpu_multidraft.py runs exactly multi_walk.grid()), the C ABI's argument checks through
-ctypes, and the torch op's fake implementation."""
+(tests/test_gpu_multidraft.py runs multi_walk.grid() and edge_grid(), tests/test_gpu_multidraft_edges.py
+small_grid()) and the sharpness of their draw check, the C ABI's argument checks through ctypes, and
+the torch op's fake implementation."""
 import ctypes as C
 import itertools
 
@@ -12,6 +13,7 @@ import torch
 import multi_walk as mw
 import multidraft_ref as mref
 import perf_walk
+import row_edges as rowe
 
 
 # ---------------------------------------------------------------- the rule is lossless
@@ -142,6 +144,99 @@ def test_other_gpu_cases_have_at_most_one_close_sequence():
         if case[0] != 16:
             c = mw.case(*case)
             assert sum(r.close for r in mw.host_results(c)) <= 1, case
+
+
+# ---------------------------------------------------------------- the draw check of the GPU cases
+def _gpu_case(kind, case):
+    if kind == "edge":
+        return mw.edge_case(*case)
+    return mw.small_case(*case[:7]) if kind == "small" else mw.case(*case)
+
+
+# what the GPU files run: the walk grid, the stop-list test's case, the chunk edges, the small vocabularies
+DRAW_CASES = ([("grid", c) for c in mw.grid()] + [("grid", (16, 4, 4, 4096, torch.bfloat16, "multinomial"))]
+              + [("edge", c) for c in mw.edge_grid()] + [("small", c) for c in mw.small_grid()])
+
+
+def _case_id(kc):
+    return kc[0] + "-" + "-".join(str(v).split(".")[-1] for v in kc[1])
+
+
+@pytest.mark.parametrize("kc", DRAW_CASES, ids=_case_id)
+def test_draw_check_is_sharp_on_every_gpu_case(kc):
+    """The GPU check holds the device's token to the host's target u·Σ within 2·slack of the token's
+    running-total interval.  That says something only while the interval is wider than what it is
+    widened by: 4·slack < w[x] in at least 90 % of a case's drawn rows; and the widening admits a
+    neighbouring token in at most 2 rows of a case (host target within 2·slack of lo or hi)."""
+    c = _gpu_case(*kc)
+    m = mw.draw_margins(c, mw.host_results(c))
+    wide = [b for b, slack, w, edge in m if 4 * slack < w]
+    near = [b for b, slack, w, edge in m if edge <= 2 * slack]
+    if m:
+        print(f"[draw-margin] {_case_id(kc)} drawn={len(m)} wide={len(wide)} near={near} "
+              f"worst 2 slack / w[x]={max(2 * slack / w for b, slack, w, edge in m):.3g}")
+    assert len(wide) >= 0.9 * len(m), (len(wide), len(m))
+    assert len(near) <= 2, near
+
+
+def test_edge_cases_draw_on_both_sides_of_the_last_chunk():
+    """The boosted-tail cases of multi_walk.edge_grid() on the host model: each has at least 3 rows
+    whose token lies in the short last chunk and at least 3 in an earlier one, at most one close row,
+    and (greedy) a maximum that is unique by the GPU check's 1e-4 margin, so the cross-chunk argmax
+    is exact; over the set, both exits draw from the last chunk and a residual draw follows two or
+    more rejections at its node.  Every case, boosted or not, has at most one close row."""
+    exits, deep = set(), 0
+    for case in mw.edge_grid():
+        c = mw.edge_case(*case)
+        rows = mw.host_results(c)
+        assert sum(r.close for r in rows) <= 1, case
+        if not c.proc.stochastic:
+            assert all(int((r.weights >= r.weights.max() * (1 - 1e-4)).sum()) == 1 for r in rows), case
+        if not c.tail:
+            continue
+        first = mw.last_chunk_start(c.V)
+        assert 0 < c.V - first < mw.CHUNK and first >= mw.CHUNK
+        last = [r for r in rows if r.x is not None and r.x >= first]
+        assert len(last) >= 3 and sum(r.x is not None and r.x < first for r in rows) >= 3, (case, len(last))
+        if c.proc.stochastic:
+            exits |= {r.status for r in last}
+            deep += sum(r.status == mref.RESIDUAL and len(r.masses) >= 2 for r in rows)
+    assert exits == {mref.RESIDUAL, mref.BONUS}
+    assert deep >= 1
+    # plain rows never reach the last chunk: why the tail is boosted
+    plain = [mw.edge_case(*case) for case in mw.edge_grid() if case[3] > mw.CHUNK and not case[6] and case[5] != "greedy"]
+    assert plain and not any(r.x >= mw.last_chunk_start(c.V) for c in plain for r in mw.host_results(c))
+
+
+def test_small_cases_on_the_host_model():
+    """tests/test_gpu_multidraft_edges.py's cases: top-k with k > V is k = V (the keep is the whole
+    finite row), V = 1 gives bonus exits only, every larger V reaches both exits in some case, no case
+    has more than one close row, and building the cases warns of nothing (a zero residual sum at small
+    V leaves the iid draft)."""
+    import warnings
+    from oracle import specdec_ref as ref
+    exits = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        for case in mw.small_grid():
+            B, K, g, V, dtype, name, mask, layout, hinted = case
+            c = mw.small_case.__wrapped__(*case[:7])
+            rows = mw.host_results(c)
+            assert sum(r.close for r in rows) <= 1, case
+            exits.setdefault(V, set()).update(r.status for r in rows)
+            if name == "topk50" and V < 50:
+                all_of = ref.Processor("topk", 1.0, top_k=V)
+                plain = ref.Processor("multinomial", 1.0)
+                for x in (c.tl, c.dl):
+                    assert torch.equal(ref.process(x, c.proc, exact=True), ref.process(x, all_of, exact=True))
+                    assert torch.equal(ref.process(x, c.proc, exact=True), ref.process(x, plain, exact=True))
+            # a target row and its drafter row have the same `-inf` entries
+            assert torch.equal(c.tl[:, :, :g].isinf(), c.dl.isinf()), case
+    assert exits[1] == {mref.BONUS}
+    assert all(exits[V] == {mref.RESIDUAL, mref.BONUS} for V in mw.SMALL_VOCABS if V > 1), exits
+    vs = {(c[3], c[7]) for c in mw.small_grid()} | {(c[3], c[4]) for c in mw.small_grid()}
+    assert all((V, x) in vs for V in mw.SMALL_VOCABS for x in rowe.LAYOUTS + tuple(mw.DTYPES))
+    assert len(mw.small_grid()) <= 150
 
 
 # ---------------------------------------------------------------- C ABI argument checks (ctypes)
