@@ -320,6 +320,7 @@ typedef enum {
     SD_PATH_VERIFY_FUSED_TICKET = 5,/* k_verify_fused in ticket order (ABI 11): one launch, any B  */
     SD_PATH_VERIFY_MULTI = 6,       /* sd_verify_multi: k_stats, k_multi_mass x (K+1), k_multi_walk */
     SD_PATH_VERIFY_VP = 7,          /* sd_vp_finish: the vocabulary-parallel step's last phase    */
+    SD_PATH_VERIFY_TREE = 8,        /* sd_verify_tree: k_stats, k_tree_mass x (C_max+1), k_tree_walk */
     SD_PATH_SAMPLE_DRAW_LEAN = 16,  /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
@@ -764,6 +765,91 @@ size_t sd_vp_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local);
 int32_t sd_vp_stats(const sd_vp_args* args, void* stream);
 int32_t sd_vp_decide(const sd_vp_args* args, void* stream);
 int32_t sd_vp_finish(const sd_vp_args* args, void* stream);
+
+/* ---- Token-tree speculative verification (csrc/sd_verify_tree.inc; additive, ABI 12) --------------
+ * One verify step over a token tree per sequence (SpecInfer / Medusa / EAGLE): N drafted nodes with
+ * arbitrary parents, scored by the target in one forward under a tree attention mask.  All B sequences
+ * of a call share one topology.  Nodes are 0..N-1; parent[i] is in {-1, 0..i-1}, -1 a child of the root
+ * (the last committed token).  Slot 0 is the root, slot i+1 node i.  The target row of slot s is the
+ * target's logit row after the path to s (N+1 rows); the drafter row of slot s is needed only where s
+ * has children, and the children of a slot must be iid draws from that slot's processed drafter row.
+ * Probabilities are SD_RULE_SPEC's (processor, temperature, rounded to the rows' dtype); target and
+ * drafter rows share ONE processor and one dtype.  Per sequence:
+ *
+ *   s = 0; path = []
+ *   loop:
+ *       C = children of s, ascending node index
+ *       if C empty: x ~ P(target row s), SD_ROW_BONUS, stop
+ *       p = P(target row s);  q = P(drafter row s);  r = p
+ *       for c in C:
+ *           x = tok[c];  u = accept uniform number c
+ *           if not (u > r[x] / q[x]): path += [c]; s = c + 1; continue the outer loop   (fp32, as SPEC)
+ *           m = Σ_v max(r[v] - q[v], 0);  r = max(r - q, 0) / m          (one more sibling rejected)
+ *       x ~ r, SD_ROW_RESIDUAL, stop
+ *   n = len(path)
+ *
+ * then the stop scan over the path's tokens (the stop listed first that occurs, at its first position:
+ * SD_ROW_STOP_IN_DRAFTS, stop_index, no token drawn, next_token = -1).  Noise is SD_NOISE_PHILOX only
+ * (SD_NOISE_STREAM: SD_ERR_UNSUPPORTED): sequence b is row row_base + b, the sample is drawn by inverse
+ * CDF on the row's cdf uniform (greedy: the argmax, lowest index first); one call consumes one offset.
+ * Out-of-range draft ids, zero or NaN mass (SD_ROW_INVALID_DIST), status_or and resample_mass behave
+ * as in sd_verify_multi.  Bad topology (a parent out of range or not below its child's index):
+ * SD_ERR_INVALID; more than SD_TREE_MAX_CHILDREN children of one slot, depth above SD_MAX_GAMMA, N above
+ * SD_TREE_MAX_NODES or a grid beyond the launch limits: SD_ERR_UNSUPPORTED.
+ * Kernels: the row statistics of the N+1 target rows and the I internal drafter rows per sequence, then
+ * C_max + 1 launches (C_max the largest child count) that form the residual masses m_1..m_c of every
+ * internal slot with c children, then one launch that walks and samples.  No workgroup waits on
+ * another (launch boundaries only): capturable, safe on a shared GPU.                               */
+#define SD_TREE_MAX_NODES 64       /* N                                                              */
+#define SD_TREE_MAX_CHILDREN 8     /* children of one slot                                           */
+#define SD_TREE_MAX_BATCH 16384    /* B                                                              */
+
+typedef struct {
+    int32_t batch;               /* B                                                              */
+    int32_t num_nodes;           /* N, 1..SD_TREE_MAX_NODES                                         */
+    int32_t vocab;
+    int32_t parent[SD_TREE_MAX_NODES];   /* host: parent[i] in {-1, 0..i-1}; entries from N on unread */
+    /* rows by slot: target row of slot s at target_rows[s] + b * target_stride_b, drafter row at
+       draft_rows[s] + b * draft_stride_b (entries of leaf slots are ignored and may be null)       */
+    const void* target_rows[SD_TREE_MAX_NODES + 1];
+    int64_t target_stride_b;
+    const void* draft_rows[SD_TREE_MAX_NODES + 1];
+    int64_t draft_stride_b;
+    int32_t dtype;               /* sd_dtype of every row                                           */
+    const int64_t* draft_tokens; /* [B, >=N] the nodes' drafted ids                                 */
+    int64_t draft_tokens_stride_b;
+    sd_processor proc;           /* the loop's logits_processor, for target and drafter rows       */
+    const int64_t* stop_tokens;  /* device [n_stop]                                                */
+    int32_t n_stop;
+    int64_t pad_token;           /* fills tokens_out past the emitted tokens                        */
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+
+    /* outputs, device, [B] */
+    int32_t* n_accepted;         /* accepted depth n                                               */
+    int32_t* last_node;          /* the deepest accepted node, -1 if none                           */
+    int64_t* next_token;         /* x, -1 if none (stop token on the path)                          */
+    float* resample_mass;        /* mass m of the last residual formed, NaN if none (nullable)      */
+    int32_t* n_sibling_rejects;  /* accept tests that failed (nullable)                             */
+    int32_t* stop_index;         /* position of the stop token on the path, -1 (nullable)           */
+    int32_t* row_status;         /* SD_ROW_* bits                                                  */
+    /* int32 [B, >=depth] at path + b * path_stride_b: the node accepted at each depth, -1 beyond n
+       (depth: the tree's, the longest root-to-leaf path in nodes)                                  */
+    int32_t* path;
+    int64_t path_stride_b;
+    /* optional (nullable): int64 [B, >=depth+1] at tokens_out + b * tokens_out_stride_b: the path's
+       tokens, then x (when one was drawn), then pad_token up to depth+1 entries                    */
+    int64_t* tokens_out;
+    int64_t tokens_out_stride_b;
+
+    void* workspace;             /* sd_verify_tree_workspace_size bytes, zero-filled once; shares
+                                    the other entry points' convention (counter block left at zero) */
+    size_t workspace_bytes;
+    int32_t* status_or;          /* nullable: every sequence's SD_ROW_ERROR_MASK bits ORed in       */
+} sd_tree_args;
+
+/* 0 for a topology or shape sd_verify_tree does not take                                            */
+size_t sd_verify_tree_workspace_size(int32_t batch, int32_t num_nodes, const int32_t* parent, int32_t vocab);
+int32_t sd_verify_tree(const sd_tree_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,8 @@
 //
 // The multi-draft verify (sd_verify_multi, sd_verify_multi.inc): k_stats, then K + 1 mass launches over
 // every (chain, depth) row pair and one walk-and-draw launch; launch boundaries only.
+// The token-tree verify (sd_verify_tree, sd_verify_tree.inc): k_stats over the tree's rows in row groups,
+// then C_max + 1 mass launches over the slots that still have a j-th child and one walk-and-draw launch.
 //
 // Every logit row is read once by the statistics pass (the algorithmic bytes); the sampling pass
 // re-reads at most two rows per sequence (served from the 256 MiB Infinity Cache).  See DESIGN.md.
@@ -3583,9 +3585,10 @@ constexpr int kEptSmall = 8;
 
 int max_chunks(int vocab) { return (vocab + kThreads * kEptSmall - 1) / (kThreads * kEptSmall); }
 
-void carve(Plan& P, Carve& c, int rows_total, int B, int gamma, int vocab) {
+// everything of a Plan's workspace but the counter block: a call that runs several Plans (sd_verify_tree's
+// row groups) carves one of these per Plan behind the one counter block they share
+void carve_rows(Plan& P, Carve& c, int rows_total, int B, int gamma, int vocab) {
     const int nc = max_chunks(vocab);
-    P.cnt = c.take<uint32_t>(kCntBlockBytes / sizeof(uint32_t));   // first, at a fixed offset (sd_device.h)
     P.part = c.take<float2>((size_t)rows_total * nc);
     P.rowstat = c.take<float2>(rows_total);
     P.keep = c.take<RowKeep>(rows_total);
@@ -3606,6 +3609,11 @@ void carve(Plan& P, Carve& c, int rows_total, int B, int gamma, int vocab) {
     P.thr_hist = c.take<int32_t>((size_t)rows_total * kThrWin);
     P.thr_shist = c.take<int32_t>((size_t)kThrShistSlots * kThrWin);
     P.thr = c.take<ThrRow>(rows_total);
+}
+
+void carve(Plan& P, Carve& c, int rows_total, int B, int gamma, int vocab) {
+    P.cnt = c.take<uint32_t>(kCntBlockBytes / sizeof(uint32_t));   // first, at a fixed offset (sd_device.h)
+    carve_rows(P, c, rows_total, B, gamma, vocab);
 }
 
 bool valid_proc(const sd_processor& p) {
@@ -4339,3 +4347,4 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
 
 #include "sd_ngram.inc"
 #include "sd_verify_multi.inc"
+#include "sd_verify_tree.inc"

@@ -598,6 +598,132 @@ def verify_multi(target, draft, draft_tokens: torch.Tensor, proc, noise, num_dra
     return out
 
 
+# --------------------------------------------------------------------------- token-tree verify
+TREE_FIELDS = ("n_accepted", "last_node", "next_token", "resample_mass", "n_sibling_rejects", "stop_index",
+               "row_status")
+
+
+def _tree_of(parent):
+    from .tree import TokenTree
+    return parent if isinstance(parent, TokenTree) else TokenTree(parent)
+
+
+_ROW_PTRS = C.c_void_p * (_lib.SD_TREE_MAX_NODES + 1)
+
+
+def _slot_rows(x, name: str, slots, n_slots: int, like):
+    """(addresses by slot (None where the slot is not in `slots`), batch stride, B, V, dtype, device)
+    of the rows of `slots`: x is a tensor [B, len(slots), V] holding them in order, or a sequence of
+    n_slots entries [B, V] (entries outside `slots` are ignored).  like: the (B, V, dtype, device) the
+    rows must share with the other side, or None."""
+    ptrs = [None] * n_slots
+    if torch.is_tensor(x):
+        if x.dim() != 3 or x.shape[1] != len(slots):
+            raise ValueError(f"{name}: expected [B, {len(slots)}, V], got {tuple(x.shape)}")
+        B, _, V = x.shape
+        _require_rows(x[:, 0, :], f"{name}_rows", V)
+        step = x.stride(1) * x.element_size()
+        base = x.data_ptr()
+        for i, s in enumerate(slots):
+            ptrs[s] = base + i * step
+        stride, dt, dev = (x.stride(0) if B > 1 else 0), x.dtype, x.device
+    else:
+        rows = list(x)
+        if len(rows) != n_slots:
+            raise ValueError(f"expected {n_slots} {name} entries, got {len(rows)}")
+        first = rows[slots[0]]
+        if first is None:
+            raise ValueError(f"{name}_rows[{slots[0]}]: slot {slots[0]} needs a row")
+        B, V = first.shape[0], first.shape[-1]
+        stride, dt, dev = (first.stride(0) if B > 1 else 0), first.dtype, first.device
+        for s in slots:
+            t = rows[s]
+            if t is None:
+                raise ValueError(f"{name}_rows[{s}]: slot {s} has children and needs a drafter row")
+            _require_rows(t, f"{name}_rows[{s}]", V)
+            if t.shape[0] != B or t.dtype != dt or (B > 1 and t.stride(0) != stride) or t.device != dev:
+                raise ValueError(f"{name} rows must share batch, dtype, row stride and device")
+            ptrs[s] = t.data_ptr()
+    if like is not None and (B, V, dt, dev) != like:
+        raise ValueError("target and draft rows must share batch, vocabulary, dtype and device")
+    return ptrs, stride, B, V, dt, dev
+
+
+def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
+                stop_tokens: Optional[torch.Tensor] = None, row_base: int = 0,
+                status_or: Optional[torch.Tensor] = None, pad_token_id: int = 0, want_tokens: bool = True):
+    """One token-tree verify step (sd_verify_tree): N drafted nodes per sequence with parents
+    ``parent`` (a TokenTree or a parent list; one topology for the whole call), walked from the root by
+    recursive rejection sampling, so the emitted tokens keep the target's distribution exactly.
+
+    target: [B, N+1, V] logits (or N+1 tensors [B, V]): slot 0 the root's row, slot i+1 the row after
+    node i.  draft: a list of N+1 entries [B, V] with None at leaf slots, or a [B, I, V] tensor holding
+    the internal slots' rows in ascending slot order.  draft_tokens: int64 [B, >=N].  proc: one of the
+    five processors, used for target and drafter rows alike.  noise: PhiloxNoise (one offset per call).
+    Returns a namespace of the [B] outputs n_accepted, last_node, next_token, resample_mass,
+    n_sibling_rejects, stop_index, row_status, of path int32 [B, depth] (the node accepted at each
+    depth, -1 beyond n) and tokens_out int64 [B, depth+1] (the path's tokens, then x, then
+    pad_token_id; None without want_tokens)."""
+    from types import SimpleNamespace
+    if _user_process(proc) is not None:
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: verify_tree fuses the processing "
+                        "of target and drafter rows and cannot run a user _process")
+    spec = proc_spec(proc)
+    if not isinstance(noise, PhiloxNoise):
+        raise TypeError("verify_tree needs PhiloxNoise (the rule defines no stream order for this step)")
+    tree = _tree_of(parent)
+    N, depth = tree.num_nodes, tree.depth
+    internal = tree.internal_slots
+    # slot -> device address of its row of sequence 0, and the batch stride in elements
+    t_ptrs, t_stride, B, V, tdt, dev = _slot_rows(target, "target", list(range(N + 1)), N + 1, None)
+    d_ptrs, d_stride, _, _, _, _ = _slot_rows(draft, "draft", internal, N + 1, (B, V, tdt, dev))
+    if not 1 <= B <= _lib.SD_TREE_MAX_BATCH:
+        raise ValueError(f"verify_tree: batch must be in 1..{_lib.SD_TREE_MAX_BATCH}, got {B}")
+    if draft_tokens.dtype != torch.long or draft_tokens.dim() != 2 or draft_tokens.shape[0] != B \
+            or draft_tokens.shape[1] < N or draft_tokens.stride(1) != 1 or draft_tokens.device != dev:
+        raise ValueError(f"draft_tokens must be int64 [B, >={N}] on {dev}")
+    stops = stop_tokens if stop_tokens is not None else torch.empty(0, dtype=torch.long, device=dev)
+    if stops.dtype != torch.long or stops.device != dev or not stops.is_contiguous():
+        raise ValueError("stop_tokens must be a contiguous int64 device tensor")
+    # one allocation: next_token (int64) first, then the six 4-byte fields and the path
+    buf = torch.empty(8 * B + 4 * (6 + depth) * B, dtype=torch.uint8, device=dev)
+    nxt = buf[:8 * B].view(torch.long)
+    f4 = buf[8 * B:].view(torch.int32)
+    i32 = [f4[k * B:(k + 1) * B] for k in range(6)]
+    out = SimpleNamespace(n_accepted=i32[0], last_node=i32[1], next_token=nxt, resample_mass=i32[2].view(torch.float32),
+                          n_sibling_rejects=i32[3], stop_index=i32[4], row_status=i32[5],
+                          path=f4[6 * B:].view(B, depth),
+                          tokens_out=torch.empty(B, depth + 1, dtype=torch.long, device=dev) if want_tokens else None)
+    nz, keep = _noise_struct(noise, 0, dev, row_base)
+    par = getattr(tree, "_c_parent", None)
+    if par is None:
+        par = tree._c_parent = (C.c_int32 * _lib.SD_TREE_MAX_NODES)(*tree.parent)
+    ws = _workspace(lib.sd_verify_tree_workspace_size(B, N, par, V), dev)
+    a = _lib.sd_tree_args()
+    a.batch, a.num_nodes, a.vocab = B, N, V
+    a.parent = par
+    a.target_rows = _ROW_PTRS(*t_ptrs)
+    a.draft_rows = _ROW_PTRS(*d_ptrs)
+    a.target_stride_b, a.draft_stride_b = t_stride, d_stride
+    a.dtype = _DT[tdt]
+    a.draft_tokens = draft_tokens.data_ptr()
+    a.draft_tokens_stride_b = draft_tokens.stride(0) if B > 1 else draft_tokens.shape[1]
+    a.proc = spec.struct()
+    a.stop_tokens, a.n_stop = (stops.data_ptr() if stops.numel() else None), stops.numel()
+    a.pad_token = int(pad_token_id)
+    a.noise = nz
+    for f in TREE_FIELDS:
+        setattr(a, f, getattr(out, f).data_ptr())
+    a.path, a.path_stride_b = out.path.data_ptr(), depth
+    if want_tokens:
+        a.tokens_out, a.tokens_out_stride_b = out.tokens_out.data_ptr(), depth + 1
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_verify_tree(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_verify_tree")
+    del keep
+    return out
+
+
 # --------------------------------------------------------------------------- n-gram verify (A11)
 @dataclass
 class NgramOut:

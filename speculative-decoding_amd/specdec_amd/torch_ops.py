@@ -19,6 +19,13 @@ GPU), and callable as ``torch.ops.specdec.*``.
             prune_drafter, prune_target, stop_index, row_status int32 [B])
         One multi-draft verify step over K chains per sequence (sd_verify_multi), Philox noise.
 
+    torch.ops.specdec.verify_tree(target [B, N+1, V], draft [B, I, V], draft_tokens int64 [B, >=N], parent int[N],
+                                  stop_tokens int64 [n], kind, temperature, top_k, top_p, seed, offset, row_base)
+        -> (n_accepted, last_node int32 [B], next_token int64 [B], resample_mass fp32 [B], n_sibling_rejects,
+            stop_index, row_status int32 [B], path int32 [B, depth])
+        One token-tree verify step (sd_verify_tree): N nodes with parents `parent`, the I internal slots'
+        drafter rows in ascending slot order, Philox noise.
+
     torch.ops.specdec.beam_topk(logits [R, V], k) -> (logprob fp32 [R, k], token int64 [R, k])
         The beam step's row pass: topk(log_softmax(logits), k), lowest index first among equal values
         (sampling/base_decoding.py:136-137).
@@ -40,7 +47,7 @@ mode keeps generator state on the host side and stays on the Python API.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import List, Tuple
 
 import torch
 from torch import Tensor
@@ -113,6 +120,27 @@ def _(target, draft, draft_tokens, stop_tokens, kind, temperature, top_k, top_p,
     B = target.shape[0]
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
     return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.MULTI_FIELDS)
+
+
+@torch.library.custom_op("specdec::verify_tree", mutates_args=())
+def verify_tree(target: Tensor, draft: Tensor, draft_tokens: Tensor, parent: List[int], stop_tokens: Tensor, kind: int,
+                temperature: float, top_k: int, top_p: float, seed: int, offset: int,
+                row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """One token-tree verify step (ops.verify_tree): target [B, N+1, V], draft [B, I, V] (the internal
+    slots), draft_tokens int64 [B, >=N]; the seven [B] outputs in ops.TREE_FIELDS' order, then path."""
+    out = ops.verify_tree(target, draft, draft_tokens, list(parent), _spec(kind, temperature, top_k, top_p),
+                          PhiloxNoise(seed, offset), stop_tokens=stop_tokens, row_base=row_base, want_tokens=False)
+    # views of one buffer: outputs may not alias
+    return tuple(getattr(out, f).clone() for f in ops.TREE_FIELDS) + (out.path.clone(),)
+
+
+@verify_tree.register_fake
+def _(target, draft, draft_tokens, parent, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
+    from .tree import TokenTree
+    B = target.shape[0]
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.TREE_FIELDS) + (
+        target.new_empty(B, TokenTree(list(parent)).depth, dtype=torch.int32),)
 
 
 def _vp_step(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens, shard: int, num_shards: int,
