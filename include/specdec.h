@@ -851,6 +851,54 @@ typedef struct {
 size_t sd_verify_tree_workspace_size(int32_t batch, int32_t num_nodes, const int32_t* parent, int32_t vocab);
 int32_t sd_verify_tree(const sd_tree_args* args, void* stream);
 
+/* ---- KV-cache compaction onto an accepted tree path (csrc/kv_compact.hip; additive, ABI 12) ---------
+ * After a tree-masked forward the cache holds the N tree nodes behind the committed tokens, node i at
+ * position base + slot(i); sd_verify_tree's `path` names the accepted node of every depth.  One launch
+ * moves the accepted rows of ALL K/V tensors (every layer) to the front.  For every tensor t, sequence
+ * b, head h and depth d < min(count[b], max_depth), IN ASCENDING d:
+ *
+ *     src = base_b + slot(path[b][d]);   dst = base_b + d
+ *     if src != dst: copy row_bytes bytes from
+ *         tensors[t] + b*stride_b + h*stride_h + src*stride_pos   to   ... + dst*stride_pos
+ *
+ * slot(i) = node_slot[i] when node_slot is given, else i; base_b = base (+ *base_dev when given).
+ * The copy is dtype-agnostic (bytes).  In place: slot(path[d]) >= d, so a destination never lies above
+ * its source, but depth d's destination may be depth d-1's source.  One thread owns a fixed byte range
+ * of one (tensor, b, head) for all depths and walks d upward, so everything written before depth d lies
+ * below position base_b + d <= src: no load can read a byte an earlier depth wrote.
+ * On the device a path entry outside [0, SD_TREE_MAX_NODES), or a slot outside [d, num_slots), ends
+ * that sequence's moves at that depth (-1 beyond n is the normal case); when count[b] says the entry
+ * should have been moved, SD_ROW_INVALID_DIST is ORed into status_or.  A base_b with base_b < 0 or
+ * base_b + num_slots > num_positions moves nothing and raises the same bit.  Nothing outside positions
+ * [base_b, base_b + num_slots) is read or written.  One launch, no workspace, no workgroup waits on
+ * another: capturable, safe on a shared GPU.                                                         */
+#define SD_KV_MAX_TENSORS 256
+
+typedef struct {
+    int32_t n_tensors;           /* 1..SD_KV_MAX_TENSORS                                            */
+    int32_t batch;               /* B                                                              */
+    int32_t heads;               /* H                                                              */
+    int32_t max_depth;           /* 1..SD_MAX_GAMMA: entries of a path row that may be read          */
+    int32_t num_slots;           /* 1..SD_TREE_MAX_NODES: positions [base_b, base_b + num_slots)      */
+    int32_t row_bytes;           /* head_dim * element size; even                                   */
+    void* const* tensors;        /* HOST array of n_tensors device pointers (the K and V buffers of
+                                    every layer, one shape); handed to the kernel by value           */
+    int64_t stride_b;            /* byte strides of the batch, head and position axes               */
+    int64_t stride_h;
+    int64_t stride_pos;          /* >= row_bytes                                                    */
+    int64_t num_positions;       /* L, positions of a (b, head) row set; >= num_slots                */
+    int64_t base;                /* host part of the base position                                  */
+    const int64_t* base_dev;     /* nullable: device int64 [1] added to base when the kernel runs
+                                    (transformers' StaticLayer.cumulative_length is an int64 tensor) */
+    const int32_t* path;         /* device int32 [B, >=max_depth]: sd_verify_tree's output          */
+    int64_t path_stride_b;       /* >= max_depth                                                    */
+    const int32_t* count;        /* device int32 [B]: usually sd_verify_tree's n_accepted            */
+    const int32_t* node_slot;    /* nullable HOST int32 [SD_TREE_MAX_NODES]: node -> cache slot      */
+    int32_t* status_or;          /* nullable device int32 [1]                                       */
+} sd_kv_compact_args;
+
+int32_t sd_kv_compact(const sd_kv_compact_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ dadiaokua/speculative-decoding).
 Module layout mirrors the reference's import paths for the hot path:
 
     specdec_amd.utils.logits_processor   <- utils/logits_processor.py
-    specdec_amd.utils.caching            <- utils/caching.py
+    specdec_amd.utils.caching            <- utils/caching.py; compact_cache (a cache onto a tree's accepted path)
     specdec_amd.sampling                 <- sampling/speculative_decoding.py (speculative_generate, max_fn);
                                             multidraft_speculative_generate (K draft chains per step);
                                             vocab_parallel_speculative_generate (tensor-parallel target)
@@ -19,11 +19,11 @@ All compute goes through libspecdec.so (HIP, gfx950); importing fails if it is m
 from . import _lib  # noqa: F401  (loads libspecdec.so or raises)
 from ._lib import RowError, get_poll_policy, set_poll_policy  # noqa: F401
 from .noise import PhiloxNoise, StreamNoise, default_noise, set_noise_mode  # noqa: F401
-from .ops import ProcSpec, proc_spec, probs_rows, sample_rows, verify, verify_multi, verify_tree  # noqa: F401
+from .ops import ProcSpec, kv_compact, proc_spec, probs_rows, sample_rows, verify, verify_multi, verify_tree  # noqa: F401
 from .tree import TokenTree  # noqa: F401
 from .vocab_parallel import GroupExchange, LocalShards, VocabShard, verify_vocab_parallel  # noqa: F401
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.specdec.sample / .verify)
 
 __all__ = ["RowError", "get_poll_policy", "set_poll_policy", "PhiloxNoise", "StreamNoise", "default_noise", "set_noise_mode", "ProcSpec", "proc_spec",
-           "probs_rows", "sample_rows", "verify", "verify_multi", "verify_tree", "TokenTree", "GroupExchange", "LocalShards", "VocabShard",
+           "probs_rows", "sample_rows", "verify", "verify_multi", "verify_tree", "kv_compact", "TokenTree", "GroupExchange", "LocalShards", "VocabShard",
            "verify_vocab_parallel"]

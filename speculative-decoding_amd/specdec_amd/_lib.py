@@ -69,7 +69,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_verify_multi_workspace_size", "sd_verify_multi",
            "sd_vp_stats_bytes", "sd_vp_cand_bytes", "sd_vp_workspace_size", "sd_vp_stats", "sd_vp_decide",
            "sd_vp_finish",
-           "sd_verify_tree_workspace_size", "sd_verify_tree")
+           "sd_verify_tree_workspace_size", "sd_verify_tree",
+           "sd_kv_compact")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -81,6 +82,9 @@ SD_MULTI_MAX_DRAFTS, SD_MULTI_MAX_NODES, SD_MULTI_MAX_ROWS = 8, 64, 16384
 
 # token-tree verify
 SD_TREE_MAX_NODES, SD_TREE_MAX_CHILDREN, SD_TREE_MAX_BATCH = 64, 8, 16384
+
+# KV-cache compaction onto a tree path
+SD_KV_MAX_TENSORS = 256
 
 # beam step (ABI 12)
 SD_BEAM_MAX_BEAMS, SD_BEAM_MAX_TOPK, SD_BEAM_MAX_CANDIDATES, SD_BEAM_MAX_VOCAB = 64, 64, 1024, 524288
@@ -240,6 +244,18 @@ class sd_tree_args(C.Structure):
     ]
 
 
+class sd_kv_compact_args(C.Structure):
+    _fields_ = [
+        ("n_tensors", C.c_int32), ("batch", C.c_int32), ("heads", C.c_int32), ("max_depth", C.c_int32),
+        ("num_slots", C.c_int32), ("row_bytes", C.c_int32),
+        ("tensors", C.POINTER(C.c_void_p)),
+        ("stride_b", C.c_int64), ("stride_h", C.c_int64), ("stride_pos", C.c_int64),
+        ("num_positions", C.c_int64), ("base", C.c_int64), ("base_dev", C.c_void_p),
+        ("path", C.c_void_p), ("path_stride_b", C.c_int64), ("count", C.c_void_p),
+        ("node_slot", C.POINTER(C.c_int32)), ("status_or", C.c_void_p),
+    ]
+
+
 class sd_vp_header(C.Structure):
     _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
                 ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
@@ -321,6 +337,8 @@ def _load():
     lib.sd_verify_tree_workspace_size.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
     lib.sd_verify_tree.restype = C.c_int32
     lib.sd_verify_tree.argtypes = [C.POINTER(sd_tree_args), C.c_void_p]
+    lib.sd_kv_compact.restype = C.c_int32
+    lib.sd_kv_compact.argtypes = [C.POINTER(sd_kv_compact_args), C.c_void_p]
     lib.sd_vp_stats_bytes.restype = C.c_size_t
     lib.sd_vp_stats_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.sd_vp_cand_bytes.restype = C.c_size_t

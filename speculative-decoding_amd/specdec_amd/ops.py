@@ -724,6 +724,75 @@ def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
     return out
 
 
+# --------------------------------------------------------------------------- KV-cache compaction
+def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, num_slots: int, node_slot=None,
+               base_dev: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None) -> None:
+    """Move the accepted path of a token tree to the front of its cache window, in place
+    (sd_kv_compact): in every tensor of ``tensors`` (the K and V buffers [B, H, L, D] of all layers: one
+    shape, dtype and stride set, unit stride along D), for every sequence b and depth
+    d < min(count[b], path.shape[1]) in ascending d, position ``base + slot(path[b, d])`` is copied to
+    ``base + d``.  path: int32 [B, depth] and count: int32 [B] on the device, as ``verify_tree``
+    returns them (``path``, ``n_accepted``): nothing is read back.  slot(i) is ``node_slot[i]`` (a host
+    sequence: node index -> the order in which the node entered the cache) or i.  base_dev: an int64
+    device tensor of one element added to ``base`` when the kernel runs (a StaticLayer's
+    ``cumulative_length``), so a captured step needs no host value.  Only positions
+    [base, base + num_slots) are read or written; a path entry that leaves the window ends its
+    sequence's moves and ORs SD_ROW_INVALID_DIST into ``status_or``.  More than SD_KV_MAX_TENSORS
+    tensors take one launch per 256, on the current stream."""
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("kv_compact: no tensors")
+    t0 = tensors[0]
+    if t0.dim() != 4:
+        raise ValueError(f"kv_compact: expected [B, H, L, D] tensors, got {tuple(t0.shape)}")
+    for t in tensors:
+        if t.shape != t0.shape or t.dtype != t0.dtype or t.stride() != t0.stride() or t.device != t0.device:
+            raise ValueError("kv_compact: the tensors must share one shape, dtype, stride set and device")
+    if t0.stride(3) != 1:
+        raise ValueError("kv_compact: the last dimension must have unit stride")
+    B, H, L, D = t0.shape
+    es, dev = t0.element_size(), t0.device
+    if (D * es) % 2:
+        raise ValueError("kv_compact: rows of an odd number of bytes are not supported")
+    if not t0.is_cuda:
+        raise ValueError("kv_compact: the tensors must be device tensors")
+    if path.dtype != torch.int32 or path.dim() != 2 or path.shape[0] != B or path.stride(1) != 1 or path.device != dev \
+            or not 1 <= path.shape[1] <= _lib.SD_MAX_GAMMA:
+        raise ValueError(f"kv_compact: path must be int32 [B, 1..{_lib.SD_MAX_GAMMA}] on {dev}")
+    if count.dtype != torch.int32 or count.shape != (B,) or count.device != dev or not count.is_contiguous():
+        raise ValueError(f"kv_compact: count must be a contiguous int32 [B] on {dev}")
+    num_slots, base = int(num_slots), int(base)
+    if not 1 <= num_slots <= min(_lib.SD_TREE_MAX_NODES, L):
+        raise ValueError(f"kv_compact: num_slots must be in 1..{min(_lib.SD_TREE_MAX_NODES, L)}, got {num_slots}")
+    if base_dev is None:
+        if not 0 <= base <= L - num_slots:
+            raise ValueError(f"kv_compact: positions [{base}, {base + num_slots}) leave the cache's {L}")
+    elif base_dev.dtype != torch.int64 or base_dev.numel() != 1 or base_dev.device != dev:
+        raise ValueError("kv_compact: base_dev must be an int64 tensor of one element on the tensors' device")
+    slots = None
+    if node_slot is not None:
+        node_slot = [int(s) for s in node_slot]
+        if len(node_slot) > _lib.SD_TREE_MAX_NODES:
+            raise ValueError(f"kv_compact: node_slot has at most {_lib.SD_TREE_MAX_NODES} entries")
+        slots = (C.c_int32 * _lib.SD_TREE_MAX_NODES)(*(node_slot + [-1] * (_lib.SD_TREE_MAX_NODES - len(node_slot))))
+    a = _lib.sd_kv_compact_args()
+    a.batch, a.heads, a.max_depth, a.num_slots, a.row_bytes = B, H, path.shape[1], num_slots, D * es
+    a.stride_b, a.stride_h, a.stride_pos = (t0.stride(0) * es if B > 1 else 0), t0.stride(1) * es, t0.stride(2) * es
+    a.num_positions, a.base = L, base
+    a.base_dev = base_dev.data_ptr() if base_dev is not None else None
+    a.path, a.path_stride_b = path.data_ptr(), (path.stride(0) if B > 1 else path.shape[1])
+    a.count = count.data_ptr()
+    if slots is not None:
+        a.node_slot = slots
+    a.status_or = _status_or_ptr(status_or, dev)
+    stream = C.c_void_p(_stream_ptr(dev))
+    for i in range(0, len(tensors), _lib.SD_KV_MAX_TENSORS):
+        part = tensors[i:i + _lib.SD_KV_MAX_TENSORS]
+        table = (C.c_void_p * len(part))(*(t.data_ptr() for t in part))
+        a.n_tensors, a.tensors = len(part), table
+        _lib.check(lib.sd_kv_compact(C.byref(a), stream), "sd_kv_compact")
+
+
 # --------------------------------------------------------------------------- n-gram verify (A11)
 @dataclass
 class NgramOut:

@@ -42,12 +42,18 @@ GPU), and callable as ``torch.ops.specdec.*``.
         The three phases of the vocabulary-parallel verify on one rank's slices (sd_vp_stats / sd_vp_decide /
         sd_vp_finish; specdec_amd.vocab_parallel); the caller all-gathers the blocks between them.
 
+    torch.ops.specdec.kv_compact(tensors Tensor[] ([B, H, L, D] each), path int32 [B, depth], count int32 [B], base,
+                                 num_slots, node_slot int[]?, base_dev int64 [1]?) -> ()
+        KV-cache compaction onto the accepted path (sd_kv_compact), in place: in every tensor, position
+        base + slot(path[b, d]) moves to base + d for d < count[b].  Mutates `tensors`; the sticky error
+        word (status_or) stays on the Python API, ops.kv_compact.
+
 All run the same C-ABI calls as ``specdec_amd.ops`` (libspecdec.so); the parity STREAM noise
 mode keeps generator state on the host side and stays on the Python API.
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -213,3 +219,15 @@ def beam_topk(logits: Tensor, k: int) -> Tuple[Tensor, Tensor]:
 def _(logits, k):
     R = logits.shape[0]
     return logits.new_empty(R, k, dtype=torch.float32), logits.new_empty(R, k, dtype=torch.long)
+
+
+@torch.library.custom_op("specdec::kv_compact", mutates_args=("tensors",))
+def kv_compact(tensors: List[Tensor], path: Tensor, count: Tensor, base: int, num_slots: int,
+               node_slot: Optional[List[int]] = None, base_dev: Optional[Tensor] = None) -> None:
+    """ops.kv_compact: the K/V tensors of all layers compacted in place onto verify_tree's path."""
+    ops.kv_compact(tensors, path, count, base, num_slots=num_slots, node_slot=node_slot, base_dev=base_dev)
+
+
+@kv_compact.register_fake
+def _(tensors, path, count, base, num_slots, node_slot=None, base_dev=None):
+    return None

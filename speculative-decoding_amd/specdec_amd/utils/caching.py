@@ -10,10 +10,15 @@ it calls ``DynamicCache.crop(-k)``, the transformers-5 way to drop the last k po
 Reference semantics kept on purpose: the tuple path slices ``[:, :, :-k, :]`` (:51), so k = 0
 returns EMPTY K/V views, exactly as the reference does (its loops never prune 0 positions:
 the prune only runs after a reject, k_drafter >= 1, k_target >= 2).
+
+``compact_cache`` is the tree loop's counterpart (sampling/tree_decoding.py; no reference code): a crop
+is not enough after a tree verify, the accepted nodes lie scattered among rejected siblings, so one
+sd_kv_compact launch moves them to the front of the tree's window in every layer before the length is
+set.
 """
 from __future__ import annotations
 
-from typing import Tuple, Union
+from typing import Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -95,3 +100,57 @@ def prune_static_cache(cache, num_tokens_to_discard: Union[int, Tensor]):
         torch._foreach_sub_(lens, int(num_tokens_to_discard))
     return cache
 
+
+
+def _kv_groups(tensors):
+    """The tensors grouped by (shape, strides, dtype): one sd_kv_compact call serves one layout (K and V
+    of a model whose head sizes differ form two groups)."""
+    groups = {}
+    for t in tensors:
+        groups.setdefault((tuple(t.shape), t.stride(), t.dtype), []).append(t)
+    return list(groups.values())
+
+
+def compact_cache(cache, path: Tensor, count: Tensor, base: int, *, num_slots: int, node_slot=None,
+                  new_length: Optional[int] = None):
+    """Compact a KV cache onto the accepted path of a token tree and set its length.
+
+    The cache holds the tree's nodes at positions ``base + slot(i)`` (``slot(i) = node_slot[i]``, or i).
+    ``path`` (int32 [B, depth]) and ``count`` (int32 [B]) are ``verify_tree``'s device outputs
+    (``path``, ``n_accepted``): in every K/V tensor of every layer, position ``base + slot(path[b, d])``
+    moves to ``base + d`` for d < count[b] — ONE kernel launch for the whole cache, nothing read back —
+    and the cache's length becomes ``new_length`` (normally base + count).
+
+    DynamicCache (transformers 5): ``layer.keys`` / ``layer.values`` compacted, then ``crop`` to
+    new_length (a host int, required).  StaticCache: compacted, then ``cumulative_length`` of every
+    layer set on the device in one multi-tensor call — ``new_length``, or ``base + count[0]`` computed
+    on the device when it is None.  A tuple cache: compacted, the sliced views returned.  Anything
+    else raises ValueError("Unsupported cache type.")."""
+    from ..ops import kv_compact
+    lens = _static_lengths(cache)
+    if lens is not None:
+        tensors = [t for layer in cache.layers for t in (layer.keys, layer.values)]
+    elif isinstance(cache, tuple):
+        tensors = [t for layer in cache if layer is not None for t in layer]
+    elif DynamicCache is not None and isinstance(cache, DynamicCache):
+        tensors = [t for layer in cache.layers for t in (layer.keys, layer.values)]
+    else:
+        raise ValueError("Unsupported cache type.")
+    if lens is None and new_length is None:
+        raise ValueError("compact_cache: new_length (a host int) is needed to crop this cache")
+    for group in _kv_groups(tensors):
+        kv_compact(group, path, count, base, num_slots=num_slots, node_slot=node_slot)
+    if lens is not None:
+        if new_length is None:
+            length = (count.reshape(-1)[0] + int(base)).to(lens[0].dtype)
+        else:
+            length = torch.full((), int(new_length), dtype=lens[0].dtype, device=lens[0].device)
+        torch._foreach_copy_(lens, [length] * len(lens))
+        return cache
+    new_length = int(new_length)
+    if isinstance(cache, tuple):
+        return tuple(None if layer is None else tuple(t[:, :, :new_length, :] for t in layer) for layer in cache)
+    drop = tensors[0].shape[2] - new_length
+    if drop > 0:
+        cache.crop(-drop)                       # the negative form: remove `drop` positions
+    return cache
