@@ -321,6 +321,7 @@ typedef enum {
     SD_PATH_VERIFY_MULTI = 6,       /* sd_verify_multi: k_stats, k_multi_mass x (K+1), k_multi_walk */
     SD_PATH_VERIFY_VP = 7,          /* sd_vp_finish: the vocabulary-parallel step's last phase    */
     SD_PATH_VERIFY_TREE = 8,        /* sd_verify_tree: k_stats, k_tree_mass x (C_max+1), k_tree_walk */
+    SD_PATH_VERIFY_TREE_DISTINCT = 9,   /* sd_verify_tree_distinct: k_stats, k_treed_rowsum, k_treed_walk */
     SD_PATH_SAMPLE_DRAW_LEAN = 16,  /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
@@ -850,6 +851,87 @@ typedef struct {
 /* 0 for a topology or shape sd_verify_tree does not take                                            */
 size_t sd_verify_tree_workspace_size(int32_t batch, int32_t num_nodes, const int32_t* parent, int32_t vocab);
 int32_t sd_verify_tree(const sd_tree_args* args, void* stream);
+
+/* ---- Token-tree verification, distinct children (csrc/sd_verify_tree_distinct.inc; additive, ABI 12) --
+ * sd_verify_tree asks that the children of a slot be iid draws of the slot's drafter row.  Here they
+ * are DISTINCT candidates that depend on the prefix alone, not on this call's noise: the drafter's
+ * top-c tokens, as Medusa and EAGLE draft them.  No drafter row is read.  Topology, slots, parent[],
+ * limits, noise keying (node c takes the row's accept uniform number c, the draw the row's cdf
+ * uniform, one call consumes one offset, SD_NOISE_PHILOX only) and the status conventions are
+ * sd_verify_tree's.  p_s is the SD_RULE_SPEC probability row of the target row of slot s
+ * (round_dt(softmax(round_dt(process(l) / T)))).  Per sequence:
+ *
+ *   s = 0; path = []
+ *   loop:
+ *       C = children of s, ascending node index
+ *       if C empty: x ~ p_s / Z_s, SD_ROW_BONUS, stop
+ *       Z_s = Σ_v p_s[v]      (fp32 sums of 2048-element chunks, added in fp64 in chunk order)
+ *       rem = Z_s; excluded = {}
+ *       for c in C:
+ *           x = tok[c]
+ *           w = p_s[x] if 0 <= x < V and x not in excluded else 0
+ *           if w > 0 and not (u_c > (float)w / (float)rem): path += [c]; s = c + 1; continue the outer loop
+ *           if w > 0: excluded += {x}; rem -= w                                              (fp64)
+ *       x ~ (p_s with the excluded tokens zeroed) / rem, SD_ROW_RESIDUAL, stop
+ *   n = len(path)
+ *
+ * A child without weight (an id outside [0, V), a repeat of an earlier sibling, a token the processor
+ * cut) is rejected without consulting its uniform.  resample_mass is (float)(rem / Z_s) at a residual
+ * exit, NaN otherwise; n_sibling_rejects counts the children rejected.  The stop scan, stop_index,
+ * SD_ROW_STOP_IN_DRAFTS (no token drawn), path, last_node, tokens_out and status_or are
+ * sd_verify_tree's.  Z_s or rem that is not finite or not positive at the slot drawn from:
+ * SD_ROW_INVALID_DIST, next_token = -1.
+ * Greedy (SD_PROC_GREEDY): a child with weight is accepted iff the processed logit of its token equals
+ * the row maximum (exact: the maximum is an element of the row); the exit token is the argmax of the
+ * processed logits, lowest index first.  Where every row maximum is unique the emitted tokens are the
+ * target's own greedy decode; a tie at the maximum may resolve toward a drafted child.
+ * Lossless: the children do not depend on the verify's noise; child j is accepted with probability
+ * w_j / rem_j, so token x_j is emitted with probability (Π_{i<j} (1 - w_i / rem_i)) w_j / rem_j =
+ * p[x_j] / Z and any other v with probability (rem_c / Z)(p[v] / rem_c) = p[v] / Z.  A slot accepts
+ * with total probability p(C) / Z, the most a set of distinct candidates can reach; sd_verify_tree's
+ * Σ min(p, q) per iid draw can be higher (p = q flat) or lower (greedy, peaked drafters): the two are
+ * complementary.
+ * Kernels: the row statistics of the N+1 target rows, ONE launch that sums every 2048-element chunk
+ * of every row, one launch that walks and samples.  Launch boundaries only: capturable.           */
+typedef struct {
+    int32_t batch;               /* B                                                              */
+    int32_t num_nodes;           /* N, 1..SD_TREE_MAX_NODES                                         */
+    int32_t vocab;
+    int32_t parent[SD_TREE_MAX_NODES];   /* host: parent[i] in {-1, 0..i-1}; entries from N on unread */
+    /* target row of slot s at target_rows[s] + b * target_stride_b                                 */
+    const void* target_rows[SD_TREE_MAX_NODES + 1];
+    int64_t target_stride_b;
+    int32_t dtype;               /* sd_dtype of every row                                           */
+    const int64_t* draft_tokens; /* [B, >=N] the nodes' drafted ids                                 */
+    int64_t draft_tokens_stride_b;
+    sd_processor proc;           /* the loop's logits_processor                                     */
+    const int64_t* stop_tokens;  /* device [n_stop]                                                */
+    int32_t n_stop;
+    int64_t pad_token;           /* fills tokens_out past the emitted tokens                        */
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+
+    /* outputs, device, [B]: as sd_tree_args'                                                       */
+    int32_t* n_accepted;
+    int32_t* last_node;
+    int64_t* next_token;
+    float* resample_mass;        /* (float)(rem / Z) at a residual exit, else NaN (nullable)        */
+    int32_t* n_sibling_rejects;  /* children rejected (nullable)                                    */
+    int32_t* stop_index;         /* nullable                                                       */
+    int32_t* row_status;
+    int32_t* path;               /* int32 [B, >=depth] at path + b * path_stride_b                  */
+    int64_t path_stride_b;
+    int64_t* tokens_out;         /* nullable: int64 [B, >=depth+1]                                  */
+    int64_t tokens_out_stride_b;
+
+    void* workspace;             /* sd_verify_tree_distinct_workspace_size bytes, zero-filled once;
+                                    shares the other entry points' convention                       */
+    size_t workspace_bytes;
+    int32_t* status_or;          /* nullable                                                       */
+} sd_tree_distinct_args;
+
+/* 0 for a topology or shape sd_verify_tree_distinct does not take                                   */
+size_t sd_verify_tree_distinct_workspace_size(int32_t batch, int32_t num_nodes, const int32_t* parent, int32_t vocab);
+int32_t sd_verify_tree_distinct(const sd_tree_distinct_args* args, void* stream);
 
 /* ---- KV-cache compaction onto an accepted tree path (csrc/kv_compact.hip; additive, ABI 12) ---------
  * After a tree-masked forward the cache holds the N tree nodes behind the committed tokens, node i at

@@ -20,10 +20,11 @@ from . import _lib  # noqa: F401  (loads libspecdec.so or raises)
 from ._lib import RowError, get_poll_policy, set_poll_policy  # noqa: F401
 from .noise import PhiloxNoise, StreamNoise, default_noise, set_noise_mode  # noqa: F401
 from .ops import ProcSpec, kv_compact, proc_spec, probs_rows, sample_rows, verify, verify_multi, verify_tree  # noqa: F401
+from .ops import topk_children, verify_tree_distinct  # noqa: F401
 from .tree import TokenTree  # noqa: F401
 from .vocab_parallel import GroupExchange, LocalShards, VocabShard, verify_vocab_parallel  # noqa: F401
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.specdec.sample / .verify)
 
 __all__ = ["RowError", "get_poll_policy", "set_poll_policy", "PhiloxNoise", "StreamNoise", "default_noise", "set_noise_mode", "ProcSpec", "proc_spec",
-           "probs_rows", "sample_rows", "verify", "verify_multi", "verify_tree", "kv_compact", "TokenTree", "GroupExchange", "LocalShards", "VocabShard",
+           "probs_rows", "sample_rows", "verify", "verify_multi", "verify_tree", "verify_tree_distinct", "topk_children", "kv_compact", "TokenTree", "GroupExchange", "LocalShards", "VocabShard",
            "verify_vocab_parallel"]

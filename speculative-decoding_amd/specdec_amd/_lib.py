@@ -41,6 +41,7 @@ SD_PATH_VERIFY_FUSED_TICKET = 5
 SD_PATH_VERIFY_MULTI = 6
 SD_PATH_VERIFY_VP = 7
 SD_PATH_VERIFY_TREE = 8
+SD_PATH_VERIFY_TREE_DISTINCT = 9
 SD_PATH_SAMPLE_DRAW_LEAN, SD_PATH_SAMPLE_DRAW, SD_PATH_SAMPLE_NUCLEUS, SD_PATH_SAMPLE_STREAM = 16, 17, 18, 19
 SD_PATH_SAMPLE_GREEDY_LEAN, SD_PATH_SAMPLE_MULTI = 20, 21
 PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PATH_VERIFY_FUSED: "k_verify_fused",
@@ -49,6 +50,7 @@ PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PAT
               SD_PATH_VERIFY_MULTI: "k_stats+k_multi_mass+k_multi_walk",
               SD_PATH_VERIFY_VP: "k_vp_stats+k_vp_decide+k_vp_finish",
               SD_PATH_VERIFY_TREE: "k_stats+k_tree_mass+k_tree_walk",
+              SD_PATH_VERIFY_TREE_DISTINCT: "k_stats+k_treed_rowsum+k_treed_walk",
               SD_PATH_SAMPLE_DRAW_LEAN: "k_draw_lean", SD_PATH_SAMPLE_DRAW: "k_draw", SD_PATH_SAMPLE_NUCLEUS: "k_draw_nuc",
               SD_PATH_SAMPLE_STREAM: "k_draw_stream", SD_PATH_SAMPLE_GREEDY_LEAN: "k_draw_lean<greedy>",
               SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize"}
@@ -70,6 +72,7 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_vp_stats_bytes", "sd_vp_cand_bytes", "sd_vp_workspace_size", "sd_vp_stats", "sd_vp_decide",
            "sd_vp_finish",
            "sd_verify_tree_workspace_size", "sd_verify_tree",
+           "sd_verify_tree_distinct_workspace_size", "sd_verify_tree_distinct",
            "sd_kv_compact")
 
 # vocabulary-parallel verify
@@ -244,6 +247,25 @@ class sd_tree_args(C.Structure):
     ]
 
 
+class sd_tree_distinct_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("num_nodes", C.c_int32), ("vocab", C.c_int32),
+        ("parent", C.c_int32 * SD_TREE_MAX_NODES),
+        ("target_rows", C.c_void_p * (SD_TREE_MAX_NODES + 1)), ("target_stride_b", C.c_int64),
+        ("dtype", C.c_int32),
+        ("draft_tokens", C.c_void_p), ("draft_tokens_stride_b", C.c_int64),
+        ("proc", sd_processor), ("stop_tokens", C.c_void_p), ("n_stop", C.c_int32), ("pad_token", C.c_int64),
+        ("noise", sd_noise),
+        ("n_accepted", C.c_void_p), ("last_node", C.c_void_p), ("next_token", C.c_void_p),
+        ("resample_mass", C.c_void_p), ("n_sibling_rejects", C.c_void_p), ("stop_index", C.c_void_p),
+        ("row_status", C.c_void_p),
+        ("path", C.c_void_p), ("path_stride_b", C.c_int64),
+        ("tokens_out", C.c_void_p), ("tokens_out_stride_b", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("status_or", C.c_void_p),
+    ]
+
+
 class sd_kv_compact_args(C.Structure):
     _fields_ = [
         ("n_tensors", C.c_int32), ("batch", C.c_int32), ("heads", C.c_int32), ("max_depth", C.c_int32),
@@ -337,6 +359,10 @@ def _load():
     lib.sd_verify_tree_workspace_size.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
     lib.sd_verify_tree.restype = C.c_int32
     lib.sd_verify_tree.argtypes = [C.POINTER(sd_tree_args), C.c_void_p]
+    lib.sd_verify_tree_distinct_workspace_size.restype = C.c_size_t
+    lib.sd_verify_tree_distinct_workspace_size.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    lib.sd_verify_tree_distinct.restype = C.c_int32
+    lib.sd_verify_tree_distinct.argtypes = [C.POINTER(sd_tree_distinct_args), C.c_void_p]
     lib.sd_kv_compact.restype = C.c_int32
     lib.sd_kv_compact.argtypes = [C.POINTER(sd_kv_compact_args), C.c_void_p]
     lib.sd_vp_stats_bytes.restype = C.c_size_t

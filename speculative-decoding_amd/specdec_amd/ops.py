@@ -724,6 +724,83 @@ def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
     return out
 
 
+def verify_tree_distinct(target, draft_tokens: torch.Tensor, parent, proc, noise,
+                         stop_tokens: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None,
+                         pad_token_id: int = 0, row_base: int = 0):
+    """One token-tree verify step for DISTINCT children (sd_verify_tree_distinct): the children of a
+    slot are distinct candidates fixed by the prefix (the drafter's top-c tokens, ``topk_children``),
+    not iid draws, so no drafter row is read: child j of a slot is accepted with probability
+    p[x_j] / (Z - the weights of the siblings rejected before it), and the emitted tokens keep the
+    target's distribution exactly.  Under greedy a child is accepted iff its token is
+    the row's maximum: the output is the target's greedy decode.
+
+    target: [B, N+1, V] logits (or N+1 tensors [B, V]): slot 0 the root's row, slot i+1 the row after
+    node i.  draft_tokens: int64 [B, >=N].  parent, proc, noise, stop_tokens, status_or, pad_token_id and
+    the returned namespace are ``verify_tree``'s (resample_mass: the share of the row's mass left at a
+    residual exit; n_sibling_rejects: the children rejected)."""
+    from types import SimpleNamespace
+    if _user_process(proc) is not None:
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: verify_tree_distinct fuses the "
+                        "processing of the target rows and cannot run a user _process")
+    spec = proc_spec(proc)
+    if not isinstance(noise, PhiloxNoise):
+        raise TypeError("verify_tree_distinct needs PhiloxNoise (the rule defines no stream order for this step)")
+    tree = _tree_of(parent)
+    N, depth = tree.num_nodes, tree.depth
+    t_ptrs, t_stride, B, V, tdt, dev = _slot_rows(target, "target", list(range(N + 1)), N + 1, None)
+    if not 1 <= B <= _lib.SD_TREE_MAX_BATCH:
+        raise ValueError(f"verify_tree_distinct: batch must be in 1..{_lib.SD_TREE_MAX_BATCH}, got {B}")
+    if draft_tokens.dtype != torch.long or draft_tokens.dim() != 2 or draft_tokens.shape[0] != B \
+            or draft_tokens.shape[1] < N or draft_tokens.stride(1) != 1 or draft_tokens.device != dev:
+        raise ValueError(f"draft_tokens must be int64 [B, >={N}] on {dev}")
+    stops = stop_tokens if stop_tokens is not None else torch.empty(0, dtype=torch.long, device=dev)
+    if stops.dtype != torch.long or stops.device != dev or not stops.is_contiguous():
+        raise ValueError("stop_tokens must be a contiguous int64 device tensor")
+    # one allocation: next_token (int64) first, then the six 4-byte fields and the path
+    buf = torch.empty(8 * B + 4 * (6 + depth) * B, dtype=torch.uint8, device=dev)
+    nxt = buf[:8 * B].view(torch.long)
+    f4 = buf[8 * B:].view(torch.int32)
+    i32 = [f4[k * B:(k + 1) * B] for k in range(6)]
+    out = SimpleNamespace(n_accepted=i32[0], last_node=i32[1], next_token=nxt, resample_mass=i32[2].view(torch.float32),
+                          n_sibling_rejects=i32[3], stop_index=i32[4], row_status=i32[5],
+                          path=f4[6 * B:].view(B, depth),
+                          tokens_out=torch.empty(B, depth + 1, dtype=torch.long, device=dev))
+    nz, keep = _noise_struct(noise, 0, dev, row_base)
+    par = getattr(tree, "_c_parent", None)
+    if par is None:
+        par = tree._c_parent = (C.c_int32 * _lib.SD_TREE_MAX_NODES)(*tree.parent)
+    ws = _workspace(lib.sd_verify_tree_distinct_workspace_size(B, N, par, V), dev)
+    a = _lib.sd_tree_distinct_args()
+    a.batch, a.num_nodes, a.vocab = B, N, V
+    a.parent = par
+    a.target_rows = _ROW_PTRS(*t_ptrs)
+    a.target_stride_b = t_stride
+    a.dtype = _DT[tdt]
+    a.draft_tokens = draft_tokens.data_ptr()
+    a.draft_tokens_stride_b = draft_tokens.stride(0) if B > 1 else draft_tokens.shape[1]
+    a.proc = spec.struct()
+    a.stop_tokens, a.n_stop = (stops.data_ptr() if stops.numel() else None), stops.numel()
+    a.pad_token = int(pad_token_id)
+    a.noise = nz
+    for f in TREE_FIELDS:
+        setattr(a, f, getattr(out, f).data_ptr())
+    a.path, a.path_stride_b = out.path.data_ptr(), depth
+    a.tokens_out, a.tokens_out_stride_b = out.tokens_out.data_ptr(), depth + 1
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_verify_tree_distinct(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_verify_tree_distinct")
+    del keep
+    return out
+
+
+def topk_children(logits_rows: torch.Tensor, k: int) -> torch.Tensor:
+    """The k best token ids of every row of logits [R, V], int64 [R, k]: value descending, lowest index
+    first among equals (one ``beam_topk`` pass).  These are the children ``verify_tree_distinct`` takes:
+    the top-k of the raw logits is the top-k under any temperature and softmax, so no processor is
+    applied.  R <= 64, k <= 64."""
+    return beam_topk(logits_rows, int(k))[1]
+
+
 # --------------------------------------------------------------------------- KV-cache compaction
 def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, num_slots: int, node_slot=None,
                base_dev: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None) -> None:

@@ -23,7 +23,7 @@ from torch.nn import Module
 
 from .. import _lib
 from ..noise import PhiloxNoise
-from ..ops import _user_process, proc_spec, sample_rows, verify_tree
+from ..ops import _user_process, proc_spec, sample_rows, topk_children, verify_tree, verify_tree_distinct
 from ..tree import TokenTree
 from ..utils.caching import DynamicCache, _static_lengths, compact_cache
 from ..utils.logits_processor import GreedyProcessor, LogitsProcessor
@@ -96,7 +96,22 @@ class _CachedModel:
         self.len = new_length
 
 
-def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, input_ids, spec, noise, err, pad_token_id):
+def _topk_level(logits: torch.Tensor, row_of, tr: TokenTree, level) -> torch.Tensor:
+    """The tokens of a level's nodes under ``children="topk"``: ONE ``topk_children`` call over the rows
+    of the level's distinct parent slots (row_of: slot -> row of `logits`), k the level's largest child
+    count; child j of a slot, in ascending node index, gets the slot's (j+1)-th best token."""
+    slots = sorted({tr.parent[c] + 1 for c in level})
+    dev, V = logits.device, logits.shape[-1]
+    k = min(max(len(tr.children[s]) for s in slots), V)
+    at = torch.tensor([row_of[s] for s in slots], dtype=torch.long, device=dev)
+    best = topk_children(logits.index_select(0, at), k)
+    r = [slots.index(tr.parent[c] + 1) for c in level]
+    j = [min(tr.children[tr.parent[c] + 1].index(c), k - 1) for c in level]    # k < child count only where V is
+    return best[torch.tensor(r, dtype=torch.long, device=dev), torch.tensor(j, dtype=torch.long, device=dev)]
+
+
+def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, input_ids, spec, noise, err, pad_token_id,
+                 children: str = "sample"):
     """One step's drafting and target forward on the caches: the uncached loop's draws (one sample_rows call
     per level, the parent's row once per child) on rows of forwards over the new tokens only.  Returns
     (target rows [1, N + 1, V], drafter rows by slot, drafts [1, N], slot), slot[i] the order in which node i
@@ -118,11 +133,14 @@ def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, in
             row_of = {i + 1: r for r, i in enumerate(prev)}
         for s in sorted({tr.parent[c] + 1 for c in level}):
             draft_rows[s] = logits[row_of[s]:row_of[s] + 1, :]
-        at = torch.tensor([row_of[tr.parent[c] + 1] for c in level], dtype=torch.long, device=dev)
-        rows = logits.index_select(0, at)
-        toks = torch.empty(len(level), dtype=torch.long, device=dev)
-        sample_rows(rows, spec, noise, tokens_out=toks, status_or=err)
-        toks.clamp_(0, rows.shape[-1] - 1)                 # a failed row's -1 never reaches a forward
+        if children == "topk":
+            toks = _topk_level(logits, row_of, tr, level)
+        else:
+            at = torch.tensor([row_of[tr.parent[c] + 1] for c in level], dtype=torch.long, device=dev)
+            rows = logits.index_select(0, at)
+            toks = torch.empty(len(level), dtype=torch.long, device=dev)
+            sample_rows(rows, spec, noise, tokens_out=toks, status_or=err)
+            toks.clamp_(0, rows.shape[-1] - 1)             # a failed row's -1 never reaches a forward
         drafts[0, torch.tensor(level, dtype=torch.long, device=dev)] = toks
     m = cur - tm.len                                       # committed tokens the target's cache lacks (the root is last)
     allow, pos = _allowed(tr, cur, tm.len, list(range(N)), list(range(N)))
@@ -147,6 +165,7 @@ def tree_speculative_generate(
     static_cache: bool = False,
     tree: Optional[TokenTree] = None,
     trace: Optional[list] = None,
+    children: str = "sample",
 ) -> Tuple[List[int], float]:
     """``speculative_generate`` with a token tree per step; returns (tokens, accepted / speculated
     drafts with the tree's depth speculated per step, so the rate compares with
@@ -163,7 +182,16 @@ def tree_speculative_generate(
     ``use_cache``.  A processor that overrides ``_process``, ``sample`` or ``__call__`` raises
     TypeError.  trace: a list that receives per step ``dict(cur, offset, parent, draft_tokens [N], n,
     path, x, sibling_rejects)``, and under ``use_cache`` the cache lengths at the step's start,
-    ``cache_len_target`` and ``cache_len_drafter``."""
+    ``cache_len_target`` and ``cache_len_drafter``.
+
+    children: "sample" (the default) draws the children of a slot as iid samples of the slot's drafter
+    row and verifies with ``sd_verify_tree``.  "topk" gives child j of a slot the slot's (j+1)-th best
+    drafter token (one ``topk_children`` call per level) and verifies with ``sd_verify_tree_distinct``
+    (DESIGN.md §4f): distinct candidates, no drafter rows in the verify, and under greedy exactly the
+    target's greedy decode.  Pick "topk" for greedy and for peaked drafters, "sample" for flat ones."""
+    if children not in ("sample", "topk"):
+        raise ValueError(f"children must be 'sample' or 'topk', got {children!r}")
+    topk = children == "topk"
     spec = proc_spec(logits_processor)             # TypeError for __call__ / sample overrides
     if _user_process(logits_processor) is not None:
         raise TypeError(f"unsupported logits processor {type(logits_processor).__name__}: the tree verify "
@@ -233,7 +261,8 @@ def tree_speculative_generate(
         N = tr.num_nodes
         if use_cache:
             t_len, d_len = tm.len, dm.len
-            target_rows, draft_rows, drafts, slot = _cached_rows(tm, dm, tr, cur, input_ids, spec, noise, err, pad_token_id)
+            target_rows, draft_rows, drafts, slot = _cached_rows(tm, dm, tr, cur, input_ids, spec, noise, err, pad_token_id,
+                                                                 children)
         else:
             seq = torch.cat([input_ids[:, :cur], torch.full((1, N), pad_token_id, dtype=torch.long, device=dev)], 1)
             draft_rows = [None] * (N + 1)
@@ -243,12 +272,15 @@ def tree_speculative_generate(
                 slots = sorted({tr.parent[c] + 1 for c in level})
                 for s in slots:
                     draft_rows[s] = logits[cur - 1 + s:cur + s, :]
-                # the parent's row once per child: every child is an independent draw (its own noise row)
-                at = torch.tensor([cur - 1 + tr.parent[c] + 1 for c in level], dtype=torch.long, device=dev)
-                rows = logits.index_select(0, at)
-                toks = torch.empty(len(level), dtype=torch.long, device=dev)
-                sample_rows(rows, spec, noise, tokens_out=toks, status_or=err)
-                toks.clamp_(0, rows.shape[-1] - 1)     # a failed row's -1 never reaches a forward
+                if topk:
+                    toks = _topk_level(logits, {s: cur - 1 + s for s in slots}, tr, level)
+                else:
+                    # the parent's row once per child: every child is an independent draw (its own noise row)
+                    at = torch.tensor([cur - 1 + tr.parent[c] + 1 for c in level], dtype=torch.long, device=dev)
+                    rows = logits.index_select(0, at)
+                    toks = torch.empty(len(level), dtype=torch.long, device=dev)
+                    sample_rows(rows, spec, noise, tokens_out=toks, status_or=err)
+                    toks.clamp_(0, rows.shape[-1] - 1) # a failed row's -1 never reaches a forward
                 seq[0, cur + torch.tensor(level, dtype=torch.long, device=dev)] = toks
                 placed = max(placed, max(level) + 1)
             tlogits = _tree_forward(target, seq, tr, cur, N, t_dtype)
@@ -256,8 +288,12 @@ def tree_speculative_generate(
             target_rows = tlogits[cur - 1:cur + N][None]
         speculated += depth
         offset = noise.offset
-        out = verify_tree(target_rows, draft_rows, drafts, tr, spec, noise, stop_tokens=stop_t,
-                          status_or=err, pad_token_id=pad_token_id)
+        if topk:
+            out = verify_tree_distinct(target_rows, drafts, tr, spec, noise, stop_tokens=stop_t, status_or=err,
+                                       pad_token_id=pad_token_id)
+        else:
+            out = verify_tree(target_rows, draft_rows, drafts, tr, spec, noise, stop_tokens=stop_t,
+                              status_or=err, pad_token_id=pad_token_id)
         input_ids[0, cur:cur + depth + 1] = out.tokens_out[0]          # the path's tokens, x, pad
         n, x, status, stop_index, rejects, bits = (int(v) for v in torch.stack([
             out.n_accepted[0].long(), out.next_token[0], out.row_status[0].long(), out.stop_index[0].long(),

@@ -26,6 +26,12 @@ GPU), and callable as ``torch.ops.specdec.*``.
         One token-tree verify step (sd_verify_tree): N nodes with parents `parent`, the I internal slots'
         drafter rows in ascending slot order, Philox noise.
 
+    torch.ops.specdec.verify_tree_distinct(target [B, N+1, V], draft_tokens int64 [B, >=N], parent int[N],
+                                           stop_tokens int64 [n], kind, temperature, top_k, top_p, seed, offset,
+                                           row_base) -> the same outputs as verify_tree
+        One token-tree verify step whose children are distinct candidates, e.g. the drafter's top-c tokens
+        (sd_verify_tree_distinct): no drafter rows, Philox noise.
+
     torch.ops.specdec.beam_topk(logits [R, V], k) -> (logprob fp32 [R, k], token int64 [R, k])
         The beam step's row pass: topk(log_softmax(logits), k), lowest index first among equal values
         (sampling/base_decoding.py:136-137).
@@ -142,6 +148,27 @@ def verify_tree(target: Tensor, draft: Tensor, draft_tokens: Tensor, parent: Lis
 
 @verify_tree.register_fake
 def _(target, draft, draft_tokens, parent, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
+    from .tree import TokenTree
+    B = target.shape[0]
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.TREE_FIELDS) + (
+        target.new_empty(B, TokenTree(list(parent)).depth, dtype=torch.int32),)
+
+
+@torch.library.custom_op("specdec::verify_tree_distinct", mutates_args=())
+def verify_tree_distinct(target: Tensor, draft_tokens: Tensor, parent: List[int], stop_tokens: Tensor, kind: int,
+                         temperature: float, top_k: int, top_p: float, seed: int, offset: int,
+                         row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """One token-tree verify step for distinct children (ops.verify_tree_distinct): target [B, N+1, V],
+    draft_tokens int64 [B, >=N]; the seven [B] outputs in ops.TREE_FIELDS' order, then path."""
+    out = ops.verify_tree_distinct(target, draft_tokens, list(parent), _spec(kind, temperature, top_k, top_p),
+                                   PhiloxNoise(seed, offset), stop_tokens=stop_tokens, row_base=row_base)
+    # views of one buffer: outputs may not alias
+    return tuple(getattr(out, f).clone() for f in ops.TREE_FIELDS) + (out.path.clone(),)
+
+
+@verify_tree_distinct.register_fake
+def _(target, draft_tokens, parent, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
     from .tree import TokenTree
     B = target.shape[0]
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
