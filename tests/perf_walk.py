@@ -30,12 +30,13 @@ def flip_slack(logits_row, dtype):
 
 
 # ---------------------------------------------------------------- accept walk
-def host_walk_spec(p, q, seed, off, b, g):
+def host_walk_spec(p, q, seed, off, b, g, uniform=ph.accept_uniform):
     """sampling/speculative_decoding.py:139-145 on Philox uniforms: n, and whether any comparison
-    sat within fp32 rounding of the threshold (then the device may legitimately differ)."""
+    sat within fp32 rounding of the threshold (then the device may legitimately differ).
+    uniform(seed, off, b, i): draft i's accept uniform (tests/window_walk.py passes a window's)."""
     n, close = g, False
     for i in range(g):
-        r = ph.accept_uniform(seed, off, b, i)
+        r = uniform(seed, off, b, i)
         frac = np.float32(p[i]) / np.float32(q[i]) if q[i] != 0 else np.float32(np.inf if p[i] > 0 else np.nan)
         close |= bool(abs(float(r) - float(frac)) <= 1e-6 * max(1.0, float(frac)))
         if r > frac and n == g:
@@ -43,11 +44,11 @@ def host_walk_spec(p, q, seed, off, b, g):
     return n, close
 
 
-def host_walk_engine(p, q, toks, ends, seed, off, b, g):
+def host_walk_engine(p, q, toks, ends, seed, off, b, g, uniform=ph.accept_uniform):
     """engine/infer_engine.py:297-330 on Philox uniforms: (n, rejected, finished, close)."""
     n, close = 0, False
     for i in range(g):
-        u = float(ph.accept_uniform(seed, off, b, i))
+        u = float(uniform(seed, off, b, i))
         ap = 1.0 if q[i] <= 0 else min(1.0, float(p[i]) / float(q[i]))
         close |= abs(u - ap) <= 1e-6
         if u < ap:
@@ -60,10 +61,10 @@ def host_walk_engine(p, q, toks, ends, seed, off, b, g):
 
 
 # ---------------------------------------------------------------- constructed inputs
-def pivots(gamma):
+def pivots(gamma, extra=()):
     """The draft indices edge_walk_case steers walks to: the first and last draft of a Philox block
-    of four uniforms (0, 3 | 4, 7 | 8), and the last draft."""
-    return sorted({0, 3, 4, 7, 8, gamma - 1} & set(range(gamma)))
+    of four uniforms (0, 3 | 4, 7 | 8), and the last draft; `extra` adds indices (those below gamma)."""
+    return sorted(({0, 3, 4, 7, 8, gamma - 1} | set(extra)) & set(range(gamma)))
 
 
 def _oracle_probs(tl, dl, gamma):
@@ -72,11 +73,12 @@ def _oracle_probs(tl, dl, gamma):
 
 
 @functools.lru_cache(maxsize=None)
-def _edge(B, gamma, V, dtype, seed):
+def _edge(B, gamma, V, dtype, seed, piv=None):
+    """piv: the pivot cycle (a tuple, taken in its own order); None: pivots(gamma)."""
     g = torch.Generator().manual_seed(seed)
     tl = (torch.randn(B, gamma + 1, V, generator=g) * 3).to(dtype)
     bump = torch.randn(B, gamma, V, generator=g) * 0.5
-    piv = pivots(gamma)
+    piv = pivots(gamma) if piv is None else list(piv)
     k = [piv[b % len(piv)] for b in range(B)]
     dl = tl[:, :gamma].clone()
     for b in range(B):
@@ -123,9 +125,12 @@ def long_walk_case(B, gamma, V, dtype, seed):
     return c.tl, c.dl, c.ids
 
 
-def walk_case(kind, B, gamma, V, dtype, seed):
-    """The cached case with its oracle probabilities: .tl .dl .ids .k .P .Q (kind: "edge" | "long")."""
-    return (_edge if kind == "edge" else _long)(B, gamma, V, dtype, seed)
+def walk_case(kind, B, gamma, V, dtype, seed, piv=None):
+    """The cached case with its oracle probabilities: .tl .dl .ids .k .P .Q (kind: "edge" | "long").
+    piv: an edge case's own pivot cycle (a tuple; tests/window_walk.py), None: pivots(gamma)."""
+    if kind == "edge":
+        return _edge(B, gamma, V, dtype, seed) if piv is None else _edge(B, gamma, V, dtype, seed, tuple(piv))
+    return _long(B, gamma, V, dtype, seed)
 
 
 # ---------------------------------------------------------------- chunk pick

@@ -44,3 +44,13 @@ def accept_uniform(seed: int, offset: int, row: int, i: int) -> float:
 def cdf_uniform(seed: int, offset: int, row: int) -> float:
     x, y, _, _ = block(seed, offset, row, SITE_CDF, 0)
     return float(((int(x) << 32) | int(y)) >> 11) * 2.0 ** -53
+
+
+def exp1_words(seed: int, offset: int, row: int, site: int, n: int):
+    """The perf-mode Exp(1) values of elements 0..n-1 drawn at `site` (exp1_from_word): element j reads
+    word j & 3 of block j >> 2, u = (w >> 8)·2^-24 + 2^-25 in fp32 arithmetic and E = -ln u (here in
+    fp64 from the fp32 u; the device takes the fp32 logarithm).  Returns (E, u) as fp64 / fp32 [n]."""
+    words = np.stack(block(seed, offset, row, site, np.arange((n + 3) // 4, dtype=np.uint64)), axis=1).reshape(-1)[:n]
+    u = (words >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24) + np.float32(2.0 ** -25)
+    with np.errstate(divide="ignore"):
+        return -np.log(u.astype(np.float64)), u
