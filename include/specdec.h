@@ -322,7 +322,8 @@ typedef enum {
     SD_PATH_VERIFY_VP = 7,          /* sd_vp_finish: the vocabulary-parallel step's last phase    */
     SD_PATH_VERIFY_TREE = 8,        /* sd_verify_tree: k_stats, k_tree_mass x (C_max+1), k_tree_walk */
     SD_PATH_VERIFY_TREE_DISTINCT = 9,   /* sd_verify_tree_distinct: k_stats, k_treed_rowsum, k_treed_walk */
-    SD_PATH_SAMPLE_DRAW_LEAN = 16,  /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
+    SD_PATH_VERIFY_TREE_DYNAMIC = 10,   /* sd_verify_tree_dynamic: the distinct kernels, device parents      */
+    SD_PATH_SAMPLE_DRAW_LEAN = 16, /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
     SD_PATH_SAMPLE_STREAM = 19,     /* k_draw_stream (STREAM one pass)                             */
@@ -980,6 +981,140 @@ typedef struct {
 } sd_kv_compact_args;
 
 int32_t sd_kv_compact(const sd_kv_compact_args* args, void* stream);
+
+/* ---- Dynamic draft trees: growth on the device (csrc/tree_grow.hip; additive, ABI 12) -----------------
+ * EAGLE-2 style context-dependent trees without a host read of the drafter's scores.  The host knows
+ * only the SHAPE: levels L (1..SD_MAX_GAMMA), width W (1..SD_TREE_GROW_MAX_WIDTH frontier nodes expanded
+ * per level), branch c (1..SD_TREE_MAX_CHILDREN, c <= V) and the number of nodes N sent to the target.
+ * Frontier sizes are static: F_0 = 1 (the root), F_l = min(W, F_{l-1} * c).  Level l (1-based) adds
+ * F_{l-1} * c candidates to the sequence's POOL at indices base_l + r * c + j, base_1 = 0,
+ * base_{l+1} = base_l + F_{l-1} * c, r the parent's rank in the previous frontier, j the child's rank.
+ * The pool (caller-owned device arrays, <= SD_TREE_POOL_MAX entries per sequence) holds a token, a
+ * score (the cumulative drafter log-probability, fp32) and the parent's pool index (-1: the root).
+ *
+ * sd_tree_grow, one level.  For every frontier row r (the drafter's logit row after frontier node r):
+ *   children   the c best tokens by RAW logit, value descending, lowest index first (exact compares)
+ *   lp         (x - m) - log(sum exp(x - m)) in fp32, m the row's true maximum, NOT rounded to the
+ *              row dtype, clamped to <= 0
+ *   score      score(parent) + lp (one fp32 add); the root's score is 0
+ * The next frontier is the F_l best candidates OF THIS LEVEL by (score descending, pool index
+ * ascending), emitted in ASCENDING POOL INDEX: only membership depends on score arithmetic.  -inf logits
+ * give -inf scores: ordinary entries that sort last.  A NaN (or +inf) in a row, a row without a finite
+ * element, or an incoming frontier index outside the pool written so far sets SD_ROW_INVALID_DIST for
+ * the sequence (row_status, status_or); its outputs are unusable but stay inside its buffers (a NaN
+ * score ranks as -inf).  Two launches (every 2048-element chunk of every row read once, then one
+ * workgroup per sequence), launch boundaries only: capturable.
+ *
+ * sd_tree_select, the rerank: the N best pool entries by (score descending, pool index ascending),
+ * emitted in ascending pool index.  A child never scores above its parent (lp <= 0) and always has a
+ * higher pool index, so the set is closed under parents and parent[i] < i: what sd_verify_tree_dynamic
+ * takes.  One launch, one workgroup per sequence.  A selected entry whose parent is not selected (only
+ * possible for a pool not written by sd_tree_grow) sets SD_ROW_INVALID_DIST.                          */
+#define SD_TREE_POOL_MAX 2048
+#define SD_TREE_GROW_MAX_WIDTH 8
+#define SD_TREE_GROW_MAX_VOCAB 524288
+
+typedef struct {
+    int32_t batch;               /* B, 1..SD_TREE_MAX_BATCH                                         */
+    int32_t vocab;               /* V, 1..SD_TREE_GROW_MAX_VOCAB                                     */
+    int32_t level;               /* l, 1..SD_MAX_GAMMA: the level this call adds                     */
+    int32_t width;               /* W                                                              */
+    int32_t branch;              /* c                                                              */
+    int32_t dtype;               /* sd_dtype of the rows                                            */
+    /* frontier row r of sequence b at logits + (b * stride_b + r * stride_r) elements, r < F_{l-1}   */
+    const void* logits;
+    int64_t stride_b;
+    int64_t stride_r;
+    /* device int32 [B, >=F_{l-1}]: the previous call's frontier_pool (ignored and nullable at l = 1) */
+    const int32_t* frontier_in;
+    int64_t frontier_in_stride_b;
+    /* the pool, device, [B, >=base_l + F_{l-1} * c] at stride pool_stride_b                          */
+    int64_t* pool_token;
+    float* pool_score;
+    int32_t* pool_parent;
+    int64_t pool_stride_b;
+    /* outputs, device, [B, >=F_l] at stride frontier_stride_b                                        */
+    int64_t* frontier_token;
+    int32_t* frontier_pool;
+    int32_t* frontier_parent_rank;   /* rank of the parent in the previous frontier                  */
+    int64_t frontier_stride_b;
+    int32_t* row_status;         /* nullable, [B]: SD_ROW_DONE, SD_ROW_INVALID_DIST                  */
+    int32_t* status_or;          /* nullable                                                       */
+    void* workspace;             /* sd_tree_grow_workspace_size bytes; the common convention        */
+    size_t workspace_bytes;
+} sd_tree_grow_args;
+
+typedef struct {
+    int32_t batch;               /* B                                                              */
+    int32_t pool_size;           /* entries per sequence, 1..SD_TREE_POOL_MAX                        */
+    int32_t num_nodes;           /* N, 1..min(SD_TREE_MAX_NODES, pool_size)                           */
+    int32_t reserved;
+    const int64_t* pool_token;
+    const float* pool_score;
+    const int32_t* pool_parent;
+    int64_t pool_stride_b;
+    /* outputs, device, [B, >=N] at stride out_stride_b                                              */
+    int64_t* tokens;
+    int32_t* parent;             /* final indices, -1 a child of the root                            */
+    int32_t* depth;              /* 1-based                                                        */
+    int32_t* pool_index;
+    uint64_t* anc;               /* bit k: node k is node i or an ancestor of it                     */
+    int64_t out_stride_b;
+    int32_t* row_status;         /* nullable, [B]                                                  */
+    int32_t* status_or;          /* nullable                                                       */
+    void* workspace;             /* sd_tree_select_workspace_size bytes; the common convention      */
+    size_t workspace_bytes;
+} sd_tree_select_args;
+
+/* 0 for a shape the call does not take                                                             */
+size_t sd_tree_grow_workspace_size(int32_t batch, int32_t vocab, int32_t level, int32_t width, int32_t branch);
+int32_t sd_tree_grow(const sd_tree_grow_args* args, void* stream);
+size_t sd_tree_select_workspace_size(int32_t batch, int32_t pool_size, int32_t num_nodes);
+int32_t sd_tree_select(const sd_tree_select_args* args, void* stream);
+
+/* ---- Token-tree verification, distinct children, one topology PER SEQUENCE
+ * (csrc/sd_verify_tree_dynamic.inc; additive, ABI 12).  sd_verify_tree_distinct with the parents on the
+ * device: sequence b's are parent_dev[b * parent_stride_b + i], as sd_tree_select writes them.  The
+ * rule, the noise keying, the outputs and the status conventions are sd_verify_tree_distinct's; path
+ * is [B, max_depth] and tokens_out [B, max_depth + 1].  The topology is validated on the device:
+ * parent[i] in [-1, i-1], at most SD_TREE_MAX_CHILDREN children per slot, depth <= max_depth.  A
+ * sequence that fails gets SD_ROW_INVALID_DIST (ORed into status_or), n_accepted = 0, last_node = -1,
+ * next_token = -1, path all -1, tokens_out all pad_token; nothing out of range is read or written.    */
+typedef struct {
+    int32_t batch;               /* B                                                              */
+    int32_t num_nodes;           /* N, 1..SD_TREE_MAX_NODES                                         */
+    int32_t vocab;
+    int32_t max_depth;           /* 1..SD_MAX_GAMMA                                                 */
+    const int32_t* parent_dev;   /* device int32 [B, >=N]                                           */
+    int64_t parent_stride_b;
+    const void* target_rows[SD_TREE_MAX_NODES + 1];
+    int64_t target_stride_b;
+    int32_t dtype;
+    const int64_t* draft_tokens; /* [B, >=N]                                                       */
+    int64_t draft_tokens_stride_b;
+    sd_processor proc;
+    const int64_t* stop_tokens;
+    int32_t n_stop;
+    int64_t pad_token;
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+    int32_t* n_accepted;
+    int32_t* last_node;
+    int64_t* next_token;
+    float* resample_mass;        /* nullable                                                       */
+    int32_t* n_sibling_rejects;  /* nullable                                                       */
+    int32_t* stop_index;         /* nullable                                                       */
+    int32_t* row_status;
+    int32_t* path;               /* int32 [B, >=max_depth]                                          */
+    int64_t path_stride_b;
+    int64_t* tokens_out;         /* nullable: int64 [B, >=max_depth+1]                               */
+    int64_t tokens_out_stride_b;
+    void* workspace;             /* sd_verify_tree_dynamic_workspace_size bytes                     */
+    size_t workspace_bytes;
+    int32_t* status_or;          /* nullable                                                       */
+} sd_tree_dynamic_args;
+
+size_t sd_verify_tree_dynamic_workspace_size(int32_t batch, int32_t num_nodes, int32_t vocab);
+int32_t sd_verify_tree_dynamic(const sd_tree_dynamic_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -94,8 +94,11 @@ __global__ void __launch_bounds__(kThreads) k_treed_rowsum(Plan P, TreeD T) {
     }
 }
 
-template <int DT>
-__global__ void __launch_bounds__(kThreads) k_treed_walk(Plan P, TreeD T) {
+// The walk of one sequence.  DYN: the sequence's parents come from device memory (sd_verify_tree_dynamic,
+// sd_verify_tree_dynamic.inc) and the child lists are built and validated in LDS; else they are the
+// host's, in T, and parent_dev is unread.
+template <int DT, bool DYN = false>
+__global__ void __launch_bounds__(kThreads) k_treed_walk(Plan P, TreeD T, const int32_t* parent_dev, int64_t parent_stride) {
     __shared__ int64_t ltok[kTreeNodes];
     __shared__ float lu[kTreeNodes], lp[kTreeNodes];
     __shared__ float ly[kTreeNodes];                   // greedy: the token's processed logit
@@ -114,6 +117,55 @@ __global__ void __launch_bounds__(kThreads) k_treed_walk(Plan P, TreeD T) {
     __shared__ int64_t s_x;
     const int b = blockIdx.x, N = T.N, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int nmc = T.n_mchunks;
+    // DYN: this sequence's topology (children in ascending node index)
+    __shared__ int8_t d_parent[DYN ? kTreeNodes : 1];
+    __shared__ uint8_t d_nchild[DYN ? kTreeSlots : 1], d_off[DYN ? kTreeSlots : 1], d_child[DYN ? kTreeNodes : 1];
+    const int8_t* t_parent = T.parent;
+    const uint8_t *t_nchild = T.nchild, *t_off = T.child_off, *t_child = T.child;
+    if constexpr (DYN) {
+        t_parent = d_parent; t_nchild = d_nchild; t_off = d_off; t_child = d_child;
+        int bad = 0;
+        if (tid < N) {                                 // parent[i] in [-1, i-1]
+            const int32_t p = parent_dev[(int64_t)b * parent_stride + tid];
+            bad = p < -1 || p >= tid;
+            d_parent[tid] = (int8_t)(bad ? -1 : p);
+        }
+        bad = __syncthreads_or(bad);
+        if (!bad) {
+            if (tid < N) {                             // the node's place among all children by (slot, node), its depth
+                const int p = d_parent[tid];
+                int pos = 0, dep = 1;
+                for (int j = 0; j < N; ++j) pos += (d_parent[j] < p || (d_parent[j] == p && j < tid)) ? 1 : 0;
+                d_child[pos] = (uint8_t)tid;
+                for (int q = p; q >= 0; q = d_parent[q]) ++dep;
+                bad = dep > T.depth;
+            }
+            if (tid >= kThreads - (N + 1)) {           // the slot's child count and its first entry of child[]
+                const int s = tid - (kThreads - (N + 1));
+                int cnt = 0, off = 0;
+                for (int j = 0; j < N; ++j) { cnt += d_parent[j] + 1 == s ? 1 : 0; off += d_parent[j] + 1 < s ? 1 : 0; }
+                bad = cnt > kTreeC;
+                d_nchild[s] = (uint8_t)cnt; d_off[s] = (uint8_t)off;
+            }
+        }
+        bad = __syncthreads_or(bad);
+        if (bad) {                                     // an invalid topology: the sequence is flagged, nothing is walked
+            if (tid == 0) {
+                const int st = SD_ROW_DONE | SD_ROW_INVALID_DIST;
+                P.n_accepted[b] = 0;
+                T.last_node[b] = -1;
+                P.next_token[b] = -1;
+                if (P.resample_mass) P.resample_mass[b] = NAN;
+                if (T.n_rejects) T.n_rejects[b] = 0;
+                if (P.stop_index) P.stop_index[b] = -1;
+                P.row_status[b] = st;
+                flag_error(P.status_or, st);
+            }
+            if (tid < T.depth) T.path[(int64_t)b * T.path_stride + tid] = -1;
+            if (T.tokens_out && tid <= T.depth) T.tokens_out[(int64_t)b * T.tokens_out_stride + tid] = T.pad_token;
+            return;
+        }
+    }
 
     // drafted ids, accept uniforms (node i takes the row's accept uniform number i) and p of every node's
     // token under its parent slot's row
@@ -124,7 +176,7 @@ __global__ void __launch_bounds__(kThreads) k_treed_walk(Plan P, TreeD T) {
         lu[tid] = uniform_from_word((tid & 3) == 0 ? q4.x : (tid & 3) == 1 ? q4.y : (tid & 3) == 2 ? q4.z : q4.w);
         float p = 0.f, y = NAN;
         if (tok >= 0 && tok < P.V) {
-            const MultiRow<DT> Tr = treed_row<DT>(P, T, b, T.parent[tid] + 1);
+            const MultiRow<DT> Tr = treed_row<DT>(P, T, b, t_parent[tid] + 1);
             const float x = load_one<DT>(Tr.row, tok);
             p = multi_prob<DT>(P, Tr, x, tok);
             y = process_value<DT>(x, tok, P.tT, P.t_keep != 0, Tr.kp);
@@ -158,10 +210,10 @@ __global__ void __launch_bounds__(kThreads) k_treed_walk(Plan P, TreeD T) {
         int s = 0, n = 0, mode = kMultiBonus, rejects = 0, nex = 0;
         double rem = 0.0;
         for (;;) {
-            const int nc = T.nchild[s];
+            const int nc = t_nchild[s];
             rem = lz[s]; nex = 0;
             if (nc == 0) break;
-            const uint8_t* ch = T.child + T.child_off[s];
+            const uint8_t* ch = t_child + t_off[s];
             int hit = -1;
             for (int jr = 0; jr < nc; ++jr) {
                 const int c = ch[jr];
@@ -469,7 +521,8 @@ int32_t sd_verify_tree_distinct(const sd_tree_distinct_args* a, void* stream) {
         constexpr int DT = decltype(dt_)::value;
         const int64_t grid = (int64_t)B * (N + 1) * T.n_mchunks;
         if (int32_t st = launch(sd::k_treed_rowsum<DT>, dim3((uint32_t)grid), dim3(sd::kThreads), 0, stream, P, T)) return st;
-        if (int32_t st = launch(sd::k_treed_walk<DT>, dim3(B), dim3(sd::kThreads), 0, stream, P, T)) return st;
+        if (int32_t st = launch(sd::k_treed_walk<DT>, dim3(B), dim3(sd::kThreads), 0, stream, P, T, (const int32_t*)nullptr, (int64_t)0))
+            return st;
         g_verify_path = SD_PATH_VERIFY_TREE_DISTINCT;
         return SD_OK;
     });

@@ -28,7 +28,9 @@
 // The token-tree verify (sd_verify_tree, sd_verify_tree.inc): k_stats over the tree's rows in row groups,
 // then C_max + 1 mass launches over the slots that still have a j-th child and one walk-and-draw launch.
 // Its distinct-children form (sd_verify_tree_distinct, sd_verify_tree_distinct.inc): k_stats over the
-// target rows, ONE launch of per-chunk row sums and one walk-and-draw launch.
+// target rows, ONE launch of per-chunk row sums and one walk-and-draw launch.  With one topology per
+// sequence, read from device memory (sd_verify_tree_dynamic, sd_verify_tree_dynamic.inc): the same launches,
+// the walk building its child lists in LDS.
 //
 // Every logit row is read once by the statistics pass (the algorithmic bytes); the sampling pass
 // re-reads at most two rows per sequence (served from the 256 MiB Infinity Cache).  See DESIGN.md.
@@ -4351,3 +4353,4 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
 #include "sd_verify_multi.inc"
 #include "sd_verify_tree.inc"
 #include "sd_verify_tree_distinct.inc"
+#include "sd_verify_tree_dynamic.inc"

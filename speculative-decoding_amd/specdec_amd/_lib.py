@@ -42,6 +42,7 @@ SD_PATH_VERIFY_MULTI = 6
 SD_PATH_VERIFY_VP = 7
 SD_PATH_VERIFY_TREE = 8
 SD_PATH_VERIFY_TREE_DISTINCT = 9
+SD_PATH_VERIFY_TREE_DYNAMIC = 10
 SD_PATH_SAMPLE_DRAW_LEAN, SD_PATH_SAMPLE_DRAW, SD_PATH_SAMPLE_NUCLEUS, SD_PATH_SAMPLE_STREAM = 16, 17, 18, 19
 SD_PATH_SAMPLE_GREEDY_LEAN, SD_PATH_SAMPLE_MULTI = 20, 21
 PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PATH_VERIFY_FUSED: "k_verify_fused",
@@ -51,6 +52,7 @@ PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PAT
               SD_PATH_VERIFY_VP: "k_vp_stats+k_vp_decide+k_vp_finish",
               SD_PATH_VERIFY_TREE: "k_stats+k_tree_mass+k_tree_walk",
               SD_PATH_VERIFY_TREE_DISTINCT: "k_stats+k_treed_rowsum+k_treed_walk",
+              SD_PATH_VERIFY_TREE_DYNAMIC: "k_stats+k_treed_rowsum+k_treed_walk<dyn>",
               SD_PATH_SAMPLE_DRAW_LEAN: "k_draw_lean", SD_PATH_SAMPLE_DRAW: "k_draw", SD_PATH_SAMPLE_NUCLEUS: "k_draw_nuc",
               SD_PATH_SAMPLE_STREAM: "k_draw_stream", SD_PATH_SAMPLE_GREEDY_LEAN: "k_draw_lean<greedy>",
               SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize"}
@@ -73,7 +75,9 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_vp_finish",
            "sd_verify_tree_workspace_size", "sd_verify_tree",
            "sd_verify_tree_distinct_workspace_size", "sd_verify_tree_distinct",
-           "sd_kv_compact")
+           "sd_kv_compact",
+           "sd_tree_grow_workspace_size", "sd_tree_grow", "sd_tree_select_workspace_size", "sd_tree_select",
+           "sd_verify_tree_dynamic_workspace_size", "sd_verify_tree_dynamic")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -85,6 +89,9 @@ SD_MULTI_MAX_DRAFTS, SD_MULTI_MAX_NODES, SD_MULTI_MAX_ROWS = 8, 64, 16384
 
 # token-tree verify
 SD_TREE_MAX_NODES, SD_TREE_MAX_CHILDREN, SD_TREE_MAX_BATCH = 64, 8, 16384
+
+# dynamic draft trees (sd_tree_grow / sd_tree_select)
+SD_TREE_POOL_MAX, SD_TREE_GROW_MAX_WIDTH, SD_TREE_GROW_MAX_VOCAB = 2048, 8, 524288
 
 # KV-cache compaction onto a tree path
 SD_KV_MAX_TENSORS = 256
@@ -266,6 +273,52 @@ class sd_tree_distinct_args(C.Structure):
     ]
 
 
+class sd_tree_grow_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("vocab", C.c_int32), ("level", C.c_int32), ("width", C.c_int32),
+        ("branch", C.c_int32), ("dtype", C.c_int32),
+        ("logits", C.c_void_p), ("stride_b", C.c_int64), ("stride_r", C.c_int64),
+        ("frontier_in", C.c_void_p), ("frontier_in_stride_b", C.c_int64),
+        ("pool_token", C.c_void_p), ("pool_score", C.c_void_p), ("pool_parent", C.c_void_p),
+        ("pool_stride_b", C.c_int64),
+        ("frontier_token", C.c_void_p), ("frontier_pool", C.c_void_p), ("frontier_parent_rank", C.c_void_p),
+        ("frontier_stride_b", C.c_int64),
+        ("row_status", C.c_void_p), ("status_or", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class sd_tree_select_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("pool_size", C.c_int32), ("num_nodes", C.c_int32), ("reserved", C.c_int32),
+        ("pool_token", C.c_void_p), ("pool_score", C.c_void_p), ("pool_parent", C.c_void_p),
+        ("pool_stride_b", C.c_int64),
+        ("tokens", C.c_void_p), ("parent", C.c_void_p), ("depth", C.c_void_p), ("pool_index", C.c_void_p),
+        ("anc", C.c_void_p), ("out_stride_b", C.c_int64),
+        ("row_status", C.c_void_p), ("status_or", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class sd_tree_dynamic_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("num_nodes", C.c_int32), ("vocab", C.c_int32), ("max_depth", C.c_int32),
+        ("parent_dev", C.c_void_p), ("parent_stride_b", C.c_int64),
+        ("target_rows", C.c_void_p * (SD_TREE_MAX_NODES + 1)), ("target_stride_b", C.c_int64),
+        ("dtype", C.c_int32),
+        ("draft_tokens", C.c_void_p), ("draft_tokens_stride_b", C.c_int64),
+        ("proc", sd_processor), ("stop_tokens", C.c_void_p), ("n_stop", C.c_int32), ("pad_token", C.c_int64),
+        ("noise", sd_noise),
+        ("n_accepted", C.c_void_p), ("last_node", C.c_void_p), ("next_token", C.c_void_p),
+        ("resample_mass", C.c_void_p), ("n_sibling_rejects", C.c_void_p), ("stop_index", C.c_void_p),
+        ("row_status", C.c_void_p),
+        ("path", C.c_void_p), ("path_stride_b", C.c_int64),
+        ("tokens_out", C.c_void_p), ("tokens_out_stride_b", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("status_or", C.c_void_p),
+    ]
+
+
 class sd_kv_compact_args(C.Structure):
     _fields_ = [
         ("n_tensors", C.c_int32), ("batch", C.c_int32), ("heads", C.c_int32), ("max_depth", C.c_int32),
@@ -365,6 +418,18 @@ def _load():
     lib.sd_verify_tree_distinct.argtypes = [C.POINTER(sd_tree_distinct_args), C.c_void_p]
     lib.sd_kv_compact.restype = C.c_int32
     lib.sd_kv_compact.argtypes = [C.POINTER(sd_kv_compact_args), C.c_void_p]
+    lib.sd_tree_grow_workspace_size.restype = C.c_size_t
+    lib.sd_tree_grow_workspace_size.argtypes = [C.c_int32] * 5
+    lib.sd_tree_grow.restype = C.c_int32
+    lib.sd_tree_grow.argtypes = [C.POINTER(sd_tree_grow_args), C.c_void_p]
+    lib.sd_tree_select_workspace_size.restype = C.c_size_t
+    lib.sd_tree_select_workspace_size.argtypes = [C.c_int32] * 3
+    lib.sd_tree_select.restype = C.c_int32
+    lib.sd_tree_select.argtypes = [C.POINTER(sd_tree_select_args), C.c_void_p]
+    lib.sd_verify_tree_dynamic_workspace_size.restype = C.c_size_t
+    lib.sd_verify_tree_dynamic_workspace_size.argtypes = [C.c_int32] * 3
+    lib.sd_verify_tree_dynamic.restype = C.c_int32
+    lib.sd_verify_tree_dynamic.argtypes = [C.POINTER(sd_tree_dynamic_args), C.c_void_p]
     lib.sd_vp_stats_bytes.restype = C.c_size_t
     lib.sd_vp_stats_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.sd_vp_cand_bytes.restype = C.c_size_t

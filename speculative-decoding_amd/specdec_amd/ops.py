@@ -793,6 +793,198 @@ def verify_tree_distinct(target, draft_tokens: torch.Tensor, parent, proc, noise
     return out
 
 
+def verify_tree_dynamic(target, draft_tokens: torch.Tensor, parent_dev: torch.Tensor, proc, noise, max_depth: int,
+                        stop_tokens: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None,
+                        pad_token_id: int = 0, row_base: int = 0):
+    """``verify_tree_distinct`` with one topology PER SEQUENCE, read from device memory
+    (sd_verify_tree_dynamic): parent_dev int32 [B, >=N] holds every sequence's parents
+    (``tree_select`` writes them), N = target.shape[1] - 1.  max_depth (1..32) sizes path [B, max_depth] and
+    tokens_out [B, max_depth + 1].  The topology is validated on the device: a sequence whose parents
+    are out of range, has more than 8 children under one slot or is deeper than max_depth gets
+    SD_ROW_INVALID_DIST, n_accepted 0, next_token -1 and path -1.  Everything else is
+    ``verify_tree_distinct``'s."""
+    from types import SimpleNamespace
+    if _user_process(proc) is not None:
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: verify_tree_dynamic fuses the "
+                        "processing of the target rows and cannot run a user _process")
+    spec = proc_spec(proc)
+    if not isinstance(noise, PhiloxNoise):
+        raise TypeError("verify_tree_dynamic needs PhiloxNoise (the rule defines no stream order for this step)")
+    if torch.is_tensor(target):
+        if target.dim() != 3 or target.shape[1] < 2:
+            raise ValueError(f"target: expected [B, N+1, V], got {tuple(target.shape)}")
+        N = target.shape[1] - 1
+    else:
+        target = list(target)
+        N = len(target) - 1
+    depth = int(max_depth)
+    if not 1 <= N <= _lib.SD_TREE_MAX_NODES:
+        raise ValueError(f"verify_tree_dynamic: 1..{_lib.SD_TREE_MAX_NODES} nodes, got {N}")
+    if not 1 <= depth <= _lib.SD_MAX_GAMMA:
+        raise ValueError(f"verify_tree_dynamic: max_depth must be in 1..{_lib.SD_MAX_GAMMA}, got {depth}")
+    t_ptrs, t_stride, B, V, tdt, dev = _slot_rows(target, "target", list(range(N + 1)), N + 1, None)
+    if not 1 <= B <= _lib.SD_TREE_MAX_BATCH:
+        raise ValueError(f"verify_tree_dynamic: batch must be in 1..{_lib.SD_TREE_MAX_BATCH}, got {B}")
+    if draft_tokens.dtype != torch.long or draft_tokens.dim() != 2 or draft_tokens.shape[0] != B \
+            or draft_tokens.shape[1] < N or draft_tokens.stride(1) != 1 or draft_tokens.device != dev:
+        raise ValueError(f"draft_tokens must be int64 [B, >={N}] on {dev}")
+    if parent_dev.dtype != torch.int32 or parent_dev.dim() != 2 or parent_dev.shape[0] != B \
+            or parent_dev.shape[1] < N or parent_dev.stride(1) != 1 or parent_dev.device != dev:
+        raise ValueError(f"parent_dev must be int32 [B, >={N}] on {dev}")
+    stops = stop_tokens if stop_tokens is not None else torch.empty(0, dtype=torch.long, device=dev)
+    if stops.dtype != torch.long or stops.device != dev or not stops.is_contiguous():
+        raise ValueError("stop_tokens must be a contiguous int64 device tensor")
+    # one allocation: next_token (int64) first, then the six 4-byte fields and the path
+    buf = torch.empty(8 * B + 4 * (6 + depth) * B, dtype=torch.uint8, device=dev)
+    nxt = buf[:8 * B].view(torch.long)
+    f4 = buf[8 * B:].view(torch.int32)
+    i32 = [f4[k * B:(k + 1) * B] for k in range(6)]
+    out = SimpleNamespace(n_accepted=i32[0], last_node=i32[1], next_token=nxt, resample_mass=i32[2].view(torch.float32),
+                          n_sibling_rejects=i32[3], stop_index=i32[4], row_status=i32[5],
+                          path=f4[6 * B:].view(B, depth),
+                          tokens_out=torch.empty(B, depth + 1, dtype=torch.long, device=dev))
+    nz, keep = _noise_struct(noise, 0, dev, row_base)
+    ws = _workspace(lib.sd_verify_tree_dynamic_workspace_size(B, N, V), dev)
+    a = _lib.sd_tree_dynamic_args()
+    a.batch, a.num_nodes, a.vocab, a.max_depth = B, N, V, depth
+    a.parent_dev = parent_dev.data_ptr()
+    a.parent_stride_b = parent_dev.stride(0) if B > 1 else parent_dev.shape[1]
+    a.target_rows = _ROW_PTRS(*t_ptrs)
+    a.target_stride_b = t_stride
+    a.dtype = _DT[tdt]
+    a.draft_tokens = draft_tokens.data_ptr()
+    a.draft_tokens_stride_b = draft_tokens.stride(0) if B > 1 else draft_tokens.shape[1]
+    a.proc = spec.struct()
+    a.stop_tokens, a.n_stop = (stops.data_ptr() if stops.numel() else None), stops.numel()
+    a.pad_token = int(pad_token_id)
+    a.noise = nz
+    for f in TREE_FIELDS:
+        setattr(a, f, getattr(out, f).data_ptr())
+    a.path, a.path_stride_b = out.path.data_ptr(), depth
+    a.tokens_out, a.tokens_out_stride_b = out.tokens_out.data_ptr(), depth + 1
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_verify_tree_dynamic(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_verify_tree_dynamic")
+    del keep
+    return out
+
+
+# --------------------------------------------------------------------------- dynamic draft trees
+def tree_pool(batch: int, pool_size: int, device):
+    """The pool buffers ``tree_grow`` appends to and ``tree_select`` reads: a namespace of token int64,
+    score fp32 and parent int32, each [batch, pool_size]."""
+    from types import SimpleNamespace
+    return SimpleNamespace(token=torch.zeros(batch, pool_size, dtype=torch.long, device=device),
+                           score=torch.zeros(batch, pool_size, dtype=torch.float32, device=device),
+                           parent=torch.zeros(batch, pool_size, dtype=torch.int32, device=device))
+
+
+def _pool_check(pool, B: int, need: int, dev) -> int:
+    for name, dt in (("token", torch.long), ("score", torch.float32), ("parent", torch.int32)):
+        t = getattr(pool, name)
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] != B or t.shape[1] < need or t.stride(1) != 1 or t.device != dev:
+            raise ValueError(f"pool.{name} must be {dt} [B, >={need}] on {dev}")
+    st = pool.token.stride(0)
+    if pool.score.stride(0) != st or pool.parent.stride(0) != st:
+        raise ValueError("the pool's three buffers must share one row stride")
+    return st if B > 1 else pool.token.shape[1]
+
+
+def tree_grow(logits: torch.Tensor, level: int, width: int, branch: int, pool, frontier_in: Optional[torch.Tensor] = None,
+              status_or: Optional[torch.Tensor] = None):
+    """One level of a dynamic draft tree on the device (sd_tree_grow).  logits
+    [B, F_prev, V]: the drafter's rows after the nodes of the current frontier (level 1: the root's one
+    row), F_prev = ``DynamicTreeSpec.frontier[level - 1]``.  Every row's ``branch`` best tokens by raw
+    logit become candidates with score = the parent's score + the fp32 log-softmax of the token; they
+    are appended to ``pool`` (``tree_pool``) and the best min(width, F_prev * branch) of them form the next
+    frontier, in ascending pool index.  frontier_in: the previous call's ``pool`` output int32 [B, F_prev]
+    (None at level 1).  Returns a namespace of token int64, pool int32 and parent_rank int32, each
+    [B, F_next], and row_status int32 [B].  No host synchronisation; a NaN row sets SD_ROW_INVALID_DIST."""
+    from types import SimpleNamespace
+    from .tree import DynamicTreeSpec
+    if logits.dim() != 3:
+        raise ValueError(f"logits: expected [B, F, V], got {tuple(logits.shape)}")
+    B, F, V = logits.shape
+    level, width, branch = int(level), int(width), int(branch)
+    shape = DynamicTreeSpec(level, width, branch, 1)          # ValueError for a shape outside the limits
+    if branch > V:
+        raise ValueError(f"tree_grow: branch {branch} exceeds the vocabulary {V}")
+    Fp, Fn, base = shape.frontier[level - 1], shape.frontier[level], shape.base[level - 1]
+    if F != Fp:
+        raise ValueError(f"logits: level {level} expands {Fp} frontier rows, got {F}")
+    _require_rows(logits[:, 0, :], "logits", V)
+    dev = logits.device
+    if not 1 <= B <= _lib.SD_TREE_MAX_BATCH or V > _lib.SD_TREE_GROW_MAX_VOCAB:
+        raise ValueError("tree_grow: batch or vocabulary outside the limits")
+    pstride = _pool_check(pool, B, base + Fp * branch, dev)
+    a = _lib.sd_tree_grow_args()
+    if level > 1:
+        if frontier_in is None or frontier_in.dtype != torch.int32 or frontier_in.dim() != 2 or frontier_in.shape[0] != B \
+                or frontier_in.shape[1] < Fp or frontier_in.stride(1) != 1 or frontier_in.device != dev:
+            raise ValueError(f"frontier_in must be int32 [B, >={Fp}] on {dev}")
+        a.frontier_in = frontier_in.data_ptr()
+        a.frontier_in_stride_b = frontier_in.stride(0) if B > 1 else frontier_in.shape[1]
+    # one allocation: the tokens (int64) first, then pool, parent_rank and row_status
+    buf = torch.empty(8 * B * Fn + 4 * (2 * B * Fn + B), dtype=torch.uint8, device=dev)
+    f4 = buf[8 * B * Fn:].view(torch.int32)
+    out = SimpleNamespace(token=buf[:8 * B * Fn].view(torch.long).view(B, Fn), pool=f4[:B * Fn].view(B, Fn),
+                          parent_rank=f4[B * Fn:2 * B * Fn].view(B, Fn), row_status=f4[2 * B * Fn:])
+    ws = _workspace(lib.sd_tree_grow_workspace_size(B, V, level, width, branch), dev)
+    a.batch, a.vocab, a.level, a.width, a.branch, a.dtype = B, V, level, width, branch, _DT[logits.dtype]
+    a.logits = logits.data_ptr()
+    a.stride_b = logits.stride(0) if B > 1 else 0
+    a.stride_r = logits.stride(1) if Fp > 1 else V
+    a.pool_token, a.pool_score, a.pool_parent = pool.token.data_ptr(), pool.score.data_ptr(), pool.parent.data_ptr()
+    a.pool_stride_b = pstride
+    a.frontier_token, a.frontier_pool = out.token.data_ptr(), out.pool.data_ptr()
+    a.frontier_parent_rank, a.frontier_stride_b = out.parent_rank.data_ptr(), Fn
+    a.row_status = out.row_status.data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _lib.check(lib.sd_tree_grow(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_grow")
+    return out
+
+
+def tree_select(pool, num_nodes: int, pool_size: Optional[int] = None, status_or: Optional[torch.Tensor] = None):
+    """The rerank of a grown pool (sd_tree_select): the ``num_nodes`` best of the first ``pool_size`` entries
+    (default: all) by (score descending, pool index ascending), in ascending pool index — a set closed
+    under parents with parent[i] < i, what ``verify_tree_dynamic`` takes.  Returns a namespace of
+    tokens int64, parent int32 (-1: a child of the root), depth int32 (1-based), pool_index int32 and
+    anc int64 (bit k set iff node k is node i or an ancestor of it; the uint64 bit pattern), each [B, N],
+    and row_status int32 [B]."""
+    from types import SimpleNamespace
+    B = pool.token.shape[0]
+    P = pool.token.shape[1] if pool_size is None else int(pool_size)
+    N = int(num_nodes)
+    dev = pool.token.device
+    if not 1 <= P <= _lib.SD_TREE_POOL_MAX:
+        raise ValueError(f"tree_select: pool_size must be in 1..{_lib.SD_TREE_POOL_MAX}, got {P}")
+    if not 1 <= N <= min(P, _lib.SD_TREE_MAX_NODES):
+        raise ValueError(f"tree_select: num_nodes must be in 1..{min(P, _lib.SD_TREE_MAX_NODES)}, got {N}")
+    if not 1 <= B <= _lib.SD_TREE_MAX_BATCH:
+        raise ValueError("tree_select: batch outside the limits")
+    pstride = _pool_check(pool, B, P, dev)
+    # one allocation: tokens and anc (8-byte) first, then parent, depth, pool_index and row_status
+    buf = torch.empty(16 * B * N + 4 * (3 * B * N + B), dtype=torch.uint8, device=dev)
+    i8 = buf[:16 * B * N].view(torch.long)
+    f4 = buf[16 * B * N:].view(torch.int32)
+    out = SimpleNamespace(tokens=i8[:B * N].view(B, N), anc=i8[B * N:].view(B, N), parent=f4[:B * N].view(B, N),
+                          depth=f4[B * N:2 * B * N].view(B, N), pool_index=f4[2 * B * N:3 * B * N].view(B, N),
+                          row_status=f4[3 * B * N:])
+    ws = _workspace(lib.sd_tree_select_workspace_size(B, P, N), dev)
+    a = _lib.sd_tree_select_args()
+    a.batch, a.pool_size, a.num_nodes = B, P, N
+    a.pool_token, a.pool_score, a.pool_parent = pool.token.data_ptr(), pool.score.data_ptr(), pool.parent.data_ptr()
+    a.pool_stride_b = pstride
+    a.tokens, a.parent, a.depth = out.tokens.data_ptr(), out.parent.data_ptr(), out.depth.data_ptr()
+    a.pool_index, a.anc, a.out_stride_b = out.pool_index.data_ptr(), out.anc.data_ptr(), N
+    a.row_status = out.row_status.data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _lib.check(lib.sd_tree_select(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_select")
+    return out
+
+
 def topk_children(logits_rows: torch.Tensor, k: int) -> torch.Tensor:
     """The k best token ids of every row of logits [R, V], int64 [R, k]: value descending, lowest index
     first among equals (one ``beam_topk`` pass).  These are the children ``verify_tree_distinct`` takes:

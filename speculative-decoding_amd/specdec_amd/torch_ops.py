@@ -32,6 +32,19 @@ GPU), and callable as ``torch.ops.specdec.*``.
         One token-tree verify step whose children are distinct candidates, e.g. the drafter's top-c tokens
         (sd_verify_tree_distinct): no drafter rows, Philox noise.
 
+    torch.ops.specdec.tree_grow(logits [B, F, V], level, width, branch, pool_token int64 [B, P], pool_score fp32 [B, P],
+                                pool_parent int32 [B, P], frontier_in int32 [B, F]?)
+        -> (frontier_token int64 [B, F'], frontier_pool int32 [B, F'], frontier_parent_rank int32 [B, F'],
+            row_status int32 [B])
+        One level of a dynamic draft tree (sd_tree_grow): appends the level's candidates to the pool (mutated).
+    torch.ops.specdec.tree_select(pool_token, pool_score, pool_parent, num_nodes, pool_size)
+        -> (tokens int64, parent int32, depth int32, pool_index int32, anc int64 [B, N], row_status int32 [B])
+        The rerank (sd_tree_select): the N best pool entries in ascending pool index.
+    torch.ops.specdec.verify_tree_dynamic(target [B, N+1, V], draft_tokens int64 [B, >=N], parent_dev int32 [B, >=N],
+                                          max_depth, stop_tokens int64 [n], kind, temperature, top_k, top_p, seed,
+                                          offset, row_base) -> verify_tree's outputs, path int32 [B, max_depth]
+        verify_tree_distinct with one topology per sequence, read from device memory (sd_verify_tree_dynamic).
+
     torch.ops.specdec.beam_topk(logits [R, V], k) -> (logprob fp32 [R, k], token int64 [R, k])
         The beam step's row pass: topk(log_softmax(logits), k), lowest index first among equal values
         (sampling/base_decoding.py:136-137).
@@ -174,6 +187,63 @@ def _(target, draft_tokens, parent, stop_tokens, kind, temperature, top_k, top_p
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
     return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.TREE_FIELDS) + (
         target.new_empty(B, TokenTree(list(parent)).depth, dtype=torch.int32),)
+
+
+def _pool_ns(pool_token, pool_score, pool_parent):
+    from types import SimpleNamespace
+    return SimpleNamespace(token=pool_token, score=pool_score, parent=pool_parent)
+
+
+@torch.library.custom_op("specdec::tree_grow", mutates_args=("pool_token", "pool_score", "pool_parent"))
+def tree_grow(logits: Tensor, level: int, width: int, branch: int, pool_token: Tensor, pool_score: Tensor,
+              pool_parent: Tensor, frontier_in: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """One level of a dynamic draft tree (ops.tree_grow): the next frontier's tokens, pool indices and
+    parent ranks, and the row status; the level's candidates are appended to the pool tensors."""
+    out = ops.tree_grow(logits, level, width, branch, _pool_ns(pool_token, pool_score, pool_parent), frontier_in)
+    return out.token.clone(), out.pool.clone(), out.parent_rank.clone(), out.row_status.clone()   # views of one buffer
+
+
+@tree_grow.register_fake
+def _(logits, level, width, branch, pool_token, pool_score, pool_parent, frontier_in=None):
+    from .tree import DynamicTreeSpec
+    B, Fn = logits.shape[0], DynamicTreeSpec(level, width, branch, 1).frontier[level]
+    return (logits.new_empty(B, Fn, dtype=torch.long), logits.new_empty(B, Fn, dtype=torch.int32),
+            logits.new_empty(B, Fn, dtype=torch.int32), logits.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("specdec::tree_select", mutates_args=())
+def tree_select(pool_token: Tensor, pool_score: Tensor, pool_parent: Tensor, num_nodes: int,
+                pool_size: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The rerank of a grown pool (ops.tree_select): tokens, parent, depth, pool_index, anc, row_status."""
+    out = ops.tree_select(_pool_ns(pool_token, pool_score, pool_parent), num_nodes, pool_size)
+    return tuple(getattr(out, f).clone() for f in ("tokens", "parent", "depth", "pool_index", "anc", "row_status"))
+
+
+@tree_select.register_fake
+def _(pool_token, pool_score, pool_parent, num_nodes, pool_size):
+    B = pool_token.shape[0]
+    e = lambda dt: pool_token.new_empty(B, num_nodes, dtype=dt)
+    return (e(torch.long), e(torch.int32), e(torch.int32), e(torch.int32), e(torch.long),
+            pool_token.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("specdec::verify_tree_dynamic", mutates_args=())
+def verify_tree_dynamic(target: Tensor, draft_tokens: Tensor, parent_dev: Tensor, max_depth: int, stop_tokens: Tensor,
+                        kind: int, temperature: float, top_k: int, top_p: float, seed: int, offset: int,
+                        row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """One token-tree verify step with per-sequence device topologies (ops.verify_tree_dynamic): the seven
+    [B] outputs in ops.TREE_FIELDS' order, then path int32 [B, max_depth]."""
+    out = ops.verify_tree_dynamic(target, draft_tokens, parent_dev, _spec(kind, temperature, top_k, top_p),
+                                  PhiloxNoise(seed, offset), max_depth, stop_tokens=stop_tokens, row_base=row_base)
+    return tuple(getattr(out, f).clone() for f in ops.TREE_FIELDS) + (out.path.clone(),)
+
+
+@verify_tree_dynamic.register_fake
+def _(target, draft_tokens, parent_dev, max_depth, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
+    B = target.shape[0]
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.TREE_FIELDS) + (
+        target.new_empty(B, max_depth, dtype=torch.int32),)
 
 
 def _vp_step(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens, shard: int, num_shards: int,

@@ -11,6 +11,7 @@ from typing import List, Sequence
 import torch
 
 MAX_NODES, MAX_CHILDREN, MAX_DEPTH = 64, 8, 32      # SD_TREE_MAX_NODES, SD_TREE_MAX_CHILDREN, SD_MAX_GAMMA
+MAX_WIDTH, MAX_POOL = 8, 2048                       # SD_TREE_GROW_MAX_WIDTH, SD_TREE_POOL_MAX
 
 
 class TokenTree:
@@ -120,3 +121,68 @@ class TokenTree:
 
     def __repr__(self) -> str:
         return f"TokenTree(nodes={self.num_nodes}, depth={self.depth}, parent={self.parent})"
+
+
+class DynamicTreeSpec:
+    """The static shape of a dynamic draft tree (sd_tree_grow / sd_tree_select): ``levels``
+    growth levels, ``width`` frontier nodes expanded per level, ``branch`` children per expanded node and
+    ``num_nodes`` nodes sent to the target.  What the host knows without reading a score:
+
+    frontier[l]   nodes of the frontier after level l (frontier[0] = 1, the root): min(width, frontier[l-1] * branch)
+    base[l]       pool index of level l + 1's first candidate; level l + 1 adds frontier[l] * branch
+    pool_size     base[levels]
+    """
+
+    def __init__(self, levels: int, width: int, branch: int, num_nodes: int):
+        levels, width, branch, num_nodes = int(levels), int(width), int(branch), int(num_nodes)
+        if not 1 <= levels <= MAX_DEPTH:
+            raise ValueError(f"levels must be in 1..{MAX_DEPTH}, got {levels}")
+        if not 1 <= width <= MAX_WIDTH:
+            raise ValueError(f"width must be in 1..{MAX_WIDTH}, got {width}")
+        if not 1 <= branch <= MAX_CHILDREN:
+            raise ValueError(f"branch must be in 1..{MAX_CHILDREN}, got {branch}")
+        self.levels, self.width, self.branch = levels, width, branch
+        self.frontier: List[int] = [1]
+        self.base: List[int] = [0]
+        for _ in range(levels):
+            self.base.append(self.base[-1] + self.frontier[-1] * branch)
+            self.frontier.append(min(width, self.frontier[-1] * branch))
+        self.pool_size = self.base[-1]
+        if self.pool_size > MAX_POOL:
+            raise ValueError(f"the pool holds at most {MAX_POOL} candidates, this shape makes {self.pool_size}")
+        if not 1 <= num_nodes <= min(MAX_NODES, self.pool_size):
+            raise ValueError(f"num_nodes must be in 1..{min(MAX_NODES, self.pool_size)}, got {num_nodes}")
+        self.num_nodes = num_nodes
+
+    def truncated(self, depth: int) -> "DynamicTreeSpec":
+        """The first `depth` levels, num_nodes cut to the smaller pool (for the end of a sequence)."""
+        if depth >= self.levels:
+            return self
+        if depth < 1:
+            raise ValueError("truncated: depth must be at least 1")
+        pool = self.base[depth]
+        return DynamicTreeSpec(depth, self.width, self.branch, min(self.num_nodes, pool))
+
+    def __repr__(self) -> str:
+        return (f"DynamicTreeSpec(levels={self.levels}, width={self.width}, branch={self.branch}, "
+                f"num_nodes={self.num_nodes}, pool={self.pool_size})")
+
+
+def dynamic_attention_inputs(anc: torch.Tensor, depth: torch.Tensor, prefix_len: int, dtype: torch.dtype = torch.float32):
+    """(mask, position_ids) of a forward over prefix + the N nodes ``tree_select`` chose, built on the
+    device from its ``anc`` int64 [B, N] and ``depth`` int32 [B, N] with ``TokenTree.attention_inputs``'
+    conventions: the additive mask [B, 1, L, L] (0 where attention is allowed, finfo(dtype).min where
+    not), L = prefix_len + N, and position_ids [B, L] with node i at prefix_len + depth(i) - 1.  No host
+    read."""
+    B, n = anc.shape
+    dev = anc.device
+    L = prefix_len + n
+    allow = torch.zeros(B, L, L, dtype=torch.bool, device=dev)
+    allow[:, :prefix_len, :prefix_len] = torch.ones(prefix_len, prefix_len, dtype=torch.bool, device=dev).tril()
+    allow[:, prefix_len:, :prefix_len] = True
+    bits = torch.arange(n, device=dev, dtype=torch.long)
+    allow[:, prefix_len:, prefix_len:] = ((anc[:, :, None] >> bits[None, None, :]) & 1).bool()
+    mask = torch.zeros(B, L, L, dtype=dtype, device=dev)
+    mask.masked_fill_(~allow, torch.finfo(dtype).min)
+    pos = torch.cat([torch.arange(prefix_len, device=dev).expand(B, prefix_len), prefix_len + depth.long() - 1], 1)
+    return mask[:, None], pos
