@@ -305,6 +305,10 @@ typedef enum {
     SD_OPT_SAMP_CHUNKS = 8,     /* ABI 11. 0 (default: 2, 4 in ticket order): 2048-element chunks each
                                    sampling workgroup of the fused verify draws; 2, 4 or 8 pin it
                                    (the same chunks and draws whatever the grouping)              */
+    SD_OPT_ARG_FAST = 9,        /* 1 (default): k_verify_fused in block-id order forms its row
+                                   addresses from leading (preloaded) kernel parameters when the
+                                   target rows are equally spaced; 0: always from the row table
+                                   (A/B, tests; the same results)                                 */
 } sd_option;
 int32_t sd_set_option(int32_t option, int32_t value);
 int32_t sd_get_option(int32_t option, int32_t* value);

@@ -433,6 +433,14 @@ constexpr int kMaxSampPairs = 4;   // chunk pairs per fused sampler in ticket or
 #ifndef SD_SAMP_PREFETCH
 #define SD_SAMP_PREFETCH 0            // 1: ticket-order samplers load the next chunk pair ahead (93 VGPRs: slower at B = 512)
 #endif
+// The block-id fused verify's leading kernel parameters (stats_body, ARGS)
+struct SpanArgs {
+    const char* tbase;      // target slot 0, sequence 0; null: the rows are not equally spaced (P.trow[s])
+    int64_t slot_stride;    // bytes from slot s to slot s + 1 (>= 0; 0: every slot is one tensor)
+    int64_t seq_stride;     // bytes from sequence b to b + 1 (P.tstride in bytes)
+    int32_t V, n_chunks, chunk, n_tslots, xcd_affine, B;   // as in Plan
+};
+
 template <int DT, bool FAST, int MAXP>
 __device__ __forceinline__ void fused_sampler(const Plan& P, int b, int c, int wg_id);
 template <int DT, bool FAST>
@@ -444,25 +452,37 @@ __device__ __forceinline__ void fused_finish(const Plan& P, int b, const Decisio
 // P.n_samp sampling workgroups poll the decider's decision records, draw their chunk's candidate of
 // the decided row and publish it; the decider then polls those records and finishes (the token, the
 // outputs, the engine state): no k_sample launch, no kernel boundary, no decision reload.
+//
+// ARGS (the block-id fused verify): what a span's first row load depends on comes from the kernel's
+// leading scalar parameters (SpanArgs), which gfx950 preloads into SGPRs before the wave starts
+// (k_draw_lean's DrawLeanRest has the details), not from scalar loads of P: the batch, the span
+// geometry, the placement flag and the rows' layout.  With equally spaced target rows (views
+// tl[:, t, :] of one tensor: fa.tbase set) the row address is formed from them alone; otherwise
+// (fa.tbase null) the row's base is the one table load P.trow[s].  The launch is 1-D, in poll mode,
+// over the target slots [0, n_tslots) only (launch_fused), so the block id, the mode and the slot
+// range need no load either.  The decider, the samplers and the finish read P as before.
 template <int DT, bool FAST, bool TAIL, bool SAMP, bool TICKET = false>
-__device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_cnt) {
+__device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_cnt, const SpanArgs& fa = SpanArgs{}) {
     __shared__ float lm[4], ls[4];
     constexpr int VEC = Elem<DT>::kVec;
     constexpr int STEP = kThreads * VEC;                      // elements per workgroup stage
-    const int wg_id = blockIdx.y * gridDim.x + blockIdx.x;
+    constexpr bool ARGS = SAMP && !TICKET;
+    if constexpr (ARGS) { slot_lo = 0; slot_cnt = fa.n_tslots; }
+    const int wg_id = ARGS ? blockIdx.x : blockIdx.y * gridDim.x + blockIdx.x;
     SD_TS(wg_id, 0);
     // The kernel-argument fields the first row loads depend on, read in one straight-line block (no
     // branch between them, both row tables indexed unconditionally): the scalar loads then go out
     // together with one wait, instead of a chain of ~10 dependent waits that put the first row
     // load ~3 us after the start at batch 1.
-    const int gx = P.n_chunks;
-    const int xa = P.xcd_affine, nt = P.n_tslots;
+    const int gx = ARGS ? fa.n_chunks : P.n_chunks;
+    const int xa = ARGS ? fa.xcd_affine : P.xcd_affine, nt = ARGS ? fa.n_tslots : P.n_tslots;
     const int64_t tstr = P.tstride, dstr = P.dstride;
+    const int nB = ARGS ? fa.B : P.B, nV = ARGS ? fa.V : P.V, span_elems = ARGS ? fa.chunk : P.chunk;
     // poll mode (TAIL): a 1-D grid of B x (slot_cnt x n_chunks + 1) workgroups — per sequence its
     // streaming spans and one DECIDER, which streams nothing: it prefetches the drafts' inputs while
     // the spans stream, polls their records and decides.  Counter mode: (n_chunks, B x slot_cnt), the
     // last arrival decides.
-    const bool poll = TAIL && P.kpoll;
+    const bool poll = ARGS || (TAIL && P.kpoll);
     const int n_span = slot_cnt * gx;
     const int per_seq = n_span + (poll ? 1 : 0);
     int b, s, chunk;
@@ -504,14 +524,14 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
         chunk = samp < 0 && item < n_span ? item % gx : 0;
         SD_TS_ROLE(wg_id, ((int64_t)s_tk << 32) | ((int64_t)b << 12) |
                               (samp >= 0 ? 0x800 | samp : (decider ? 0x400 : item)));
-    } else if (SAMP && !TICKET && wg_id >= P.B * per_seq) {
+    } else if (SAMP && !TICKET && wg_id >= nB * per_seq) {
         // the samplers come after every span and decider in dispatch order (block id): they only wait
         // for a decision, so the spans, which wait for nothing, always get their slots first, and a
         // sampler frees its slot once it has published.  Sequence b = id % B: with B % 8 == 0 every
         // workgroup of a sequence sits on one XCD group (affine_split's rule)
-        const int t = wg_id - P.B * per_seq;
-        b = t % P.B;
-        samp = t / P.B;
+        const int t = wg_id - nB * per_seq;
+        b = t % nB;
+        samp = t / nB;
         s = slot_lo;
         chunk = 0;
     } else {
@@ -554,11 +574,17 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
             seq_advance(P, b, s_epoch);
         return;
     }
-    const bool is_t = s < nt;
-    const char* tp = static_cast<const char*>(P.trow[is_t ? s : 0]);
-    const char* dp = static_cast<const char*>(P.drow[is_t ? 0 : s - nt]);
+    const bool is_t = ARGS || s < nt;
     const int r = b * P.slots + s;
-    const void* row = is_t ? tp + b * tstr * (P.tdt == SD_F32 ? 4 : 2) : dp + b * dstr * (P.ddt == SD_F32 ? 4 : 2);
+    const void* row;
+    if constexpr (ARGS) {
+        const char* tp = fa.tbase ? fa.tbase + s * fa.slot_stride : static_cast<const char*>(P.trow[s]);
+        row = tp + b * fa.seq_stride;
+    } else {
+        const char* tp = static_cast<const char*>(P.trow[is_t ? s : 0]);
+        const char* dp = static_cast<const char*>(P.drow[is_t ? 0 : s - nt]);
+        row = is_t ? tp + b * tstr * (P.tdt == SD_F32 ? 4 : 2) : dp + b * dstr * (P.ddt == SD_F32 ? 4 : 2);
+    }
     // poll mode: this call's epoch of sequence b (thread 0), issued AFTER the first row loads and
     // kept in a register until the record: loads complete in order, so an atomic issued first
     // held back the wave's first stage (batch 1: stream done 3.2 vs ~1.4 us after the start)
@@ -580,14 +606,14 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
     const bool has_keep = !FAST && (is_t ? P.t_keep : P.d_keep);
     const RowKeep kp = has_keep ? keep_of(P, r) : RowKeep{-INFINITY, INT_MAX, 0, 0};
     // This workgroup's stages (STEP elements each) of the row: one contiguous span.
-    const int nst = (P.V + STEP - 1) / STEP;
-    const int spw = P.chunk / STEP;
+    const int nst = (nV + STEP - 1) / STEP;
+    const int spw = span_elems / STEP;
     const int cnt = chunk * spw < nst ? min(spw, nst - chunk * spw) : 0;
     auto stage_of = [&](int i) -> int64_t { return (int64_t)chunk * spw + i; };
-    const int64_t hi = P.V;
+    const int64_t hi = nV;
     const bool aligned = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
     // the row's last stage is partial when STEP does not divide V: it is this workgroup's last, if any
-    const bool last_partial = cnt > 0 && (stage_of(cnt - 1) + 1) * STEP > P.V;
+    const bool last_partial = cnt > 0 && (stage_of(cnt - 1) + 1) * STEP > nV;
     float m = -INFINITY, acc = 0.f;
 
     // Terms are exp(y - m) = exp2((y - m) * log2e): subtract, multiply, v_exp_f32.  y - m is exact
@@ -643,10 +669,10 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
     // flight with counted vmcnt waits instead of draining to vmcnt(0) each stage.
     const int nfull = aligned ? cnt - (last_partial ? 1 : 0) : 0;
     // the row's ragged last stage (aligned rows): one clamped vector per lane, loaded up front
-    const bool vtail = aligned && last_partial && P.V >= VEC;
+    const bool vtail = aligned && last_partial && nV >= VEC;
     const int64_t tail_e0 = vtail ? stage_of(cnt - 1) * STEP + threadIdx.x * VEC : 0;
     uint4 tailv = make_uint4(0u, 0u, 0u, 0u);
-    if (vtail) tailv = ld16_clamped<DT>(row, tail_e0, last_whole_vec<DT>(P.V));
+    if (vtail) tailv = ld16_clamped<DT>(row, tail_e0, last_whole_vec<DT>(nV));
     if (nfull > 0) {
         // ticket order (large batches): more vectors in flight per span (SD_TICKET_PIPE)
         constexpr int PIPE = TICKET ? kTicketPipe : kPipe;
@@ -678,7 +704,7 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
     }
     if (vtail) {
         float x[VEC];
-        finish16<DT>(tailv, row, tail_e0, P.V, x);
+        finish16<DT>(tailv, row, tail_e0, nV, x);
         consume(x, tail_e0, std::true_type{});
     }
     // misaligned rows: guarded element loads
@@ -752,9 +778,14 @@ __global__ void __launch_bounds__(kThreads) SD_SGPR_CAP k_stats(Plan P, int slot
 #endif
 // TICKET: the ticket-order layout (fused_role; any batch): its own instantiation, so the block-id
 // kernel of small batches carries neither the ticket code nor the multi-chunk samplers' registers
+// The leading scalar parameters are a SpanArgs, field by field (preloaded: 12 SGPRs); the ticket-order
+// instantiation receives them too and reads P alone.
 template <int DT, bool FAST, bool TICKET>
-__global__ void __launch_bounds__(kThreads) SD_SGPR_CAP SD_FUSED_VGPR_CAP k_verify_fused(Plan P, int slot_lo, int slot_cnt) {
-    stats_body<DT, FAST, true, true, TICKET>(P, slot_lo, slot_cnt);
+__global__ void __launch_bounds__(kThreads) SD_SGPR_CAP SD_FUSED_VGPR_CAP
+k_verify_fused(const char* tbase, int64_t slot_stride, int64_t seq_stride, int32_t V, int32_t n_chunks, int32_t chunk,
+               int32_t n_tslots, int32_t xcd_affine, int32_t B, Plan P, int slot_lo, int slot_cnt) {
+    stats_body<DT, FAST, true, true, TICKET>(P, slot_lo, slot_cnt,
+                                             SpanArgs{tbase, slot_stride, seq_stride, V, n_chunks, chunk, n_tslots, xcd_affine, B});
 }
 
 // combine the chunk partials of row r (one wave)
@@ -3006,7 +3037,8 @@ static_assert(2 * sizeof(ResPart) >= 8 * sizeof(float4), "k_draw_lean's line-pad
 // 16-byte aligned.  Same draw and outputs as k_draw, restructured for the latency chain that
 // bounds a 8 MB launch (scripts/microbench/draw_shapes.hip: a bare span pass over the same rows
 // takes 3.5 us):
-//   * a compact kernel-argument block (one scalar-load batch, no hidden-argument division);
+//   * a compact kernel-argument block (no hidden-argument division) whose leading scalars arrive
+//     preloaded in SGPRs, so the row loads wait for no scalar load (DrawLeanRest below);
 //   * spans of NST x 2048 elements, every vector in flight at once, no per-element tests except
 //     in a row's ragged last span;
 //   * the thread holding the span's candidate stores the partial itself (no candidate barrier)
@@ -3032,6 +3064,36 @@ struct DrawLean {
     int32_t* status_or;   // the caller's sticky error word (nullable)
     uint64_t* ts;         // phase timestamps (SD_PHASE_TIMING builds only)
 };
+
+// How k_draw_lean receives a DrawLean.  gfx950 delivers leading scalar kernel parameters in SGPRs
+// before the wave starts (kernel-argument preload: the unit is compiled with
+// -amdgpu-kernarg-preload-count, Makefile), but only flat scalars, never a struct passed by value.
+// So what the first row load depends on (rows, stride_bytes, V, n_span) and what wave 0 needs beside
+// the loads (cnt, poll, the Philox seed / offset / offset_dev) are leading parameters, 16 dwords, and
+// the remaining fields follow as one by-value struct the kernel reads by the usual scalar loads.
+struct DrawLeanRest {
+    float4* part;
+    int64_t* next_token;
+    int64_t nt_stride;
+    float* token_prob;
+    float2* row_stats;
+    int32_t* row_status;
+    int64_t* words_used;
+    const uint32_t* noise_words;   // sd_noise without seed, offset, offset_dev
+    int64_t noise_n_words;
+    int64_t noise_row_base;
+    int32_t noise_mode;
+    int32_t pstride;
+    int32_t spin_limit;
+    int32_t* status_or;
+    uint64_t* ts;
+};
+
+__device__ __host__ __forceinline__ DrawLeanRest draw_lean_rest(const DrawLean& A) {
+    return DrawLeanRest{A.part, A.next_token, A.nt_stride, A.token_prob, A.row_stats, A.row_status, A.words_used,
+                        A.noise.words, A.noise.n_words, A.noise.row_base, A.noise.mode,
+                        A.pstride, A.spin_limit, A.status_or, A.ts};
+}
 
 // phase timestamps of k_draw_lean (diagnostic builds): slot wg = r * n_span + c
 #ifdef SD_PHASE_TIMING
@@ -3129,8 +3191,18 @@ __device__ __forceinline__ uint4 lean_finish16(uint4 w, const char* row, int64_t
 }
 
 template <int DT, int NST, bool GREEDY = false>
-__global__ void __launch_bounds__(kThreads) k_draw_lean(DrawLean A) {
+__global__ void __launch_bounds__(kThreads)
+k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, uint32_t* cnt, int32_t poll,
+            uint64_t seed, uint64_t offset, const uint64_t* offset_dev, DrawLeanRest R) {
     constexpr int VEC = 8, STEP = kThreads * VEC, EPT = NST * VEC, NW = kThreads / kWave;
+    // the launcher's DrawLean again: the leading fields from the (preloaded) parameters
+    DrawLean A;
+    A.rows = rows; A.stride_bytes = stride_bytes; A.V = V; A.n_span = n_span; A.cnt = cnt; A.poll = poll;
+    A.part = R.part; A.next_token = R.next_token; A.nt_stride = R.nt_stride; A.token_prob = R.token_prob;
+    A.row_stats = R.row_stats; A.row_status = R.row_status; A.words_used = R.words_used;
+    A.noise.mode = R.noise_mode; A.noise.words = R.noise_words; A.noise.n_words = R.noise_n_words;
+    A.noise.seed = seed; A.noise.offset = offset; A.noise.row_base = R.noise_row_base; A.noise.offset_dev = offset_dev;
+    A.pstride = R.pstride; A.spin_limit = R.spin_limit; A.status_or = R.status_or; A.ts = R.ts;
     // (XCD-affine placement of a row's spans measured slower, 6.6 vs 6.4 us: plain grid order)
     const int c = blockIdx.x, r = blockIdx.y;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -3546,7 +3618,7 @@ void policy_init() {
 
 // Dispatch options (sd_set_option), indexed by sd_option; relaxed reads on every call.
 std::atomic<int> g_opt_fused{1}, g_opt_lean{-1}, g_opt_thr_poll{1}, g_opt_draw_stream{1}, g_opt_ticket{-1};
-std::atomic<int> g_opt_draw_span{0}, g_opt_ticket_lag{0}, g_opt_samp_chunks{0};
+std::atomic<int> g_opt_draw_span{0}, g_opt_ticket_lag{0}, g_opt_samp_chunks{0}, g_opt_arg_fast{1};
 // k_draw_lean: batches above kDrawSpan4MinB take 4 stages per workgroup (measured round 6, packed
 // registers: B = 128 one stage 12.9 us, two 13.7, four 13.3; B = 512 four 33.5, one 38.7)
 constexpr int kDrawSpan4MinB = 128;
@@ -3555,6 +3627,7 @@ std::atomic<int>* option_slot(int32_t opt) {
         case SD_OPT_DRAW_SPAN: return &g_opt_draw_span;
         case SD_OPT_TICKET_LAG: return &g_opt_ticket_lag;
         case SD_OPT_SAMP_CHUNKS: return &g_opt_samp_chunks;
+        case SD_OPT_ARG_FAST: return &g_opt_arg_fast;
         case SD_OPT_FUSED_VERIFY: return &g_opt_fused;
         case SD_OPT_FUSED_TICKET: return &g_opt_ticket;
         case SD_OPT_LEAN_VERIFY: return &g_opt_lean;
@@ -3685,7 +3758,7 @@ int resident_cap(const void* kern, int threads, size_t dyn) {
 }
 
 // the fused kernel of P's dtype and FAST case, in block-id or ticket order
-using FusedKernel = void (*)(sd::Plan, int, int);
+using FusedKernel = void (*)(const char*, int64_t, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, sd::Plan, int, int);
 FusedKernel fused_kernel(const sd::Plan& P, bool ticket) {
     return dispatch_dtype(P.tdt, [&](auto dt_) {
         return dispatch_bool(P.fast(), [&](auto fast_) {
@@ -3694,6 +3767,24 @@ FusedKernel fused_kernel(const sd::Plan& P, bool ticket) {
             });
         });
     });
+}
+
+// k_verify_fused's leading parameters.  Uniform layout (tbase set): 16-bit target rows, 16-byte aligned,
+// whose slots trow[0 .. n_tslots) lie at one constant non-negative spacing — views tl[:, t, :] of one
+// [B, T, V] or [T, B, V] tensor, or one tensor for every slot (spacing 0).  Anything else, or
+// SD_OPT_ARG_FAST = 0, passes a null base and the kernel looks the row up in P.trow.
+sd::SpanArgs span_args(const sd::Plan& P) {
+    const int64_t esz = P.tdt == SD_F32 ? 4 : 2;
+    sd::SpanArgs fa{nullptr, 0, P.tstride * esz, P.V, P.n_chunks, P.chunk, P.n_tslots, P.xcd_affine, P.B};
+    if (opt(g_opt_arg_fast) == 0 || P.tdt == SD_F32 || P.n_tslots < 1) return fa;
+    const char* base = static_cast<const char*>(P.trow[0]);
+    const int64_t d = P.n_tslots > 1 ? static_cast<const char*>(P.trow[1]) - base : 0;
+    if (d < 0 || (d & 15) || (reinterpret_cast<uintptr_t>(base) & 15) || (fa.seq_stride & 15)) return fa;
+    for (int t = 2; t < P.n_tslots; ++t)
+        if (static_cast<const char*>(P.trow[t]) - static_cast<const char*>(P.trow[t - 1]) != d) return fa;
+    fa.tbase = base;
+    fa.slot_stride = d;
+    return fa;
 }
 
 // The whole perf-mode verify of stochastic target rows in ONE launch (k_stats<.., TAIL, SAMP>): the
@@ -3707,7 +3798,10 @@ int32_t launch_fused(const sd::Plan& P, void* stream) {
     const int64_t total = P.ticket ? seqs * (P.n_tslots * P.n_chunks + 1 + P.n_samp) : head + (int64_t)P.B * P.n_samp;
     sd::Plan Q = P;
     Q.kpoll = 1;
-    const int32_t st = launch(fused_kernel(P, P.ticket != 0), dim3((uint32_t)total), dim3(kThreads), 0, stream, Q, 0, P.n_tslots);
+    const sd::SpanArgs fa = span_args(P);
+    const int32_t st = launch(fused_kernel(P, P.ticket != 0), dim3((uint32_t)total), dim3(kThreads), 0, stream, fa.tbase,
+                              fa.slot_stride, fa.seq_stride, fa.V, fa.n_chunks, fa.chunk, fa.n_tslots, fa.xcd_affine, fa.B,
+                              Q, 0, P.n_tslots);
     return st == SD_OK ? 1 : st;
 }
 
@@ -3865,7 +3959,8 @@ int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
     A.spin_limit = P.spin_limit;
     A.status_or = P.status_or;
     A.ts = P.ts;
-    return launch(k_draw_lean<DT, NST, GREEDY>, dim3(A.n_span, P.B), dim3(kThreads), 0, stream, A);
+    return launch(k_draw_lean<DT, NST, GREEDY>, dim3(A.n_span, P.B), dim3(kThreads), 0, stream, A.rows, A.stride_bytes,
+                  A.V, A.n_span, A.cnt, A.poll, A.noise.seed, A.noise.offset, A.noise.offset_dev, draw_lean_rest(A));
 }
 
 // The one-launch verify of a few sequences (sd_verify_lean.inc): 1 launched, 0 not applicable (the
