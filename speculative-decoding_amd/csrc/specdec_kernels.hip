@@ -352,7 +352,15 @@ __device__ __forceinline__ void pf_late(const Plan& P, int b, int i, DraftPf& pf
 }
 template <int DT = -1, bool FAST = false>
 __device__ __forceinline__ void decide_seq(const Plan& P, int b, const DraftPf& pf, int wg_id, Decision* out = nullptr,
-                           bool publish = true, bool coh = true, const uint32_t* poll_epoch = nullptr);
+                           bool publish = true, bool coh = true, const uint32_t* poll_epoch = nullptr,
+                           bool sampler_recs = false);
+
+// Tag of the fused verify's decision record k (0 / 1) of sequence b (fused_sampler polls for them)
+__device__ __forceinline__ uint32_t dec_tag(uint32_t epoch, int b, int k) {
+    uint32_t h = epoch * 0x9E3779B1u + (uint32_t)b * 0x85EBCA77u + (uint32_t)k * 0xC2B2AE3Du + 0x1B873593u;
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;   // murmur3 fmix32
+    return h | 1u;
+}
 
 // Poll-mode tag of k_stats' partial record (slot s, chunk c) of sequence b (k_draw_lean's protocol,
 // its own salt; the sequence's epoch lives in counter set 3, shared with k_sample's finish)
@@ -428,6 +436,9 @@ __device__ __forceinline__ void fused_role(int t, int nb, int D, int per_seq, in
 
 #ifndef SD_TAIL_PRIO
 #define SD_TAIL_PRIO 1   // s_setprio for the draws' tail wave and the fused verify's decider (B = 32 step -0.35 us)
+#endif
+#ifndef SD_DEC_RECS_FIRST
+#define SD_DEC_RECS_FIRST 1   // fused verify: the decider's lane sends the samplers' decision records before its bookkeeping
 #endif
 constexpr int kMaxSampPairs = 4;   // chunk pairs per fused sampler in ticket order: samp_cps <= 8
 #ifndef SD_SAMP_PREFETCH
@@ -562,7 +573,7 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
         if constexpr (SAMP) {
             __shared__ Decision s_dec;
             const double u_row = uniform_d(cdf_uniform(P.noise, (uint32_t)b));   // the chunk pick's, ahead of the records
-            decide_seq<DT, FAST>(P, b, pf, wg_id, &s_dec, true, true, &s_epoch);
+            decide_seq<DT, FAST>(P, b, pf, wg_id, &s_dec, true, true, &s_epoch, SD_DEC_RECS_FIRST != 0);
             __syncthreads();
             SD_TS(wg_id, 3);
             fused_finish<DT, FAST>(P, b, s_dec, s_epoch, wg_id, u_row);
@@ -1286,7 +1297,7 @@ __device__ __forceinline__ void draft_ratio(const Plan& P, int b, int i, const D
 // (wave 0; lane 0 builds the Decision, carrying the sampled rows' (m, S) from lstat).
 __device__ __forceinline__ void walk_decision(const Plan& P, int b, const uint8_t* lacc, const uint8_t* lstop, bool act,
                                               const float2* lstat, Decision* out, bool publish,
-                                              int32_t extra_status = 0) {
+                                              int32_t extra_status = 0, const uint32_t* rec_epoch = nullptr) {
     const int lane = threadIdx.x & 63;
     if (threadIdx.x < kWave) {
         const int g = P.gamma;
@@ -1352,6 +1363,16 @@ __device__ __forceinline__ void walk_decision(const Plan& P, int b, const uint8_
             d.mst = lstat[d.slot];
             d.msd = d.mode == kModeResid && !P.draft_is_probs ? lstat[P.n_tslots + d.slot] : make_float2(0.f, 1.f);
         }
+        if (rec_epoch) {
+            // fused verify: the two records the sequence's samplers are polling for leave first, from
+            // registers (a wave's stores drain in order: behind the bookkeeping below they left ~12
+            // stores later); mode / slot sanitised as fused_finish does
+            const bool none = d.mode <= kModeNone || d.mode > kModePRow || d.slot < 0 || d.slot >= P.n_tslots;
+            const uint32_t mslot = none ? (uint32_t)kModeNone : (uint32_t)(d.mode & 0xff) | ((uint32_t)d.slot << 8);
+            const uint32_t ep = *rec_epoch;
+            st_coh16(P.drec + 2 * b, make_uint4(mslot, __float_as_uint(d.mst.x), __float_as_uint(d.mst.y), dec_tag(ep, b, 0)));
+            st_coh16(P.drec + 2 * b + 1, make_uint4(__float_as_uint(d.msd.x), __float_as_uint(d.msd.y), 0u, dec_tag(ep, b, 1)));
+        }
         if (out) *out = d;
         if (publish) {
             publish_decision(P, b, d);
@@ -1372,7 +1393,7 @@ __device__ __forceinline__ void walk_decision(const Plan& P, int b, const uint8_
 // path is compiled (a shorter, branch-free critical path after the records)
 template <int DT, bool FAST>
 __device__ __forceinline__ void decide_seq(const Plan& P, int b, const DraftPf& pf, int wg_id, Decision* out, bool publish, bool coh,
-                           const uint32_t* poll_epoch) {
+                           const uint32_t* poll_epoch, bool sampler_recs) {
     __shared__ float2 lstat[2 * SD_MAX_GAMMA + 1];
     __shared__ float lp[SD_MAX_GAMMA], lq[SD_MAX_GAMMA];
     __shared__ uint8_t lacc[SD_MAX_GAMMA], lstop[SD_MAX_GAMMA];
@@ -1461,7 +1482,7 @@ __device__ __forceinline__ void decide_seq(const Plan& P, int b, const DraftPf& 
 #pragma unroll
         for (int k = 0; k < kThreads / kWave; ++k) xs |= s_lost[k];
         walk_decision(P, b, lacc, lstop, pf.act, lstat, out, publish,
-                      xs ? SD_ROW_EXCHANGE_TIMEOUT | SD_ROW_INVALID_DIST : 0);
+                      xs ? SD_ROW_EXCHANGE_TIMEOUT | SD_ROW_INVALID_DIST : 0, sampler_recs ? poll_epoch : nullptr);
         SD_TS(wg_id, 5);
         return;
     } else {
@@ -1876,7 +1897,7 @@ __device__ __forceinline__ void pick_wave(const Plan& P, int b, const Decision& 
 // Outputs of sequence b (one thread): token, mass, engine state (engine/infer_engine.py:307-336
 // applied in place), row status with the threshold flags.
 __device__ void finalize_write(const Plan& P, int b, const Decision& d, int64_t x, float mass, int32_t status,
-                               int64_t acc0, const int64_t* lstops = nullptr) {
+                               int64_t acc0, int64_t rc0, int64_t rc1, const int64_t* lstops = nullptr) {
     const int g = P.gamma;
     P.next_token[b * P.next_token_stride] = x;
     if (P.resample_mass) P.resample_mass[b] = mass;
@@ -1900,10 +1921,25 @@ __device__ void finalize_write(const Plan& P, int b, const Decision& d, int64_t 
         for (int s2 = P.n_tslots; s2 < P.slots; ++s2) status |= keep_of(P, b * P.slots + s2).flags;
     P.row_status[b] = status;
     flag_error(P.status_or, status);
-    if (P.row_counts && (status & SD_ROW_DONE)) {   // one writer per row per call (stream-ordered calls)
+    // one writer per row per call (stream-ordered calls): the caller fetched the row's counts (rc0, rc1:
+    // finalize_early) ahead of the pick, so the launch does not end on a load
+    if (P.row_counts && (status & SD_ROW_DONE)) {
         int64_t* rc = P.row_counts + 2 * (int64_t)b;
-        rc[0] += d.n;
-        rc[1] += d.n + (d.mode != kModeNone && x >= 0 ? 1 : 0);
+        rc[0] = rc0 + d.n;
+        rc[1] = rc1 + d.n + (d.mode != kModeNone && x >= 0 ? 1 : 0);
+    }
+}
+
+// finalize_write's engine-state and counter inputs of sequence b (its one thread), loaded early.  DONE
+// is the decision's bit: no later step sets or clears it
+__device__ __forceinline__ void finalize_early(const Plan& P, int b, const Decision& d, int64_t& acc0, int64_t& rc0,
+                                               int64_t& rc1) {
+    acc0 = rc0 = rc1 = 0;
+    if (!(d.status & SD_ROW_DONE)) return;
+    if (P.rule == SD_RULE_ENGINE && P.generated != nullptr) acc0 = P.accepted_count[b];
+    if (P.row_counts) {
+        rc0 = P.row_counts[2 * (int64_t)b];
+        rc1 = P.row_counts[2 * (int64_t)b + 1];
     }
 }
 
@@ -1914,11 +1950,10 @@ __global__ void __launch_bounds__(64) k_finalize(Plan P) {
     int64_t x = -1;
     float mass = NAN;
     int32_t status = d.status;
+    int64_t acc0 = 0, rc0 = 0, rc1 = 0;
+    if (threadIdx.x == 0) finalize_early(P, b, d, acc0, rc0, rc1);
     if (d.mode != kModeNone && !(status & SD_ROW_NOISE_OVERRUN)) pick_wave(P, b, d, x, mass, status);
-    if (threadIdx.x == 0) {
-        const bool engine_state = P.rule == SD_RULE_ENGINE && P.generated != nullptr;
-        finalize_write(P, b, d, x, mass, status, engine_state && (status & SD_ROW_DONE) ? P.accepted_count[b] : 0);
-    }
+    if (threadIdx.x == 0) finalize_write(P, b, d, x, mass, status, acc0, rc0, rc1);
 }
 
 // ------------------------------------------------------------------ k_sample (PHILOX / perf mode)
@@ -2188,9 +2223,8 @@ template <int TDT, int DDT, bool FAST, bool STOCH, int EPT = 8>
 __device__ __forceinline__ void sample_finish(const Plan& P, const Decision& d, int b, PairRows R, double u_row,
                                               int wg_id, const uint32_t* poll_epoch = nullptr) {
     constexpr int VEC = PairVec<TDT, DDT>::kVec, NV = EPT / VEC;
-    const bool engine_state = P.rule == SD_RULE_ENGINE && P.generated != nullptr;
-    int64_t acc0 = 0;
-    if (threadIdx.x == 0 && engine_state && (d.status & SD_ROW_DONE)) acc0 = P.accepted_count[b];   // early
+    int64_t acc0 = 0, rc0 = 0, rc1 = 0;
+    if (threadIdx.x == 0) finalize_early(P, b, d, acc0, rc0, rc1);   // early: the finish then only stores
     // the stop list into registers now, into LDS after the partials' loads are issued (one round trip)
     __shared__ int64_t lstops[kLdsStops];   // read by thread 0 at the end
     const bool stop_lane = threadIdx.x < P.n_stop && threadIdx.x < kLdsStops;
@@ -2282,7 +2316,7 @@ __device__ __forceinline__ void sample_finish(const Plan& P, const Decision& d, 
         __syncthreads();
         status |= s_xstat;
     }
-    if (threadIdx.x == 0) finalize_write(P, b, d, x, mass, status, acc0, lstops);
+    if (threadIdx.x == 0) finalize_write(P, b, d, x, mass, status, acc0, rc0, rc1, lstops);
     SD_TS(wg_id, 6);
 }
 
@@ -2403,12 +2437,6 @@ __global__ void __launch_bounds__(kThreads) SD_SGPR_CAP k_sample(Plan P) {
 #endif
 constexpr int kFusedEpt = 8;                       // k_sample's chunking: 2048-element chunks, the same draws
 
-__device__ __forceinline__ uint32_t dec_tag(uint32_t epoch, int b, int k) {
-    uint32_t h = epoch * 0x9E3779B1u + (uint32_t)b * 0x85EBCA77u + (uint32_t)k * 0xC2B2AE3Du + 0x1B873593u;
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;   // murmur3 fmix32
-    return h | 1u;
-}
-
 // pair_weights_from's FAST weights of one 16-bit vector pair (T = 1, no processor, drafter logits),
 // the same values and psum order, with the row's mode (RESID) and the chunk's raggedness (WHOLE:
 // every element inside the vocabulary) out of the element loop
@@ -2478,6 +2506,173 @@ __device__ __forceinline__ void fused_weights(const PairRows& R, int cc, int rch
     } else {
         if (whole) fused_weights_v<DT, false, true>(R, e0, rt, rd, w, psum);
         else fused_weights_v<DT, false, false>(R, e0, rt, rd, w, psum);
+    }
+}
+
+#ifndef SD_SAMP_TOTALS_FIRST
+// 1: a block-id sampler publishes both chunks' totals records before either in-chunk walk (fused_pair_pick).
+// Parked: equal outputs, 73 VGPRs / 78 SGPRs, but the B = 32 step is 0.85 us slower with it
+#define SD_SAMP_TOTALS_FIRST 0
+#endif
+// A block-id sampler's chunk pair (c0, c0 + 1; has1: the second exists) from the four packed vectors
+// (whole workgroup, split records): both chunks' totals first — the finisher can pick the chunk only
+// once every chunk's totals record is in, and needs one candidate after that — then the two in-chunk
+// walks and the candidate records.  It is chunk_pick_tot twice with the steps interleaved: the same
+// per-thread fp64 sums, DPP scans, cross-wave order, intervals and fallbacks, so the same records;
+// one barrier per step serves both chunks (two instead of four).  No thread keeps its weights: the
+// hit lane recomputes its own from the still-packed vectors with the instruction sequence that summed
+// them, as k_draw_lean's claiming lane does; the rounding fallback's last positive element is looked
+// for only when no lane was hit.
+template <int DT>
+__device__ __forceinline__ void fused_pair_pick(const Plan& P, const PairRows& R, int b, int c0, bool has1, int64_t e0,
+                                                int64_t e1, uint4 t0, uint4 d0, uint4 t1, uint4 d1, double u0, double u1,
+                                                uint32_t ep, int wg_id) {
+    constexpr int EPT = kFusedEpt, NW = kThreads / kWave;
+    __shared__ double s_wtot[2][NW];
+    __shared__ float s_ptot[2][NW];
+    __shared__ int s_pos[2][NW], s_lastp[2][NW];
+    __shared__ double2 s_iv0[kThreads];
+    __shared__ uint8_t s_have0[kThreads];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nc = has1 ? 2 : 1;
+    // Chunk 0: the thread's fp64 total and the wave scan; its interval and its positive-total flag wait in
+    // LDS (17 bytes per thread, read back by the thread that wrote them), so only the packed vectors of
+    // chunk 0 are live while chunk 1's weights are formed.  (The kernel's static LDS must stay <= 20 KiB:
+    // above that the compiler sees fewer than 8 waves per SIMD and drops the SGPR cap, SD_SGPR_CAP.)
+    {
+        float wv[EPT], psum;
+        fused_weights<DT>(R, c0, P.rchunk, e0, t0, d0, wv, psum);
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) tot += (double)wv[k];
+        s_have0[threadIdx.x] = tot > 0.0 ? 1 : 0;
+        const double wincl = wave_incl_scan_d(tot);
+        const double excl = dpp_d<0x138, 0xF, true>(0.0, wincl);   // wave_shr:1 -> the previous lane's inclusive
+        const float wp = wave_sum(psum);
+        s_iv0[threadIdx.x] = make_double2(excl, wincl);
+        if (lane == 63) {
+            s_wtot[0][w] = wincl;
+            s_ptot[0][w] = wp;
+        }
+    }
+    // the walks recompute the weights: opaque vectors, or the compiler keeps the summed values alive
+    asm volatile("" : "+v"(t0.x), "+v"(t0.y), "+v"(t0.z), "+v"(t0.w), "+v"(d0.x), "+v"(d0.y), "+v"(d0.z), "+v"(d0.w));
+    __builtin_amdgcn_sched_barrier(0);   // chunk 0's work is not to be interleaved with chunk 1's (registers)
+    // Chunk 1: its packed vectors stay in registers for the walk
+    uint32_t have1 = 0u;   // (a VGPR, like chunk 0's flag in LDS: the SGPR budget is 80)
+    double excl1 = 0.0, end1 = 0.0;
+    if (has1) {
+        float wv[EPT], psum;
+        fused_weights<DT>(R, c0 + 1, P.rchunk, e1, t1, d1, wv, psum);
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) tot += (double)wv[k];
+        have1 = tot > 0.0 ? 1u : 0u;
+        end1 = wave_incl_scan_d(tot);
+        excl1 = dpp_d<0x138, 0xF, true>(0.0, end1);
+        const float wp = wave_sum(psum);
+        if (lane == 63) {
+            s_wtot[1][w] = end1;
+            s_ptot[1][w] = wp;
+        }
+        asm volatile("" : "+v"(t1.x), "+v"(t1.y), "+v"(t1.z), "+v"(t1.w), "+v"(d1.x), "+v"(d1.y), "+v"(d1.z), "+v"(d1.w));
+    }
+    SD_TS(wg_id, 8);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (j < nc) {
+            double T = 0.0, woff = 0.0;
+            float PT = 0.f;
+#pragma unroll
+            for (int k = 0; k < NW; ++k) {
+                if (k == w) woff = T;
+                T += s_wtot[j][k];
+                PT += s_ptot[j][k];
+            }
+            if (threadIdx.x == 0)
+                st_coh16(P.sprec + (int64_t)b * P.rn_chunks + c0 + j,
+                         make_uint4(__float_as_uint((float)T), __float_as_uint(PT), 0xffffffffu, sample_tag(ep, b, c0 + j)));
+            const double t = (j ? u1 : u0) * T;
+            double excl, end;
+            if (j == 0) {
+                const double2 iv = s_iv0[threadIdx.x];
+                excl = iv.x + woff;
+                end = woff + iv.y;
+            } else {
+                excl = excl1 + woff;
+                end = woff + end1;
+            }
+            const bool pos_t = (j ? have1 : (uint32_t)s_have0[threadIdx.x]) != 0u;   // the thread's own total is positive
+            const bool hit = pos_t && excl <= t && t < end;
+            const uint64_t hm = __ballot(hit);
+            // Only the hit lane walks here (a divergent recompute costs its whole wave the weights' VALU
+            // work: with every wave's last positive lane walking too, as chunk_pick_tot has it for the
+            // rounding fallback, the samplers' burst doubled and the step lost 1.9 us).  The fallback's
+            // last positive element is found below, if ever it is needed.
+            if (hit) {
+                float wv[EPT], ps;
+                fused_weights<DT>(R, c0 + j, P.rchunk, j ? e1 : e0, j ? t1 : t0, j ? d1 : d0, wv, ps);   // as summed
+                int mypos = INT_MAX, lastp = -1;
+                double run = excl;
+#pragma unroll
+                for (int k = 0; k < EPT; ++k) {
+                    run += (double)wv[k];
+                    if (wv[k] > 0.f) {
+                        lastp = threadIdx.x * EPT + k;
+                        if (run > t && mypos == INT_MAX) mypos = threadIdx.x * EPT + k;
+                    }
+                }
+                s_pos[j][w] = mypos != INT_MAX ? mypos : lastp;   // the hit thread's own rounding fallback
+            }
+            if (lane == 0 && !hm) s_pos[j][w] = INT_MAX;
+        }
+    }
+    __syncthreads();
+    SD_TS(wg_id, 9);
+    int pos[2] = {0, 0};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (j < nc) {
+            pos[j] = INT_MAX;
+#pragma unroll
+            for (int k = 0; k < NW; ++k) pos[j] = s_pos[j][k] < pos[j] ? s_pos[j][k] : pos[j];
+        }
+    }
+    if (pos[0] == INT_MAX || pos[1] == INT_MAX) {   // uniform, rare
+        // rounding left t at/after the running total's end (or the chunk has no positive weight): the
+        // chunk's last positive element, from each wave's last positive lane
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j < nc && pos[j] == INT_MAX) {
+                const uint64_t lm = __ballot((j ? have1 : (uint32_t)s_have0[threadIdx.x]) != 0u);
+                if (lm && lane == 63 - __builtin_clzll(lm)) {
+                    float wv[EPT], ps;
+                    fused_weights<DT>(R, c0 + j, P.rchunk, j ? e1 : e0, j ? t1 : t0, j ? d1 : d0, wv, ps);
+                    int lastp = -1;
+#pragma unroll
+                    for (int k = 0; k < EPT; ++k)
+                        if (wv[k] > 0.f) lastp = threadIdx.x * EPT + k;
+                    s_lastp[j][w] = lastp;
+                }
+                if (lane == 0 && !lm) s_lastp[j][w] = -1;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j < nc && pos[j] == INT_MAX) {
+                int lp = -1;
+#pragma unroll
+                for (int k = 0; k < NW; ++k) lp = s_lastp[j][k] > lp ? s_lastp[j][k] : lp;
+                pos[j] = lp;
+            }
+        }
+    }
+    if ((int)threadIdx.x < nc) {
+        const int j = threadIdx.x, cc = c0 + j, pj = j ? pos[1] : pos[0];
+        const uint32_t cand = (uint32_t)(pj < 0 ? -1 : (int32_t)chunk_elem<DT, DT, EPT>((int64_t)cc * P.rchunk, pj));
+        st_coh16(P.crec + (int64_t)b * P.rn_chunks + cc, make_uint4(cand, 0u, 0u, sample_tag(ep, b, cc) ^ 0x5bd1e995u));
     }
 }
 
@@ -2577,6 +2772,15 @@ __device__ __forceinline__ void fused_sampler(const Plan& P, int b, int c, int w
         // weights and draws run)
         uint4 t0, d0, t1, d1;
         ld_pair(q0, t0, d0, t1, d1);
+        if constexpr (MAXP == 1 && SD_SAMP_TOTALS_FIRST != 0) {
+            // block id (one pair per sampler; every fused launch has split records, sd_verify): both
+            // chunks' totals before either walk
+            const int64_t e0 = (int64_t)(2 * q0) * P.rchunk + tid8;
+            fused_pair_pick<DT>(P, R, b, 2 * q0, 2 * q0 + 1 < P.rn_chunks, e0, e0 + P.rchunk, t0, d0, t1, d1, u0, u1, ep,
+                                wg_id);
+            SD_TS(wg_id, 2);
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < MAXP; ++k) {
             const int q = q0 + k, c0 = 2 * q, c1 = 2 * q + 1;
@@ -2656,7 +2860,7 @@ __device__ __forceinline__ void fused_finish(const Plan& P, int b, const Decisio
                                              double u_row) {
     Decision d = d0;
     if (d.mode < kModeNone || d.mode > kModePRow || d.slot < 0 || d.slot >= P.n_tslots) d.mode = kModeNone;
-    if (threadIdx.x == 0) {
+    if (!SD_DEC_RECS_FIRST && threadIdx.x == 0) {   // else: walk_decision's lane has sent them already
         const uint32_t mslot = (uint32_t)(d.mode & 0xff) | ((uint32_t)(d.mode != kModeNone ? d.slot : 0) << 8);
         st_coh16(P.drec + 2 * b, make_uint4(mslot, __float_as_uint(d.mst.x), __float_as_uint(d.mst.y), dec_tag(epoch, b, 0)));
         st_coh16(P.drec + 2 * b + 1, make_uint4(__float_as_uint(d.msd.x), __float_as_uint(d.msd.y), 0u, dec_tag(epoch, b, 1)));
