@@ -22,6 +22,12 @@
 //                    the partials the mass launches left (the last residual's, or the bonus row's),
 //                    the element from that one chunk, recomputed
 //
+// What the later walks share lives here and in sd_pick.h.  sd_pick.h (vocab_parallel.hip includes it too)
+// holds the draw rule itself: chunk_total / chunk_pick, pick_in_chunk, greedy_over_chunks, chunk_argmax,
+// accept_uniform.  This file adds, for the walks of this translation unit: make_row (the one MultiRow
+// constructor), mass_prev (m_{j-1} from launch j-1's partials), walk_stop_scan (stop scan and status word)
+// and walk_draw (the draw of sd_verify_multi and sd_verify_tree on those pieces).
+//
 // Launch boundaries are the only synchronisation of these kernels: nothing polls, no workgroup waits on
 // another.  (The threshold search of a top-k / nucleus processor, in its launch-per-phase design, counts
 // arrivals in the workspace's counter block and re-arms them, as in every other entry point.)
@@ -57,18 +63,25 @@ struct MultiRow {
     RowKeep kp;
     bool aligned;
 };
+__device__ __forceinline__ RowKeep keep_all() { return RowKeep{-INFINITY, INT_MAX, 0, 0}; }
+// the one constructor (the tree forms' rows are made by it too): the row's first element as
+// (base, element offset), its statistics, its keep predicate
 template <int DT>
-__device__ __forceinline__ MultiRow<DT> multi_row(const Plan& P, int chain, int slot) {
+__device__ __forceinline__ MultiRow<DT> make_row(const void* base, int64_t elem, float2 ms, RowKeep kp) {
     MultiRow<DT> R;
-    const int r = chain * P.slots + slot;
-    R.row = slot < P.n_tslots
-                ? static_cast<const char*>(P.trow[slot]) + (int64_t)chain * P.tstride * Elem<DT>::kBytes
-                : static_cast<const char*>(P.drow[slot - P.n_tslots]) + (int64_t)chain * P.dstride * Elem<DT>::kBytes;
-    R.ms = P.rowstat[r];
-    R.inv = 1.0f / R.ms.y;
-    R.kp = P.t_keep ? keep_of(P, r) : RowKeep{-INFINITY, INT_MAX, 0, 0};
+    R.row = static_cast<const char*>(base) + elem * Elem<DT>::kBytes;
+    R.ms = ms;
+    R.inv = 1.0f / ms.y;
+    R.kp = kp;
     R.aligned = (reinterpret_cast<uintptr_t>(R.row) & 15) == 0;
     return R;
+}
+template <int DT>
+__device__ __forceinline__ MultiRow<DT> multi_row(const Plan& P, int chain, int slot) {
+    const int r = chain * P.slots + slot;
+    const bool target = slot < P.n_tslots;
+    return make_row<DT>(target ? P.trow[slot] : P.drow[slot - P.n_tslots], (int64_t)chain * (target ? P.tstride : P.dstride),
+                        P.rowstat[r], P.t_keep ? keep_of(P, r) : keep_all());
 }
 template <int DT>
 __device__ __forceinline__ float multi_prob(const Plan& P, const MultiRow<DT>& R, float x, int64_t j) {
@@ -123,6 +136,117 @@ __device__ __forceinline__ void multi_weights(const Plan& P, const MultiRow<DT>&
     }
 }
 
+// m_{j-1} (j >= 2) of a row pair or tree slot, into lmass[j - 2]: launch j-1's chunk partials, summed in one
+// fixed order by every workgroup of the pair (`store`: this one also writes it to the mass table); the
+// masses before it come back from the table.  part: the pair's [.][nmc] partials, mtab: its masses
+__device__ __forceinline__ void mass_prev(const float* part, float* mtab, int nmc, int j, bool store, float* lmass,
+                                          float* lds) {
+    part += (int64_t)(j - 2) * nmc;
+    float v = 0.f;
+    for (int c = threadIdx.x; c < nmc; c += kThreads) v += part[c];
+    const float m = block_reduce(v, FSum{}, lds);
+    if (threadIdx.x == 0) {
+        lmass[j - 2] = m;
+        if (store) mtab[j - 2] = m;
+    }
+    if ((int)threadIdx.x < j - 2) lmass[threadIdx.x] = mtab[threadIdx.x];
+}
+
+// ---- the tail the walks share: the exit of a walk is kMultiBonus (every test passed: the token comes
+// from a target row) or kMultiResid (from a residual); kMultiNone once a stop token ends the sequence
+enum { kMultiNone = 0, kMultiBonus = 1, kMultiResid = 2 };
+
+struct WalkLds {              // one per walk kernel, in LDS
+    double target;            // the draw's target inside chunk `sub`
+    int64_t x;                // the drawn token
+    union {                   // the stop scan ends (at a barrier) before the draw begins
+        int32_t rank[SD_MAX_GAMMA];
+        PickLds pick;
+    };
+    int32_t mode, status, stop, sub;
+};
+
+// The stop scan over the n accepted tokens tok_at(0 .. n-1): the stop listed first that occurs, at its
+// first position; then the status word.  L.mode is the walk's exit on entry; a stop resets it to kMultiNone.
+template <class TokAt>
+__device__ __forceinline__ void walk_stop_scan(const Plan& P, WalkLds& L, int n, TokAt tok_at) {
+    const int tid = threadIdx.x;
+    if (tid < n) L.rank[tid] = stop_rank(P, tok_at(tid));
+    __syncthreads();
+    if (tid == 0) {
+        int best = INT_MAX, stop = -1;
+        for (int i = 0; i < n; ++i)
+            if (L.rank[i] < best) { best = L.rank[i]; stop = i; }
+        L.stop = stop;
+        int st = SD_ROW_DONE;
+        if (stop >= 0) { st |= SD_ROW_STOP_IN_DRAFTS; L.mode = kMultiNone; }
+        else st |= L.mode == kMultiBonus ? SD_ROW_BONUS : SD_ROW_RESIDUAL;
+        L.status = st;
+        L.x = -1;
+        L.sub = -1;
+    }
+    __syncthreads();
+}
+struct DrawLds {              // walk_draw's own: the chunk partials staged, the greedy reduction's scratch
+    float lw[kMultiMaxChunks];
+    float bv[kWaves];
+    int32_t bi[kWaves];
+};
+__device__ __forceinline__ bool walk_drawn(const WalkLds& L) {
+    return L.mode != kMultiNone && !(L.status & SD_ROW_INVALID_DIST);
+}
+
+// The draw of sd_verify_multi and sd_verify_tree into L.x: under greedy the argmax over the exit's chunk
+// argmaxes `best`; else by inverse CDF, the chunk from the exit's chunk partials `part` (the last
+// residual's, or a target row's), the element from that one chunk, its weights recomputed from the rows
+// rows(false) (target) and, for a residual, rows(true) (drafter).  A picked chunk without a weighted element
+// leaves L.x = -1.
+template <int DT, class Rows>
+__device__ __forceinline__ void walk_draw(const Plan& P, WalkLds& L, DrawLds& D, int b, int nmc, const float* part,
+                                          const float2* best, bool resid, int nrej, const float* lmass, Rows rows) {
+    const int tid = threadIdx.x;
+    if (!P.t_stoch) {
+        float bv;
+        int32_t bi;
+        greedy_over_chunks(best, nmc, D.bv, D.bi, bv, bi);
+        if (tid == 0) L.x = bi;
+    } else {
+        float* lw = D.lw;
+        for (int c = tid; c < nmc; c += kThreads) lw[c] = part[c];
+        __syncthreads();
+        if (tid == 0) {                                // the chunk the row's uniform falls in
+            const double total = chunk_total(lw, nmc);
+            if (total > 0.0 && total < (double)INFINITY) {
+                double in_chunk;
+                L.sub = chunk_pick(lw, nmc, cdf_uniform(P.noise, (uint32_t)b) * total, &in_chunk);
+                L.target = in_chunk;
+            } else {
+                L.status |= SD_ROW_INVALID_DIST;       // zero / NaN / inf mass: torch.multinomial raises
+            }
+        }
+        __syncthreads();
+        const int pick = L.sub;
+        if (pick >= 0) {                               // the element inside the chunk, weights recomputed
+            const MultiRow<DT> Tr = rows(false);
+            MultiRow<DT> Dr{};
+            const int64_t e0 = (int64_t)pick * kMultiChunk + tid * kMultiEpt;
+            float xt[kMultiEpt], xd[kMultiEpt], wv[kMultiEpt];
+#pragma unroll
+            for (int e = 0; e < kMultiEpt; ++e) xd[e] = 0.f;
+            multi_load<DT>(Tr, e0, P.V, xt);
+            if (resid) {
+                Dr = rows(true);
+                multi_load<DT>(Dr, e0, P.V, xd);
+            }
+            multi_weights<DT>(P, Tr, Dr, resid, nrej - 1, lmass, e0, xt, xd, wv);
+            bool any;
+            const int pe = pick_in_chunk<kMultiEpt>(wv, L.target, L.pick, &any);
+            if (pe >= 0) L.x = e0 + pe;
+        }
+    }
+    __syncthreads();
+}
+
 // launch j (1 .. K+1) of the mass recursion; 1-D grid over (sequence, chain < ka, depth, chunk).
 // Launch 1 has one more depth slot, gamma: the chain's bonus row.
 template <int DT>
@@ -153,18 +277,7 @@ __global__ void __launch_bounds__(kThreads) k_multi_mass(Plan P, Multi M, int j)
 #pragma unroll
         for (int e = 0; e < kMultiEpt; ++e) xd[e] = 0.f;
     }
-    if (j >= 2) {
-        // m_{j-1}: launch j-1's partials, summed in one fixed order by every workgroup of the pair
-        const float* part = M.mpart + (pr * K + (j - 2)) * M.n_mchunks;
-        float v = 0.f;
-        for (int c = threadIdx.x; c < M.n_mchunks; c += kThreads) v += part[c];
-        const float m = block_reduce(v, FSum{}, lds);
-        if (threadIdx.x == 0) {
-            lmass[j - 2] = m;
-            if (chunk == 0) M.mtab[pr * K + (j - 2)] = m;
-        }
-        if ((int)threadIdx.x < j - 2) lmass[threadIdx.x] = M.mtab[pr * K + threadIdx.x];
-    }
+    if (j >= 2) mass_prev(M.mpart + pr * K * M.n_mchunks, M.mtab + pr * K, M.n_mchunks, j, chunk == 0, lmass, lds);
     if (k > K - j) return;                             // this chain needed m_{j-1} only
     __syncthreads();
     float wv[kMultiEpt];
@@ -176,42 +289,28 @@ __global__ void __launch_bounds__(kThreads) k_multi_mass(Plan P, Multi M, int j)
     const int64_t slot = bonus ? (int64_t)chain * M.n_mchunks + chunk : (pr * K + (j - 1)) * M.n_mchunks + chunk;
     if (threadIdx.x == 0) (bonus ? M.bpart : M.mpart)[slot] = s;
     if (!P.t_stoch) {                                  // greedy: the chunk's argmax (NaN first, lowest index)
-        float bv = -INFINITY;
-        int32_t bi = INT_MAX;
-#pragma unroll
-        for (int e = 0; e < kMultiEpt; ++e)
-            if (e0 + e < P.V && arg_better(wv[e], (int32_t)(e0 + e), bv, bi)) { bv = wv[e]; bi = (int32_t)(e0 + e); }
-        block_argmax(bv, bi, lds, ldi);
-        if (threadIdx.x == 0) (bonus ? M.bbest : M.mbest)[slot] = make_float2(bv, __int_as_float(bi));
+        const float2 best = chunk_argmax<kMultiEpt>(wv, e0, P.V, lds, ldi);
+        if (threadIdx.x == 0) (bonus ? M.bbest : M.mbest)[slot] = best;
     }
 }
-
-enum { kMultiNone = 0, kMultiBonus = 1, kMultiResid = 2 };
 
 template <int DT>
 __global__ void __launch_bounds__(kThreads) k_multi_walk(Plan P, Multi M) {
     __shared__ int64_t ltok[kMultiNodes];
     __shared__ float lu[kMultiNodes];
-    __shared__ int32_t lrank[SD_MAX_GAMMA];
     __shared__ float lp[kMultiNodes * kMultiK], lq[kMultiNodes * kMultiK], lm[kMultiNodes * kMultiK];
-    __shared__ float lw[kMultiMaxChunks];
-    __shared__ double ldd[kThreads / kWave];
-    __shared__ int32_t lfirst[kThreads / kWave], llast[kThreads / kWave];
     __shared__ float lmass[kMultiK];
-    __shared__ float ldv[8];
-    __shared__ int32_t ldi[8];
-    __shared__ int32_t s_n, s_winner, s_mode, s_nrej, s_status, s_stop, s_rejects, s_sub;
+    __shared__ WalkLds L;
+    __shared__ DrawLds Dl;
+    __shared__ int32_t s_n, s_winner, s_nrej, s_rejects;
     __shared__ float s_mass;
-    __shared__ double s_target;
-    __shared__ int64_t s_x;
-    const int b = blockIdx.x, K = M.K, g = M.gamma, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x, K = M.K, g = M.gamma, tid = threadIdx.x;
 
     // drafted ids and accept uniforms: node i = d*K + k
     if (tid < K * g) {
         const int d = tid / K, k = tid - d * K;
         ltok[tid] = P.draft_tokens[(int64_t)(b * K + k) * P.tok_stride + d];
-        const uint4 q4 = philox_block(P.noise, (uint32_t)b, kSiteAccept, (uint32_t)(tid >> 2));
-        lu[tid] = uniform_from_word((tid & 3) == 0 ? q4.x : (tid & 3) == 1 ? q4.y : (tid & 3) == 2 ? q4.z : q4.w);
+        lu[tid] = accept_uniform(P.noise, b, tid);
     }
     __syncthreads();
     // p, q of chain k's token under the rows of chain k0 (k >= k0), and the masses of (k0, d)
@@ -255,137 +354,38 @@ __global__ void __launch_bounds__(kThreads) k_multi_walk(Plan P, Multi M) {
         }
         if (mode == kMultiBonus) win = __ffs(A) - 1;
         for (int i = 0; i < nrej; ++i) lmass[i] = lm[(n * K + win) * K + i];
-        s_n = n; s_winner = win; s_mode = mode; s_nrej = nrej; s_rejects = rejects; s_mass = mass;
+        s_n = n; s_winner = win; L.mode = mode; s_nrej = nrej; s_rejects = rejects; s_mass = mass;
     }
     __syncthreads();
     const int n = s_n, win = s_winner;
-    // the stop scan over tok[winner, :n]: the stop listed first that occurs, at its first position
-    if (tid < n) lrank[tid] = stop_rank(P, ltok[tid * K + win]);
-    __syncthreads();
-    if (tid == 0) {
-        int best = INT_MAX, stop = -1;
-        for (int i = 0; i < n; ++i)
-            if (lrank[i] < best) { best = lrank[i]; stop = i; }
-        s_stop = stop;
-        int st = SD_ROW_DONE;
-        if (stop >= 0) { st |= SD_ROW_STOP_IN_DRAFTS; s_mode = kMultiNone; }
-        else st |= s_mode == kMultiBonus ? SD_ROW_BONUS : SD_ROW_RESIDUAL;
-        s_status = st;
-        s_x = -1;
-    }
-    __syncthreads();
-    const int mode = s_mode;
-    if (mode != kMultiNone) {
-        const int nrej = s_nrej, chain = b * K + win, nmc = M.n_mchunks;
-        const bool resid = mode == kMultiResid;
+    walk_stop_scan(P, L, n, [&](int i) { return ltok[i * K + win]; });
+    if (L.mode != kMultiNone) {
         // the chunk partials the mass launches left: the last residual's (launch nrej of pair (win, n)), or
         // the bonus row's
+        const int nrej = s_nrej, chain = b * K + win, nmc = M.n_mchunks;
+        const bool resid = L.mode == kMultiResid;
         const int64_t part0 = resid ? (((int64_t)chain * g + n) * K + (nrej - 1)) * nmc : (int64_t)chain * nmc;
-        if (!P.t_stoch) {                              // greedy: argmax over the chunks' argmaxes
-            const float2* best = (resid ? M.mbest : M.bbest) + part0;
-            float bv = -INFINITY;
-            int32_t bi = INT_MAX;
-            for (int c = tid; c < nmc; c += kThreads) {
-                const float2 v = best[c];
-                if (arg_better(v.x, __float_as_int(v.y), bv, bi)) { bv = v.x; bi = __float_as_int(v.y); }
-            }
-            block_argmax(bv, bi, ldv, ldi);
-            if (tid == 0) s_x = bi;
-        } else {
-            const float* part = (resid ? M.mpart : M.bpart) + part0;
-            for (int c = tid; c < nmc; c += kThreads) lw[c] = part[c];
-            __syncthreads();
-            if (tid == 0) {                            // the chunk the row's uniform falls in
-                double total = 0.0;
-                for (int c = 0; c < nmc; ++c) total += (double)lw[c];
-                int pick = -1;
-                if (total > 0.0 && total < (double)INFINITY) {
-                    const double target = cdf_uniform(P.noise, (uint32_t)b) * total;
-                    double run = 0.0, before = 0.0;
-                    for (int c = 0; c < nmc; ++c) {
-                        const double v = (double)lw[c];
-                        if (v > 0.0) {
-                            pick = c; before = run;
-                            if (run + v > target) break;
-                        }
-                        run += v;
-                    }
-                    s_target = target - before;
-                } else {
-                    s_status |= SD_ROW_INVALID_DIST;   // zero / NaN / inf mass: torch.multinomial raises
-                }
-                s_sub = pick;
-            }
-            __syncthreads();
-            const int pick = s_sub;
-            if (pick >= 0) {                           // the element inside the chunk, weights recomputed
-                const MultiRow<DT> T = multi_row<DT>(P, chain, resid ? n : g);
-                const MultiRow<DT> D = multi_row<DT>(P, chain, P.n_tslots + (resid ? n : 0));   // residual exits only
-                const int64_t e0 = (int64_t)pick * kMultiChunk + tid * kMultiEpt;
-                float xt[kMultiEpt], xd[kMultiEpt], wv[kMultiEpt];
-                multi_load<DT>(T, e0, P.V, xt);
-                if (resid) multi_load<DT>(D, e0, P.V, xd);
-                else {
-#pragma unroll
-                    for (int e = 0; e < kMultiEpt; ++e) xd[e] = 0.f;
-                }
-                multi_weights<DT>(P, T, D, resid, nrej - 1, lmass, e0, xt, xd, wv);
-                double ls = 0.0;
-#pragma unroll
-                for (int e = 0; e < kMultiEpt; ++e) ls += (double)wv[e];
-                double incl = wave_incl_scan_d(ls);
-                if (lane == 63) ldd[w] = incl;
-                __syncthreads();
-                for (int k2 = 0; k2 < w; ++k2) incl += ldd[k2];
-                const double target = s_target;
-                const uint64_t pos = __ballot(ls > 0.0), over = __ballot(ls > 0.0 && incl > target);
-                if (lane == 0) {
-                    lfirst[w] = over ? w * kWave + __ffsll((unsigned long long)over) - 1 : INT_MAX;
-                    llast[w] = pos ? w * kWave + 63 - __clzll((long long)pos) : -1;
-                }
-                __syncthreads();
-                // the first thread whose running total passes the target, else the last with weight
-                int sel = INT_MAX, last = -1;
-                for (int k2 = 0; k2 < kThreads / kWave; ++k2) {
-                    sel = lfirst[k2] < sel ? lfirst[k2] : sel;
-                    last = llast[k2] > last ? llast[k2] : last;
-                }
-                if (sel == INT_MAX) sel = last;
-                if (tid == sel) {
-                    double run = incl - ls;
-                    int pe = 0;
-                    bool done = false;   // the first element whose running total passes, else the last with weight
-#pragma unroll
-                    for (int e = 0; e < kMultiEpt; ++e) {
-                        run += (double)wv[e];
-                        if (wv[e] > 0.f && !done) { pe = e; done = run > target; }
-                    }
-                    s_x = e0 + pe;
-                }
-            }
-        }
-        __syncthreads();
+        walk_draw<DT>(P, L, Dl, b, nmc, (resid ? M.mpart : M.bpart) + part0, (resid ? M.mbest : M.bbest) + part0, resid, nrej,
+                      lmass, [&](bool draft) { return multi_row<DT>(P, chain, draft ? P.n_tslots + n : (resid ? n : g)); });
     }
+    const bool drawn = walk_drawn(L);
     if (tid == 0) {
-        const int st = s_status;
-        const bool drawn = s_mode != kMultiNone && !(st & SD_ROW_INVALID_DIST);
-        const bool pruned = s_mode == kMultiResid;
+        const int st = L.status;
+        const bool pruned = L.mode == kMultiResid;
         P.n_accepted[b] = n;
         M.winner[b] = win;
-        P.next_token[b] = drawn ? s_x : -1;
+        P.next_token[b] = drawn ? L.x : -1;
         if (P.resample_mass) P.resample_mass[b] = s_mass;
         if (M.n_rejects) M.n_rejects[b] = s_rejects;
         if (P.prune_drafter) P.prune_drafter[b] = pruned ? g - n : 0;
         if (P.prune_target) P.prune_target[b] = pruned ? g - n + 1 : 0;
-        if (P.stop_index) P.stop_index[b] = s_stop;
+        if (P.stop_index) P.stop_index[b] = L.stop;
         P.row_status[b] = st;
         flag_error(P.status_or, st);
     }
-    if (M.tokens_out && tid <= g) {
-        const bool drawn = s_mode != kMultiNone && !(s_status & SD_ROW_INVALID_DIST);
+    if (M.tokens_out && tid <= g)
         M.tokens_out[(int64_t)b * M.tokens_out_stride + tid] =
-            tid < n ? ltok[tid * K + win] : (tid == n && drawn ? s_x : M.pad_token);
-    }
+            tid < n ? ltok[tid * K + win] : (tid == n && drawn ? L.x : M.pad_token);
 }
 
 }  // namespace sd

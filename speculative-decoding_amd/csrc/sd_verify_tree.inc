@@ -1,5 +1,9 @@
 // sd_verify_tree.inc — token-tree speculative verification (sd_verify_tree), included by
-// specdec_kernels.hip after sd_verify_multi.inc, whose row, weight and residual helpers it shares.
+// specdec_kernels.hip after sd_verify_multi.inc, whose row, weight and residual helpers, stop scan and draw
+// (walk_stop_scan, walk_draw; the draw rule itself: sd_pick.h) it shares.  The two later tree forms
+// (sd_verify_tree_distinct.inc, sd_verify_tree_dynamic.inc) take from here what all three set up alike: the
+// output block (TreeOut, tree_write_out, tree_out), the argument checks (tree_check_args,
+// tree_check_noise_workspace), the walk's Plan, the child lists, the k_stats groups and launch_tree_stats.
 //
 // N drafted nodes per sequence with arbitrary parents (one topology per call) are verified in one step
 // by recursive rejection sampling down the tree (the rule is spelled out in include/specdec.h and
@@ -34,6 +38,17 @@ constexpr int kTreeC = SD_TREE_MAX_CHILDREN;
 constexpr int kTreeGroup = SD_MAX_GAMMA + 1;        // rows per k_stats Plan
 constexpr int kTreeGroups = 4;                      // <= 2 of target rows, <= 2 of drafter rows
 
+// what both tree forms write per sequence beside the Plan's outputs
+struct TreeOut {
+    int64_t pad_token;
+    int32_t* last_node;
+    int32_t* n_rejects;
+    int32_t* path;
+    int64_t path_stride;
+    int64_t* tokens_out;
+    int64_t tokens_out_stride;
+};
+
 struct Tree {
     int32_t B, N, R;          // R rows per sequence: N+1 target rows, then the internal slots' drafter rows
     int32_t depth, n_int, n_leaf;
@@ -54,27 +69,36 @@ struct Tree {
     float2* mbest;            // greedy: [b][internal][kTreeC][n_mchunks] each chunk's (largest weight, index bits)
     float* bpart;             // [b][leaf][n_mchunks] chunk sums of the leaf's target row's p
     float2* bbest;            // greedy: [b][leaf][n_mchunks] that row's chunk argmax
-    int64_t pad_token;
-    int32_t* last_node;
-    int32_t* n_rejects;
-    int32_t* path;
-    int64_t path_stride;
-    int64_t* tokens_out;
-    int64_t tokens_out_stride;
+    TreeOut out;
 };
 
 // the processed target (draft = false) or drafter row of slot s of sequence b, with its statistics
 template <int DT>
 __device__ __forceinline__ MultiRow<DT> tree_row(const Plan& P, const Tree& T, int b, int s, bool draft) {
-    MultiRow<DT> R;
     const int64_t r = (int64_t)b * T.R + (draft ? T.N + 1 + T.idx[s] : s);
-    R.row = draft ? static_cast<const char*>(T.drow[s]) + (int64_t)b * T.dstride * Elem<DT>::kBytes
-                  : static_cast<const char*>(T.trow[s]) + (int64_t)b * T.tstride * Elem<DT>::kBytes;
-    R.ms = T.rowstat[r];
-    R.inv = 1.0f / R.ms.y;
-    R.kp = P.t_keep ? T.keep[r] : RowKeep{-INFINITY, INT_MAX, 0, 0};
-    R.aligned = (reinterpret_cast<uintptr_t>(R.row) & 15) == 0;
-    return R;
+    return make_row<DT>(draft ? T.drow[s] : T.trow[s], (int64_t)b * (draft ? T.dstride : T.tstride), T.rowstat[r],
+                        P.t_keep ? T.keep[r] : keep_all());
+}
+
+// The outputs of sequence b, by the whole workgroup: the n accepted nodes lpath[0 .. n) (lpath == nullptr:
+// none, the sequence's topology was invalid), their tokens, then the drawn token x when `drawn`
+__device__ __forceinline__ void tree_write_out(const Plan& P, const TreeOut& O, int b, int depth, int n, const int32_t* lpath,
+                                               const int64_t* ltok, bool drawn, int64_t x, int st, float mass, int rejects,
+                                               int stop) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        P.n_accepted[b] = n;
+        O.last_node[b] = n > 0 ? lpath[n - 1] : -1;
+        P.next_token[b] = drawn ? x : -1;
+        if (P.resample_mass) P.resample_mass[b] = mass;
+        if (O.n_rejects) O.n_rejects[b] = rejects;
+        if (P.stop_index) P.stop_index[b] = stop;
+        P.row_status[b] = st;
+        flag_error(P.status_or, st);
+    }
+    if (tid < depth) O.path[(int64_t)b * O.path_stride + tid] = lpath ? lpath[tid] : -1;
+    if (O.tokens_out && tid <= depth)
+        O.tokens_out[(int64_t)b * O.tokens_out_stride + tid] = tid < n ? ltok[lpath[tid]] : (tid == n && drawn ? x : O.pad_token);
 }
 
 // one wave per row of a k_stats group G: its partials combined into row row0 + s of the tree's table
@@ -119,18 +143,8 @@ __global__ void __launch_bounds__(kThreads) k_tree_mass(Plan P, Tree T, int j, i
             multi_load<DT>(Dr, e0, P.V, xd);
         }
     }
-    if (j >= 2) {
-        // m_{j-1}: launch j-1's partials, summed in one fixed order by every workgroup of the slot
-        const float* part = T.mpart + (pr * kTreeC + (j - 2)) * T.n_mchunks;
-        float v = 0.f;
-        for (int c = threadIdx.x; c < T.n_mchunks; c += kThreads) v += part[c];
-        const float m = block_reduce(v, FSum{}, lds);
-        if (threadIdx.x == 0) {
-            lmass[j - 2] = m;
-            if (chunk == 0) T.mtab[pr * kTreeC + (j - 2)] = m;
-        }
-        if ((int)threadIdx.x < j - 2) lmass[threadIdx.x] = T.mtab[pr * kTreeC + threadIdx.x];
-    }
+    if (j >= 2)
+        mass_prev(T.mpart + pr * kTreeC * T.n_mchunks, T.mtab + pr * kTreeC, T.n_mchunks, j, chunk == 0, lmass, lds);
     if (sum_only) return;
     __syncthreads();
     float wv[kMultiEpt];
@@ -142,13 +156,8 @@ __global__ void __launch_bounds__(kThreads) k_tree_mass(Plan P, Tree T, int j, i
     const int64_t slot = bonus ? pr * T.n_mchunks + chunk : (pr * kTreeC + (j - 1)) * T.n_mchunks + chunk;
     if (threadIdx.x == 0) (bonus ? T.bpart : T.mpart)[slot] = sum;
     if (!P.t_stoch) {                                  // greedy: the chunk's argmax (NaN first, lowest index)
-        float bv = -INFINITY;
-        int32_t bi = INT_MAX;
-#pragma unroll
-        for (int e = 0; e < kMultiEpt; ++e)
-            if (e0 + e < P.V && arg_better(wv[e], (int32_t)(e0 + e), bv, bi)) { bv = wv[e]; bi = (int32_t)(e0 + e); }
-        block_argmax(bv, bi, lds, ldi);
-        if (threadIdx.x == 0) (bonus ? T.bbest : T.mbest)[slot] = make_float2(bv, __int_as_float(bi));
+        const float2 best = chunk_argmax<kMultiEpt>(wv, e0, P.V, lds, ldi);
+        if (threadIdx.x == 0) (bonus ? T.bbest : T.mbest)[slot] = best;
     }
 }
 
@@ -157,26 +166,20 @@ __global__ void __launch_bounds__(kThreads) k_tree_walk(Plan P, Tree T) {
     __shared__ int64_t ltok[kTreeNodes];
     __shared__ float lu[kTreeNodes], lp[kTreeNodes], lq[kTreeNodes];
     __shared__ float lm[kTreeSlots * kTreeC];
-    __shared__ int32_t lpath[SD_MAX_GAMMA], lrank[SD_MAX_GAMMA];
-    __shared__ float lw[kMultiMaxChunks];
-    __shared__ double ldd[kThreads / kWave];
-    __shared__ int32_t lfirst[kThreads / kWave], llast[kThreads / kWave];
+    __shared__ int32_t lpath[SD_MAX_GAMMA];
     __shared__ float lmass[kTreeC];
-    __shared__ float ldv[8];
-    __shared__ int32_t ldi[8];
-    __shared__ int32_t s_n, s_slot, s_mode, s_nrej, s_status, s_stop, s_rejects, s_sub;
+    __shared__ WalkLds L;
+    __shared__ DrawLds Dl;
+    __shared__ int32_t s_n, s_slot, s_nrej, s_rejects;
     __shared__ float s_mass;
-    __shared__ double s_target;
-    __shared__ int64_t s_x;
-    const int b = blockIdx.x, N = T.N, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x, N = T.N, tid = threadIdx.x;
 
     // drafted ids, accept uniforms (node i takes the row's accept uniform number i) and p, q of every
     // node's token under its parent slot's rows
     if (tid < N) {
         const int64_t tok = P.draft_tokens[(int64_t)b * P.tok_stride + tid];
         ltok[tid] = tok;
-        const uint4 q4 = philox_block(P.noise, (uint32_t)b, kSiteAccept, (uint32_t)(tid >> 2));
-        lu[tid] = uniform_from_word((tid & 3) == 0 ? q4.x : (tid & 3) == 1 ? q4.y : (tid & 3) == 2 ? q4.z : q4.w);
+        lu[tid] = accept_uniform(P.noise, b, tid);
         float p = 0.f, q = 0.f;
         if (tok >= 0 && tok < P.V) {
             const int s = T.parent[tid] + 1;
@@ -212,135 +215,22 @@ __global__ void __launch_bounds__(kThreads) k_tree_walk(Plan P, Tree T) {
             s = hit + 1;
         }
         for (int i = 0; i < nrej; ++i) lmass[i] = lm[T.idx[s] * kTreeC + i];
-        s_n = n; s_slot = s; s_mode = mode; s_nrej = nrej; s_rejects = rejects; s_mass = mass;
+        s_n = n; s_slot = s; L.mode = mode; s_nrej = nrej; s_rejects = rejects; s_mass = mass;
     }
     __syncthreads();
     const int n = s_n, slot = s_slot;
-    // the stop scan over the path's tokens: the stop listed first that occurs, at its first position
-    if (tid < n) lrank[tid] = stop_rank(P, ltok[lpath[tid]]);
-    __syncthreads();
-    if (tid == 0) {
-        int best = INT_MAX, stop = -1;
-        for (int i = 0; i < n; ++i)
-            if (lrank[i] < best) { best = lrank[i]; stop = i; }
-        s_stop = stop;
-        int st = SD_ROW_DONE;
-        if (stop >= 0) { st |= SD_ROW_STOP_IN_DRAFTS; s_mode = kMultiNone; }
-        else st |= s_mode == kMultiBonus ? SD_ROW_BONUS : SD_ROW_RESIDUAL;
-        s_status = st;
-        s_x = -1;
-    }
-    __syncthreads();
-    const int mode = s_mode;
-    if (mode != kMultiNone) {
-        const int nrej = s_nrej, nmc = T.n_mchunks;
-        const bool resid = mode == kMultiResid;
+    walk_stop_scan(P, L, n, [&](int i) { return ltok[lpath[i]]; });
+    if (L.mode != kMultiNone) {
         // the chunk partials the mass launches left: the last residual's (launch nrej of the slot), or the
         // leaf's target row's
+        const int nrej = s_nrej, nmc = T.n_mchunks;
+        const bool resid = L.mode == kMultiResid;
         const int64_t part0 = resid ? ((((int64_t)b * T.n_int + T.idx[slot]) * kTreeC) + (nrej - 1)) * nmc
                                     : ((int64_t)b * T.n_leaf + T.idx[slot]) * nmc;
-        if (!P.t_stoch) {                              // greedy: argmax over the chunks' argmaxes
-            const float2* best = (resid ? T.mbest : T.bbest) + part0;
-            float bv = -INFINITY;
-            int32_t bi = INT_MAX;
-            for (int c = tid; c < nmc; c += kThreads) {
-                const float2 v = best[c];
-                if (arg_better(v.x, __float_as_int(v.y), bv, bi)) { bv = v.x; bi = __float_as_int(v.y); }
-            }
-            block_argmax(bv, bi, ldv, ldi);
-            if (tid == 0) s_x = bi;
-        } else {
-            const float* part = (resid ? T.mpart : T.bpart) + part0;
-            for (int c = tid; c < nmc; c += kThreads) lw[c] = part[c];
-            __syncthreads();
-            if (tid == 0) {                            // the chunk the row's uniform falls in
-                double total = 0.0;
-                for (int c = 0; c < nmc; ++c) total += (double)lw[c];
-                int pick = -1;
-                if (total > 0.0 && total < (double)INFINITY) {
-                    const double target = cdf_uniform(P.noise, (uint32_t)b) * total;
-                    double run = 0.0, before = 0.0;
-                    for (int c = 0; c < nmc; ++c) {
-                        const double v = (double)lw[c];
-                        if (v > 0.0) {
-                            pick = c; before = run;
-                            if (run + v > target) break;
-                        }
-                        run += v;
-                    }
-                    s_target = target - before;
-                } else {
-                    s_status |= SD_ROW_INVALID_DIST;   // zero / NaN / inf mass: torch.multinomial raises
-                }
-                s_sub = pick;
-            }
-            __syncthreads();
-            const int pick = s_sub;
-            if (pick >= 0) {                           // the element inside the chunk, weights recomputed
-                const MultiRow<DT> Tr = tree_row<DT>(P, T, b, slot, false);
-                MultiRow<DT> Dr{};
-                const int64_t e0 = (int64_t)pick * kMultiChunk + tid * kMultiEpt;
-                float xt[kMultiEpt], xd[kMultiEpt], wv[kMultiEpt];
-#pragma unroll
-                for (int e = 0; e < kMultiEpt; ++e) xd[e] = 0.f;
-                multi_load<DT>(Tr, e0, P.V, xt);
-                if (resid) {
-                    Dr = tree_row<DT>(P, T, b, slot, true);
-                    multi_load<DT>(Dr, e0, P.V, xd);
-                }
-                multi_weights<DT>(P, Tr, Dr, resid, nrej - 1, lmass, e0, xt, xd, wv);
-                double ls = 0.0;
-#pragma unroll
-                for (int e = 0; e < kMultiEpt; ++e) ls += (double)wv[e];
-                double incl = wave_incl_scan_d(ls);
-                if (lane == 63) ldd[w] = incl;
-                __syncthreads();
-                for (int k2 = 0; k2 < w; ++k2) incl += ldd[k2];
-                const double target = s_target;
-                const uint64_t pos = __ballot(ls > 0.0), over = __ballot(ls > 0.0 && incl > target);
-                if (lane == 0) {
-                    lfirst[w] = over ? w * kWave + __ffsll((unsigned long long)over) - 1 : INT_MAX;
-                    llast[w] = pos ? w * kWave + 63 - __clzll((long long)pos) : -1;
-                }
-                __syncthreads();
-                // the first thread whose running total passes the target, else the last with weight
-                int sel = INT_MAX, last = -1;
-                for (int k2 = 0; k2 < kThreads / kWave; ++k2) {
-                    sel = lfirst[k2] < sel ? lfirst[k2] : sel;
-                    last = llast[k2] > last ? llast[k2] : last;
-                }
-                if (sel == INT_MAX) sel = last;
-                if (tid == sel) {
-                    double run = incl - ls;
-                    int pe = 0;
-                    bool done = false;   // the first element whose running total passes, else the last with weight
-#pragma unroll
-                    for (int e = 0; e < kMultiEpt; ++e) {
-                        run += (double)wv[e];
-                        if (wv[e] > 0.f && !done) { pe = e; done = run > target; }
-                    }
-                    s_x = e0 + pe;
-                }
-            }
-        }
-        __syncthreads();
+        walk_draw<DT>(P, L, Dl, b, nmc, (resid ? T.mpart : T.bpart) + part0, (resid ? T.mbest : T.bbest) + part0, resid, nrej,
+                      lmass, [&](bool draft) { return tree_row<DT>(P, T, b, slot, draft); });
     }
-    const bool drawn = s_mode != kMultiNone && !(s_status & SD_ROW_INVALID_DIST);
-    if (tid == 0) {
-        const int st = s_status;
-        P.n_accepted[b] = n;
-        T.last_node[b] = n > 0 ? lpath[n - 1] : -1;
-        P.next_token[b] = drawn ? s_x : -1;
-        if (P.resample_mass) P.resample_mass[b] = s_mass;
-        if (T.n_rejects) T.n_rejects[b] = s_rejects;
-        if (P.stop_index) P.stop_index[b] = s_stop;
-        P.row_status[b] = st;
-        flag_error(P.status_or, st);
-    }
-    if (tid < T.depth) T.path[(int64_t)b * T.path_stride + tid] = lpath[tid];
-    if (T.tokens_out && tid <= T.depth)
-        T.tokens_out[(int64_t)b * T.tokens_out_stride + tid] =
-            tid < n ? ltok[lpath[tid]] : (tid == n && drawn ? s_x : T.pad_token);
+    tree_write_out(P, T.out, b, T.depth, n, lpath, ltok, walk_drawn(L), L.x, L.status, s_mass, s_rejects, L.stop);
 }
 
 }  // namespace sd
@@ -396,26 +286,35 @@ int32_t tree_shape_status(int64_t B, int64_t vocab, const TreeTopo& t) {
     return SD_OK;
 }
 
-// the k_stats groups of a tree: (first row of the tree's row table, rows) — target slots, then the
-// internal slots' drafter rows, at most kTreeGroup rows each
-int tree_groups(const TreeTopo& t, int* row0, int* cnt) {
+// ---- what sd_verify_tree, sd_verify_tree_distinct and sd_verify_tree_dynamic set up alike (their argument
+// structs name everything read here alike)
+
+// the k_stats groups of a tree: (first row of the tree's row table, rows) — target slots, then with
+// `drafter` (sd_verify_tree) the internal slots' drafter rows, at most kTreeGroup rows each
+int tree_groups(const TreeTopo& t, bool drafter, int* row0, int* cnt) {
     int n = 0;
-    for (int lo = 0; lo <= t.N; lo += sd::kTreeGroup) { row0[n] = lo; cnt[n++] = t.N + 1 - lo < sd::kTreeGroup ? t.N + 1 - lo : sd::kTreeGroup; }
-    for (int lo = 0; lo < t.n_int; lo += sd::kTreeGroup) {
-        row0[n] = t.N + 1 + lo;
-        cnt[n++] = t.n_int - lo < sd::kTreeGroup ? t.n_int - lo : sd::kTreeGroup;
-    }
+    const int first[2] = {0, t.N + 1}, rows[2] = {t.N + 1, drafter ? t.n_int : 0};
+    for (int k = 0; k < 2; ++k)
+        for (int lo = 0; lo < rows[k]; lo += sd::kTreeGroup) {
+            row0[n] = first[k] + lo;
+            cnt[n++] = rows[k] - lo < sd::kTreeGroup ? rows[k] - lo : sd::kTreeGroup;
+        }
     return n;
 }
 
-void carve_tree(sd::Plan* G, sd::Tree& T, Carve& c, int B, const TreeTopo& t, int vocab) {
+// the front of a tree workspace: the counter block, then every k_stats group's rows
+void carve_tree_groups(sd::Plan* G, Carve& c, int B, const TreeTopo& t, bool drafter, int vocab) {
     uint32_t* cnt = c.take<uint32_t>(kCntBlockBytes / sizeof(uint32_t));   // first, at a fixed offset (sd_device.h)
     int row0[sd::kTreeGroups], rows[sd::kTreeGroups];
-    const int ng = tree_groups(t, row0, rows);
+    const int ng = tree_groups(t, drafter, row0, rows);
     for (int g = 0; g < ng; ++g) {
         G[g].cnt = cnt;
         carve_rows(G[g], c, B * rows[g], B, 0, vocab);
     }
+}
+
+void carve_tree(sd::Plan* G, sd::Tree& T, Carve& c, int B, const TreeTopo& t, int vocab) {
+    carve_tree_groups(G, c, B, t, true, vocab);
     const size_t R = (size_t)t.N + 1 + t.n_int;
     T.n_mchunks = (vocab + sd::kMultiChunk - 1) / sd::kMultiChunk;
     T.rowstat = c.take<float2>((size_t)B * R);
@@ -426,6 +325,115 @@ void carve_tree(sd::Plan* G, sd::Tree& T, Carve& c, int B, const TreeTopo& t, in
     T.mbest = c.take<float2>(pairs * sd::kTreeC * T.n_mchunks);
     T.bpart = c.take<float>((size_t)B * t.n_leaf * T.n_mchunks);
     T.bbest = c.take<float2>((size_t)B * t.n_leaf * T.n_mchunks);
+}
+
+// The argument checks, in the order their statuses take precedence: SD_ERR_INVALID for what does not depend
+// on the shape, the shape's own status (`shape`), then SD_ERR_INVALID for null target rows and short strides.
+// An entry point's own checks go before (no status yet returned but SD_ERR_INVALID) or after this.
+template <class Args>
+int32_t tree_check_args(const Args* a, int32_t shape, int N, int depth) {
+    if (!valid_dtype(a->dtype) || !valid_proc(a->proc) || !(a->proc.temperature > 0.f)) return SD_ERR_INVALID;
+    if (!a->draft_tokens || !a->n_accepted || !a->last_node || !a->next_token || !a->row_status || !a->path)
+        return SD_ERR_INVALID;
+    if (a->n_stop < 0 || (a->n_stop > 0 && !a->stop_tokens)) return SD_ERR_INVALID;
+    if (a->noise.mode != SD_NOISE_STREAM && a->noise.mode != SD_NOISE_PHILOX) return SD_ERR_INVALID;
+    if (shape != SD_OK) return shape;
+    for (int s = 0; s <= N; ++s)
+        if (!a->target_rows[s]) return SD_ERR_INVALID;
+    if (a->draft_tokens_stride_b < N || a->path_stride_b < depth) return SD_ERR_INVALID;
+    if (a->tokens_out && a->tokens_out_stride_b < depth + 1) return SD_ERR_INVALID;
+    return SD_OK;
+}
+// ... and the last two: SD_ERR_UNSUPPORTED for STREAM noise, SD_ERR_WORKSPACE for less than `need` bytes
+template <class Args>
+int32_t tree_check_noise_workspace(const Args* a, size_t need) {
+    if (a->noise.mode == SD_NOISE_STREAM) return SD_ERR_UNSUPPORTED;   // the rule defines no stream order
+    if (a->workspace_bytes < need || !a->workspace) return SD_ERR_WORKSPACE;
+    return SD_OK;
+}
+
+// what the tree's own kernels read of a Plan: the processor, the drafts, the stop list, the noise, the outputs
+template <class Args>
+sd::Plan tree_walk_plan(const Args* a) {
+    sd::Plan P{};
+    P.B = a->batch; P.V = a->vocab; P.rule = SD_RULE_SPEC;
+    P.tdt = P.ddt = a->dtype;
+    P.t_keep = P.d_keep = needs_keep(a->proc);
+    P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
+    P.tT = P.dT = a->proc.temperature;
+    P.draft_tokens = a->draft_tokens; P.tok_stride = a->draft_tokens_stride_b;
+    P.stops = a->stop_tokens; P.n_stop = a->n_stop;
+    P.noise = a->noise;
+    P.n_accepted = a->n_accepted; P.next_token = a->next_token; P.next_token_stride = 1;
+    P.resample_mass = a->resample_mass; P.stop_index = a->stop_index; P.row_status = a->row_status;
+    P.status_or = a->status_or;
+    return P;
+}
+
+template <class Args>
+sd::TreeOut tree_out(const Args* a) {
+    sd::TreeOut O{};
+    O.pad_token = a->pad_token;
+    O.last_node = a->last_node; O.n_rejects = a->n_sibling_rejects;
+    O.path = a->path; O.path_stride = a->path_stride_b;
+    O.tokens_out = a->tokens_out; O.tokens_out_stride = a->tokens_out_stride_b;
+    return O;
+}
+
+// the topology as the walks read it (sd::Tree or sd::TreeD): parent, nchild, child_off, child
+template <class TreeT>
+void tree_child_lists(TreeT& T, const TreeTopo& t, const int32_t* parent) {
+    int fill[sd::kTreeSlots] = {};
+    for (int s = 0, off = 0; s <= t.N; ++s) {
+        T.nchild[s] = (uint8_t)t.nchild[s];
+        T.child_off[s] = (uint8_t)off;
+        off += t.nchild[s];
+    }
+    for (int i = 0; i < t.N; ++i) {
+        const int s = parent[i] + 1;
+        T.parent[i] = (int8_t)parent[i];
+        T.child[T.child_off[s] + fill[s]++] = (uint8_t)i;
+    }
+}
+
+// one row group's k_stats Plan (carved already): `rows` rows row(0 ..) of batch stride `stride`, every one a
+// "target" row of a Plan of its own (one processor, one dtype)
+template <class Args, class Row>
+void tree_stats_plan(sd::Plan& Q, const Args* a, int rows, int64_t stride, Row row) {
+    Q.B = a->batch; Q.V = a->vocab; Q.rule = SD_RULE_SPEC;
+    Q.n_tslots = Q.slots = Q.stat_slots = rows; Q.n_dslots = 0;
+    Q.tdt = Q.ddt = a->dtype;
+    Q.t_keep = needs_keep(a->proc); Q.d_keep = 0;
+    Q.t_stoch = a->proc.kind != SD_PROC_GREEDY;
+    Q.tT = a->proc.temperature; Q.dT = 1.f;
+    Q.tstride = stride;
+    for (int i = 0; i < rows; ++i) Q.trow[i] = row(i);
+    Q.noise = a->noise;
+    Q.status_or = a->status_or;
+    set_stats_chunks(Q, Q.B * Q.stat_slots);
+    set_rchunks(Q);
+}
+
+// every group's statistics into the tree's row table [b][R]: the threshold search when the processor keeps
+// a subset, k_stats, k_tree_rowstat
+int32_t launch_tree_stats(const sd::Plan* G, int ng, const int* row0, float2* rowstat, RowKeep* keep, int R,
+                          const sd_processor& proc, void* stream) {
+    const int wpb = sd::kThreads / sd::kWave;
+    for (int g = 0; g < ng; ++g) {
+        const sd::Plan& Q = G[g];
+        if (Q.t_keep)
+            if (int32_t st = launch_threshold(Q, proc, proc, stream, /*allow_poll=*/false)) return st;
+        // at most 65535 grid rows per launch
+        const int per = 65535 / Q.B < 1 ? 1 : 65535 / Q.B;
+        for (int lo = 0; lo < Q.stat_slots; lo += per) {
+            const int cnt = Q.stat_slots - lo < per ? Q.stat_slots - lo : per;
+            if (int32_t st = launch_stats_group(Q, Q.tdt, Q.t_fast(), lo, cnt, false, stream)) return st;
+        }
+        if (int32_t st = launch(sd::k_tree_rowstat, dim3((Q.B * Q.slots + wpb - 1) / wpb), dim3(sd::kThreads), 0, stream, Q,
+                                rowstat, keep, R, row0[g]))
+            return st;
+    }
+    return SD_OK;
 }
 
 }  // namespace
@@ -450,103 +458,43 @@ int32_t sd_verify_tree(const sd_tree_args* a, void* stream) {
     if (topo == SD_ERR_INVALID) return SD_ERR_INVALID;
     const int32_t shape = topo == SD_OK ? tree_shape_status(a->batch, a->vocab, t) : topo;
     if (shape == SD_ERR_INVALID || a->batch <= 0 || a->vocab <= 0) return SD_ERR_INVALID;
-    if (!valid_dtype(a->dtype) || !valid_proc(a->proc) || !(a->proc.temperature > 0.f)) return SD_ERR_INVALID;
-    if (!a->draft_tokens || !a->n_accepted || !a->last_node || !a->next_token || !a->row_status || !a->path)
-        return SD_ERR_INVALID;
-    if (a->n_stop < 0 || (a->n_stop > 0 && !a->stop_tokens)) return SD_ERR_INVALID;
-    if (a->noise.mode != SD_NOISE_STREAM && a->noise.mode != SD_NOISE_PHILOX) return SD_ERR_INVALID;
-    if (shape != SD_OK) return shape;
+    if (int32_t st = tree_check_args(a, shape, t.N, t.depth)) return st;
     for (int s = 0; s <= t.N; ++s)
-        if (!a->target_rows[s] || (t.nchild[s] && !a->draft_rows[s])) return SD_ERR_INVALID;
-    if (a->draft_tokens_stride_b < t.N || a->path_stride_b < t.depth) return SD_ERR_INVALID;
-    if (a->tokens_out && a->tokens_out_stride_b < t.depth + 1) return SD_ERR_INVALID;
-    if (a->noise.mode == SD_NOISE_STREAM) return SD_ERR_UNSUPPORTED;   // the rule defines no stream order
-    if (a->workspace_bytes < sd_verify_tree_workspace_size(a->batch, a->num_nodes, a->parent, a->vocab) || !a->workspace)
-        return SD_ERR_WORKSPACE;
+        if (t.nchild[s] && !a->draft_rows[s]) return SD_ERR_INVALID;
+    if (int32_t st = tree_check_noise_workspace(
+            a, sd_verify_tree_workspace_size(a->batch, a->num_nodes, a->parent, a->vocab)))
+        return st;
 
     const int B = a->batch, N = t.N;
-    const bool keep = needs_keep(a->proc);
-    // what the tree's own kernels read of a Plan: the processor, the drafts, the stop list, the noise, the outputs
-    sd::Plan P{};
-    P.B = B; P.V = a->vocab; P.rule = SD_RULE_SPEC;
-    P.tdt = P.ddt = a->dtype;
-    P.t_keep = P.d_keep = keep;
-    P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
-    P.tT = P.dT = a->proc.temperature;
-    P.draft_tokens = a->draft_tokens; P.tok_stride = a->draft_tokens_stride_b;
-    P.stops = a->stop_tokens; P.n_stop = a->n_stop;
-    P.noise = a->noise;
-    P.n_accepted = a->n_accepted; P.next_token = a->next_token; P.next_token_stride = 1;
-    P.resample_mass = a->resample_mass; P.stop_index = a->stop_index; P.row_status = a->row_status;
-    P.status_or = a->status_or;
-
+    const sd::Plan P = tree_walk_plan(a);
     sd::Tree T{};
     T.B = B; T.N = N; T.R = N + 1 + t.n_int;
     T.depth = t.depth; T.n_int = t.n_int; T.n_leaf = t.n_leaf;
     T.tstride = a->target_stride_b; T.dstride = a->draft_stride_b;
-    int fill[sd::kTreeSlots] = {};
-    for (int s = 0, off = 0; s <= N; ++s) {
+    int int_slot[sd::kTreeSlots];
+    for (int s = 0; s <= N; ++s) {
         T.trow[s] = a->target_rows[s];
         T.drow[s] = t.nchild[s] ? a->draft_rows[s] : nullptr;
-        T.nchild[s] = (uint8_t)t.nchild[s];
         T.idx[s] = (uint8_t)t.idx[s];
         T.order[s] = (uint8_t)t.order[s];
-        T.child_off[s] = (uint8_t)off;
-        off += t.nchild[s];
+        if (t.nchild[s]) int_slot[t.idx[s]] = s;
     }
-    for (int i = 0; i < N; ++i) {
-        const int s = a->parent[i] + 1;
-        T.parent[i] = (int8_t)a->parent[i];
-        T.child[T.child_off[s] + fill[s]++] = (uint8_t)i;
-    }
-    T.pad_token = a->pad_token;
-    T.last_node = a->last_node; T.n_rejects = a->n_sibling_rejects;
-    T.path = a->path; T.path_stride = a->path_stride_b;
-    T.tokens_out = a->tokens_out; T.tokens_out_stride = a->tokens_out_stride_b;
+    tree_child_lists(T, t, a->parent);
+    T.out = tree_out(a);
 
-    // the k_stats groups: every row a "target" row of a Plan of its own (one processor, one dtype)
     sd::Plan G[sd::kTreeGroups] = {};
     int row0[sd::kTreeGroups], rows[sd::kTreeGroups];
-    const int ng = tree_groups(t, row0, rows);
+    const int ng = tree_groups(t, true, row0, rows);
     Carve c{static_cast<char*>(a->workspace)};
     carve_tree(G, T, c, B, t, a->vocab);
-    int int_slot[sd::kTreeSlots];
-    for (int s = 0; s <= N; ++s)
-        if (t.nchild[s]) int_slot[t.idx[s]] = s;
     for (int g = 0; g < ng; ++g) {
-        sd::Plan& Q = G[g];
-        Q.B = B; Q.V = a->vocab; Q.rule = SD_RULE_SPEC;
-        Q.n_tslots = Q.slots = Q.stat_slots = rows[g]; Q.n_dslots = 0;
-        Q.tdt = Q.ddt = a->dtype;
-        Q.t_keep = keep; Q.d_keep = 0;
-        Q.t_stoch = P.t_stoch;
-        Q.tT = a->proc.temperature; Q.dT = 1.f;
-        const bool target = row0[g] <= N;
-        Q.tstride = target ? a->target_stride_b : a->draft_stride_b;
-        for (int i = 0; i < rows[g]; ++i)
-            Q.trow[i] = target ? a->target_rows[row0[g] + i] : a->draft_rows[int_slot[row0[g] - (N + 1) + i]];
-        Q.noise = a->noise;
-        Q.status_or = a->status_or;
-        set_stats_chunks(Q, Q.B * Q.stat_slots);
-        set_rchunks(Q);
+        const int r0 = row0[g];
+        if (r0 <= N) tree_stats_plan(G[g], a, rows[g], a->target_stride_b, [&](int i) { return a->target_rows[r0 + i]; });
+        else tree_stats_plan(G[g], a, rows[g], a->draft_stride_b, [&](int i) { return a->draft_rows[int_slot[r0 - (N + 1) + i]]; });
     }
 
     g_verify_path = SD_PATH_NONE;
-    const int wpb = sd::kThreads / sd::kWave;
-    for (int g = 0; g < ng; ++g) {
-        const sd::Plan& Q = G[g];
-        if (keep)
-            if (int32_t st = launch_threshold(Q, a->proc, a->proc, stream, /*allow_poll=*/false)) return st;
-        // at most 65535 grid rows per launch
-        const int per = 65535 / Q.B < 1 ? 1 : 65535 / Q.B;
-        for (int lo = 0; lo < Q.stat_slots; lo += per) {
-            const int cnt = Q.stat_slots - lo < per ? Q.stat_slots - lo : per;
-            if (int32_t st = launch_stats_group(Q, Q.tdt, Q.t_fast(), lo, cnt, false, stream)) return st;
-        }
-        if (int32_t st = launch(sd::k_tree_rowstat, dim3((Q.B * Q.slots + wpb - 1) / wpb), dim3(sd::kThreads), 0, stream, Q,
-                                T.rowstat, T.keep, T.R, row0[g]))
-            return st;
-    }
+    if (int32_t st = launch_tree_stats(G, ng, row0, T.rowstat, T.keep, T.R, a->proc, stream)) return st;
     return dispatch_dtype(a->dtype, [&](auto dt_) -> int32_t {
         constexpr int DT = decltype(dt_)::value;
         for (int j = 1; j <= t.cmax + 1; ++j) {

@@ -31,6 +31,7 @@
 // target rows, ONE launch of per-chunk row sums and one walk-and-draw launch.  With one topology per
 // sequence, read from device memory (sd_verify_tree_dynamic, sd_verify_tree_dynamic.inc): the same launches,
 // the walk building its child lists in LDS.
+// These walks and the vocabulary-parallel pick (vocab_parallel.hip) draw by one rule, defined once in sd_pick.h.
 //
 // Every logit row is read once by the statistics pass (the algorithmic bytes); the sampling pass
 // re-reads at most two rows per sequence (served from the 256 MiB Infinity Cache).  See DESIGN.md.
@@ -48,6 +49,7 @@
 
 #include "sd_device.h"
 #include "sd_host.h"
+#include "sd_pick.h"
 
 namespace sd {
 

@@ -16,7 +16,8 @@
 //                 k_vp_mass     grid (chunk) x (sequence): the chunk's total of the weights w over the
 //                               decided row pair's slice (greedy: the chunk's argmax too)
 //                 k_vp_pick     one workgroup per sequence: the fp64 prefix over the chunk totals (chunk
-//                               order), the element inside the one chosen chunk (weights recomputed),
+//                               order), the element inside the one chosen chunk (weights recomputed) by the
+//                               draw rule of sd_pick.h, which the walks of specdec_kernels.hip end in too;
 //                               the candidate record with the decision in it; the block header
 //   sd_vp_finish  k_vp_finish   one thread per sequence: the shard pick on u1, the outputs
 //
@@ -26,6 +27,7 @@
 // the workspace between them: ranks emulated in one process may share one workspace.
 #include "sd_device.h"
 #include "sd_host.h"
+#include "sd_pick.h"
 
 namespace sd {
 
@@ -213,8 +215,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_decide(Vp P) {
         float p = 0.f, q = 0.f;
         if (lown[tid]) p = prob_exact<DT>(ly[tid], lstat[tid].x, lstat[tid].y, 1.0f / lstat[tid].y);
         if (lown[rd]) q = prob_exact<DT>(ly[rd], lstat[rd].x, lstat[rd].y, 1.0f / lstat[rd].y);
-        const uint4 q4 = philox_block(P.noise, (uint32_t)b, kSiteAccept, (uint32_t)(tid >> 2));
-        const float u = uniform_from_word((tid & 3) == 0 ? q4.x : (tid & 3) == 1 ? q4.y : (tid & 3) == 2 ? q4.z : q4.w);
+        const float u = accept_uniform(P.noise, b, tid);
         lacc[tid] = !(u > p / q) ? 1 : 0;             // sampling/speculative_decoding.py:141-145 (fp32)
         const int64_t tok = P.tok[(int64_t)b * P.tok_stride + tid];
         int rank = INT_MAX;
@@ -296,28 +297,22 @@ __global__ void __launch_bounds__(kThreads) k_vp_mass(Vp P) {
     s = block_reduce(s, FSum{}, lds, kWaves);
     if (threadIdx.x == 0) P.mpart[(int64_t)b * P.n_chunks + c] = s;
     if (!P.stoch) {                                   // greedy: the chunk's argmax (NaN first, lowest index)
-        float bv = -INFINITY;
-        int32_t bi = INT_MAX;
-#pragma unroll
-        for (int e = 0; e < kVpEpt; ++e)
-            if (e0 + e < P.Vs && arg_better(wv[e], (int32_t)(e0 + e), bv, bi)) { bv = wv[e]; bi = (int32_t)(e0 + e); }
-        block_argmax(bv, bi, lds, ldi, kWaves);
-        if (threadIdx.x == 0) P.mbest[(int64_t)b * P.n_chunks + c] = make_float2(bv, __int_as_float(bi));
+        const float2 best = chunk_argmax<kVpEpt>(wv, e0, P.Vs, lds, ldi, kWaves);
+        if (threadIdx.x == 0) P.mbest[(int64_t)b * P.n_chunks + c] = best;
     }
 }
 
 template <int DT>
 __global__ void __launch_bounds__(kThreads) k_vp_pick(Vp P) {
     __shared__ float lw[kVpMaxChunks];
-    __shared__ double ldd[kThreads / kWave];
-    __shared__ int32_t lfirst[kThreads / kWave], llast[kThreads / kWave];
-    __shared__ float ldv[4];
-    __shared__ int32_t ldi[4];
+    __shared__ PickLds L;
+    __shared__ float ldv[kWaves];
+    __shared__ int32_t ldi[kWaves];
     __shared__ int32_t s_pick;
     __shared__ double s_target, s_total;
     __shared__ int64_t s_x;
     __shared__ float s_w;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nc = P.n_chunks;
+    const int b = blockIdx.x, tid = threadIdx.x, nc = P.n_chunks;
     const VpDecision d = P.dec[b];
     if (b == 0 && tid == 0) vp_write_header(P, P.cand_local);
     if (tid == 0) { s_x = -1; s_w = 0.f; s_total = 0.0; s_pick = -1; }
@@ -325,73 +320,32 @@ __global__ void __launch_bounds__(kThreads) k_vp_pick(Vp P) {
         for (int c = tid; c < nc; c += kThreads) lw[c] = P.mpart[(int64_t)b * nc + c];
         __syncthreads();
         if (tid == 0) {
-            // M_s: the chunk totals in fp64, in chunk order; then the chunk u2 falls in
-            double total = 0.0;
-            for (int c = 0; c < nc; ++c) total += (double)lw[c];
+            // M_s: recorded under greedy too; then, stochastic, the chunk u2 falls in
+            const double total = chunk_total(lw, nc);
             s_total = total;
-            int pick = -1;
             if (P.stoch && total > 0.0 && total < (double)INFINITY) {
-                const double target = cdf_uniform(P.noise, (uint32_t)b, 1u) * total;
-                double run = 0.0, before = 0.0;
-                for (int c = 0; c < nc; ++c) {
-                    const double v = (double)lw[c];
-                    if (v > 0.0) {
-                        pick = c; before = run;
-                        if (run + v > target) break;
-                    }
-                    run += v;
-                }
-                s_target = target - before;
+                double in_chunk;
+                s_pick = chunk_pick(lw, nc, cdf_uniform(P.noise, (uint32_t)b, 1u) * total, &in_chunk);
+                s_target = in_chunk;
             }
-            s_pick = pick;
         }
         __syncthreads();
         if (!P.stoch) {                               // greedy: argmax over the chunks' argmaxes
-            float bv = -INFINITY;
-            int32_t bi = INT_MAX;
-            for (int c = tid; c < nc; c += kThreads) {
-                const float2 v = P.mbest[(int64_t)b * nc + c];
-                if (arg_better(v.x, __float_as_int(v.y), bv, bi)) { bv = v.x; bi = __float_as_int(v.y); }
-            }
-            block_argmax(bv, bi, ldv, ldi, kWaves);
+            float bv;
+            int32_t bi;
+            greedy_over_chunks(P.mbest + (int64_t)b * nc, nc, ldv, ldi, bv, bi, kWaves);
             if (tid == 0 && bi != INT_MAX) { s_x = (int64_t)P.off + bi; s_w = bv; }
         } else if (s_pick >= 0) {                     // the element inside the chunk, weights recomputed
             const int pick = s_pick;
-            const int64_t e0 = (int64_t)pick * kVpChunk + tid * kVpEpt;
             float wv[kVpEpt];
             vp_chunk_weights<DT>(P, d, b, pick, wv);
-            double ls = 0.0;
-#pragma unroll
-            for (int e = 0; e < kVpEpt; ++e) ls += (double)wv[e];
-            double incl = wave_incl_scan_d(ls);
-            if (lane == 63) ldd[w] = incl;
-            __syncthreads();
-            for (int k2 = 0; k2 < w; ++k2) incl += ldd[k2];
-            const double target = s_target;
-            const uint64_t pos = __ballot(ls > 0.0), over = __ballot(ls > 0.0 && incl > target);
-            if (lane == 0) {
-                lfirst[w] = over ? w * kWave + __ffsll((unsigned long long)over) - 1 : INT_MAX;
-                llast[w] = pos ? w * kWave + 63 - __clzll((long long)pos) : -1;
-            }
-            __syncthreads();
-            // the first thread whose running total passes the target, else the last with weight
-            int sel = INT_MAX, last = -1;
-            for (int k2 = 0; k2 < kThreads / kWave; ++k2) {
-                sel = lfirst[k2] < sel ? lfirst[k2] : sel;
-                last = llast[k2] > last ? llast[k2] : last;
-            }
-            if (sel == INT_MAX) sel = last;
-            if (tid == sel) {
-                double run = incl - ls;
-                int pe = 0;
+            bool any;
+            const int pe = pick_in_chunk<kVpEpt>(wv, s_target, L, &any);
+            if (pe >= 0) {
                 float pw = 0.f;
-                bool done = false;   // the first element whose running total passes, else the last with weight
 #pragma unroll
-                for (int e = 0; e < kVpEpt; ++e) {
-                    run += (double)wv[e];
-                    if (wv[e] > 0.f && !done) { pe = e; pw = wv[e]; done = run > target; }
-                }
-                s_x = (int64_t)P.off + e0 + pe;
+                for (int e = 0; e < kVpEpt; ++e) pw = e == pe ? wv[e] : pw;
+                s_x = (int64_t)P.off + (int64_t)pick * kVpChunk + tid * kVpEpt + pe;
                 s_w = pw;
             }
         }

@@ -103,6 +103,17 @@ static void rejections() {
     b = a; b.proc.temperature = 0.f; CHECK(call(b) == SD_ERR_INVALID);
     b = a; b.noise.mode = SD_NOISE_STREAM; CHECK(call(b) == SD_ERR_UNSUPPORTED);
     b = a; b.noise.mode = 5; CHECK(call(b) == SD_ERR_INVALID);
+    // precedence: INVALID of the arguments > the shape's status > INVALID of rows and strides > STREAM > WORKSPACE
+    sd_tree_distinct_args u = a; u.batch = SD_TREE_MAX_BATCH + 1;                  // an unsupported shape
+    b = u; b.n_accepted = nullptr; CHECK(call(b) == SD_ERR_INVALID);
+    b = u; b.noise.mode = 5; CHECK(call(b) == SD_ERR_INVALID);
+    b = u; b.target_rows[0] = nullptr; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = u; b.path_stride_b = 3; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = u; b.noise.mode = SD_NOISE_STREAM; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = a; b.num_nodes = SD_TREE_MAX_NODES + 1; b.target_rows[0] = nullptr; CHECK(call(b) == SD_ERR_UNSUPPORTED);   // ... topology
+    b = a; b.noise.mode = SD_NOISE_STREAM; b.target_rows[3] = nullptr; CHECK(call(b) == SD_ERR_INVALID);
+    b = a; b.noise.mode = SD_NOISE_STREAM; b.tokens_out_stride_b = 4; CHECK(call(b) == SD_ERR_INVALID);
+    b = a; b.target_rows[28] = nullptr; b.workspace = fake(300); b.workspace_bytes = 1; CHECK(call(b) == SD_ERR_INVALID);
 }
 
 static void workspace_shapes() {

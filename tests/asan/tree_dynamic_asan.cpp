@@ -170,6 +170,19 @@ static void dynamic_rejections() {
     b = a; b.proc.temperature = 0.f; CHECK(call(b) == SD_ERR_INVALID);
     b = a; b.noise.mode = SD_NOISE_STREAM; CHECK(call(b) == SD_ERR_UNSUPPORTED);
     b = a; b.noise.mode = 5; CHECK(call(b) == SD_ERR_INVALID);
+    // precedence: INVALID of the arguments > the shape's status > INVALID of rows and strides > STREAM > WORKSPACE
+    sd_tree_dynamic_args u = a; u.batch = SD_TREE_MAX_BATCH + 1;                   // an unsupported shape
+    b = u; b.parent_dev = nullptr; CHECK(call(b) == SD_ERR_INVALID);
+    b = u; b.n_accepted = nullptr; CHECK(call(b) == SD_ERR_INVALID);
+    b = u; b.noise.mode = 5; CHECK(call(b) == SD_ERR_INVALID);
+    b = u; b.target_rows[0] = nullptr; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = u; b.parent_stride_b = 27; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = u; b.path_stride_b = 3; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = u; b.noise.mode = SD_NOISE_STREAM; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = a; b.max_depth = SD_MAX_GAMMA + 1; b.target_rows[0] = nullptr; CHECK(call(b) == SD_ERR_UNSUPPORTED);
+    b = a; b.noise.mode = SD_NOISE_STREAM; b.target_rows[3] = nullptr; CHECK(call(b) == SD_ERR_INVALID);
+    b = a; b.noise.mode = SD_NOISE_STREAM; b.parent_stride_b = 27; CHECK(call(b) == SD_ERR_INVALID);
+    b = a; b.parent_stride_b = 27; b.workspace = fake(300); b.workspace_bytes = 1; CHECK(call(b) == SD_ERR_INVALID);
 }
 
 static void workspace_shapes() {

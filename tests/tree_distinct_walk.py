@@ -84,7 +84,8 @@ def finish(tl, tok, parent, proc_name, **extra):
 
 @functools.lru_cache(maxsize=4)
 def case(tname, V, dtype, proc_name, seed=11):
-    parent = TREES[tname]
+    """tname: a name of TREES, or a parent list given as a tuple."""
+    parent = TREES[tname] if isinstance(tname, str) else list(tname)
     N = len(parent)
     gen = torch.Generator().manual_seed(seed * 1000003 + N * 101 + V)
     base = torch.randn(B, N + 1, V, generator=gen) * 3

@@ -165,8 +165,9 @@ def case(B, tname, V, dtype, proc_name, tail=False, mask="none"):
     values), drafts tok [B, N] drawn iid from Q of the parent slot and then steered by sequence b's
     scenario SCENARIOS[b % 6]; B = 1 builds SEQS_B1 sequences (see grid).  With `tail` the logits from
     the last chunk's start on get +8 in the target rows and +6 in the drafter rows; `mask` puts `-inf` entries (tests/row_edges.py) into the
-    target rows, and the drafter rows have them at the same places."""
-    parent = TREES[tname]
+    target rows, and the drafter rows have them at the same places.  tname: a name of TREES, or a parent
+    list given as a tuple."""
+    parent = TREES[tname] if isinstance(tname, str) else list(tname)
     seed = GRID_SEEDS.get((B, tname, V, dtype, proc_name, tail, mask), 11)
     N, B = len(parent), n_seqs(B)
     gen = torch.Generator().manual_seed(seed * 1000003 + N * 101 + V)
