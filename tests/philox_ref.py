@@ -1,7 +1,7 @@
 """Philox4x32-10 (Salmon, Moraes, Dror, Shaw — "Parallel random numbers: as easy as 1, 2, 3",
 SC'11) in numpy, for checking the perf-mode (SD_NOISE_PHILOX) kernels.  Mirrors
 csrc/sd_device.h: philox4x32_10, philox_block's counter layout, uniform_from_word,
-cdf_uniform.  Test infrastructure only.
+cdf_uniform, span_gumbel, and csrc/sd_draw_nucleus.inc: nuc_uniform.  Test infrastructure only.
 """
 from __future__ import annotations
 
@@ -41,9 +41,43 @@ def accept_uniform(seed: int, offset: int, row: int, i: int) -> float:
     return np.float32((w & 0xFFFFFF) * 2.0 ** -24)
 
 
-def cdf_uniform(seed: int, offset: int, row: int) -> float:
-    x, y, _, _ = block(seed, offset, row, SITE_CDF, 0)
-    return float(((int(x) << 32) | int(y)) >> 11) * 2.0 ** -53
+SITE_NUC = 4                 # k_draw_nuc's proposals (csrc/sd_draw_nucleus.inc: kSiteNuc)
+
+
+def _u53(x, y):
+    """U[0, 1) at 53 bits from two words, x the high one (sd_device.h cdf_uniform)."""
+    v = ((np.asarray(x, dtype=np.uint64) << np.uint64(32)) | np.asarray(y, dtype=np.uint64)) >> np.uint64(11)
+    return v.astype(np.float64) * 2.0 ** -53
+
+
+def cdf_uniform(seed: int, offset: int, row, idx=0):
+    """The inverse-CDF uniform of block (site CDF, idx) of the row: idx 0 picks the span / shard, idx 1 + c
+    the element inside span c (sd_device.h cdf_uniform).  Scalars give a float; arrays of rows and / or
+    indices broadcast to an fp64 array."""
+    x, y, _, _ = block(seed, offset, row, SITE_CDF, idx)
+    u = _u53(x, y)
+    return float(u) if u.ndim == 0 else u
+
+
+def span_gumbel(seed: int, offset: int, row, c):
+    """k_draw_lean's span-race noise g_c = -ln E_c (sd_device.h span_gumbel): word z of block (site CDF,
+    1 + c), u = (z >> 8)·2^-24 + 2^-25 in fp32 arithmetic (exp1_from_word), E = -ln u and g = -ln E in fp64
+    from the fp32 u (the device takes both logarithms in fp32).  Returns (g, E): floats for scalars, fp64
+    arrays otherwise."""
+    z = np.asarray(block(seed, offset, row, SITE_CDF, np.asarray(c, dtype=np.uint64) + np.uint64(1))[2])
+    u = (z >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24) + np.float32(2.0 ** -25)
+    with np.errstate(divide="ignore"):
+        E = -np.log(u.astype(np.float64))
+        g = -np.log(E)
+    return (float(g), float(E)) if g.ndim == 0 else (g, E)
+
+
+def nuc_uniform(seed: int, offset: int, row, idx):
+    """k_draw_nuc's 53-bit uniform of block (site 4, idx): idx = 128·(4·round + k) + (0: the row's slice
+    pick | 1 + c: slice c's element pick) (sd_draw_nucleus.inc nuc_uniform)."""
+    x, y, _, _ = block(seed, offset, row, SITE_NUC, idx)
+    u = _u53(x, y)
+    return float(u) if u.ndim == 0 else u
 
 
 def exp1_words(seed: int, offset: int, row: int, site: int, n: int):

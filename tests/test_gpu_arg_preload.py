@@ -11,9 +11,10 @@ stride of V + 8.  Checked three ways:
   * against the general path — the same values in rows that are not 16-byte aligned, which k_draw_lean
     does not take: equal status, equal greedy tokens (both are the exact argmax rule) and row statistics
     that agree to 2e-6 relative.  The multinomial TOKENS of the two kernels differ by design (k_draw picks
-    the span by an fp64 CDF scan, k_draw_lean by a Gumbel race on other Philox words), and the library
-    has no switch that sends aligned rows to k_draw, so token equality is held to the recorded parent
-    outputs instead;
+    the span by an fp64 CDF scan, k_draw_lean by a Gumbel race on other Philox words), so they are not
+    compared with each other here: which token each kernel must return is held, row by row, to the fp64
+    host model of both rules in tests/test_gpu_draw_exact.py (tests/draw_ref.py), and the recorded parent
+    outputs above only pin the bits;
   * the oracle check of tests/test_gpu_draw.py: exp(y - M) / S is the fp64 softmax to 2e-6 relative on
     the largest probabilities (the greedy token: the first index of the row's top rounded probability).
 

@@ -23,10 +23,7 @@ import philox_ref as ph
 MASS_TOL = mref.MASS_TOL
 
 
-def cdf_uniform(seed: int, off: int, row: int, idx: int) -> float:
-    """U[0, 1) at 53 bits from words x, y of block (site CDF, idx) of the row (sd_device.h cdf_uniform)."""
-    x, y, _, _ = ph.block(seed, off, row, ph.SITE_CDF, idx)
-    return float(((int(x) << 32) | int(y)) >> 11) * 2.0 ** -53
+cdf_uniform = ph.cdf_uniform     # (seed, off, row, idx): the one definition, tests/philox_ref.py
 
 
 def bounds(sizes):
