@@ -49,6 +49,7 @@
 
 #include "sd_device.h"
 #include "sd_host.h"
+#include "sd_index.h"
 #include "sd_pick.h"
 
 namespace sd {
@@ -452,6 +453,7 @@ struct SpanArgs {
     int64_t slot_stride;    // bytes from slot s to slot s + 1 (>= 0; 0: every slot is one tensor)
     int64_t seq_stride;     // bytes from sequence b to b + 1 (P.tstride in bytes)
     int32_t V, n_chunks, chunk, n_tslots, xcd_affine, B;   // as in Plan
+    uint32_t m_per_seq, m_chunks, m_B;   // sd_index.h: reciprocals of the id split's divisors
 };
 
 template <int DT, bool FAST, int MAXP>
@@ -537,16 +539,20 @@ __device__ __forceinline__ void stats_body(const Plan& P, int slot_lo, int slot_
         chunk = samp < 0 && item < n_span ? item % gx : 0;
         SD_TS_ROLE(wg_id, ((int64_t)s_tk << 32) | ((int64_t)b << 12) |
                               (samp >= 0 ? 0x800 | samp : (decider ? 0x400 : item)));
-    } else if (SAMP && !TICKET && wg_id >= nB * per_seq) {
+    } else if constexpr (ARGS) {
         // the samplers come after every span and decider in dispatch order (block id): they only wait
         // for a decision, so the spans, which wait for nothing, always get their slots first, and a
         // sampler frees its slot once it has published.  Sequence b = id % B: with B % 8 == 0 every
-        // workgroup of a sequence sits on one XCD group (affine_split's rule)
-        const int t = wg_id - nB * per_seq;
-        b = t % nB;
-        samp = t / nB;
-        s = slot_lo;
-        chunk = 0;
+        // workgroup of a sequence sits on one XCD group (affine_split's rule).
+        // The split is sd_index.h's: the divisors (per_seq, the span count, B) are launch constants
+        // whose reciprocals arrive with the leading parameters, so no workgroup runs an emulated
+        // integer division in front of its first row load.
+        const sd_fused_item it = sd_fused_split(sd_fused_index{nB, nt, gx, xa, fa.m_per_seq, fa.m_chunks, fa.m_B}, (uint32_t)wg_id);
+        b = it.b;
+        samp = it.samp;
+        s = it.slot;
+        chunk = it.chunk;
+        decider = it.decider != 0;
     } else {
         int item;
         if (xa) affine_split(wg_id, per_seq, b, item);
@@ -791,14 +797,19 @@ __global__ void __launch_bounds__(kThreads) SD_SGPR_CAP k_stats(Plan P, int slot
 #endif
 // TICKET: the ticket-order layout (fused_role; any batch): its own instantiation, so the block-id
 // kernel of small batches carries neither the ticket code nor the multi-chunk samplers' registers
-// The leading scalar parameters are a SpanArgs, field by field (preloaded: 12 SGPRs); the ticket-order
-// instantiation receives them too and reads P alone.
+// The leading scalar parameters are a SpanArgs, field by field: 15 dwords, of which the hardware
+// preloads the first 14 (the user SGPRs left beside the kernel-argument pointer; `make resources`).
+// m_per_seq and m_chunks are dwords 12 and 13, so the spans' and deciders' split waits for no load;
+// m_B, dword 14, is a scalar load in the samplers, which wait for the decision anyway.  The
+// ticket-order instantiation receives the parameters too and reads P alone.
 template <int DT, bool FAST, bool TICKET>
 __global__ void __launch_bounds__(kThreads) SD_SGPR_CAP SD_FUSED_VGPR_CAP
 k_verify_fused(const char* tbase, int64_t slot_stride, int64_t seq_stride, int32_t V, int32_t n_chunks, int32_t chunk,
-               int32_t n_tslots, int32_t xcd_affine, int32_t B, Plan P, int slot_lo, int slot_cnt) {
+               int32_t n_tslots, int32_t xcd_affine, int32_t B, uint32_t m_per_seq, uint32_t m_chunks, uint32_t m_B,
+               Plan P, int slot_lo, int slot_cnt) {
     stats_body<DT, FAST, true, true, TICKET>(P, slot_lo, slot_cnt,
-                                             SpanArgs{tbase, slot_stride, seq_stride, V, n_chunks, chunk, n_tslots, xcd_affine, B});
+                                             SpanArgs{tbase, slot_stride, seq_stride, V, n_chunks, chunk, n_tslots, xcd_affine, B,
+                                                      m_per_seq, m_chunks, m_B});
 }
 
 // combine the chunk partials of row r (one wave)
@@ -3396,7 +3407,10 @@ __device__ __forceinline__ uint4 lean_finish16(uint4 w, const char* row, int64_t
     return make_uint4(ws[0], ws[1], ws[2], ws[3]);
 }
 
-template <int DT, int NST, bool GREEDY = false>
+// NP: the tail wave's lane passes of 64 spans each.  launch_draw_lean_t takes NP = 1 for rows of at
+// most 64 spans (the bench's 63): a second pass would hold nothing, yet its decode, exp, log, key,
+// selects and ballots would issue in the one wave every row's output waits for.
+template <int DT, int NST, bool GREEDY = false, int NP = 2>
 __global__ void __launch_bounds__(kThreads)
 k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, uint32_t* cnt, int32_t poll,
             uint64_t seed, uint64_t offset, const uint64_t* offset_dev, DrawLeanRest R) {
@@ -3589,15 +3603,15 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
     if (SD_TAIL_PRIO) __builtin_amdgcn_s_setprio(3);
     const float2* pr = reinterpret_cast<const float2*>(A.part + (int64_t)r * A.pstride);
     float M = -INFINITY;
-    float mk[2], sk[2], yk[2];
-    int32_t jk[2];
-    bool dk[2] = {false, false};   // GREEDY: the span's dirty flag
-    const int npass = (A.n_span + kWave - 1) / kWave;   // <= 2 (host: n_span <= 128)
+    float mk[NP], sk[NP], yk[NP];
+    int32_t jk[NP];
+    bool dk[NP] = {};   // GREEDY: the span's dirty flag
+    const int npass = NP == 1 ? 1 : (A.n_span + kWave - 1) / kWave;   // <= NP (host: n_span <= 64 NP)
     // the span race's Gumbel noise, one span per lane and pass, before the wait (off the chain)
-    float gk[2] = {0.f, 0.f};
+    float gk[NP] = {};
     if constexpr (!GREEDY) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NP; ++q) {
             const int k = q * kWave + lane;
             if (q < npass && k < A.n_span) gk[q] = span_gumbel(A.noise, (uint32_t)r, (uint32_t)k);
         }
@@ -3605,10 +3619,10 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
     if (A.poll) {
         // every other span's record, re-read until its tag is this launch's; this span's own from
         // registers (the lane that would hold it)
-        bool have[2];
-        uint4 rec[2];
+        bool have[NP];
+        uint4 rec[NP];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NP; ++q) {
             const int k = q * kWave + lane;
             have[q] = !(q < npass && k < A.n_span) || k == c;
             rec[q] = make_uint4(0u, 0u, 0u, 0u);
@@ -3616,13 +3630,13 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
         uint64_t sw_ = 0; for (int spin = 0;; ++spin) {
             if (A.spin_limit >= 0) {   // < 0: the test hook, every record counts as lost
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
+                for (int q = 0; q < NP; ++q) {
                     if (!have[q]) {
                         rec[q] = ld_coh16(pr + 2 * (q * kWave + lane));
                         have[q] = rec[q].w == draw_tag(epoch, r, q * kWave + lane, A.n_span);
                     }
                 }
-                if (__all(have[0] && have[1])) break;
+                if (__all(have[0] && have[NP - 1])) break;
             }
             if (!spin_more(spin, A.spin_limit, sw_)) {   // bounded: ~tens of ms; the row is flagged, never a hang
                 xstat = SD_ROW_EXCHANGE_TIMEOUT | SD_ROW_INVALID_DIST;
@@ -3632,7 +3646,7 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
         }
         SD_TSL(ts_wg, 4);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NP; ++q) {
             const int k = q * kWave + lane;
             mk[q] = -INFINITY; sk[q] = 0.f; yk[q] = -INFINITY; jk[q] = -1;
             if (k == c) {
@@ -3648,7 +3662,7 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
         }
     } else {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < NP; ++q) {
         const int k = q * kWave + lane;
         mk[q] = -INFINITY; sk[q] = 0.f; yk[q] = -INFINITY; jk[q] = -1;
         if (q < npass && k < A.n_span) {
@@ -3661,9 +3675,9 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
     }
     }
     M = wave_max_ord(M);   // the tail's maxima: finite or -inf records, never NaN
-    float wk[2], S = 0.f;
+    float wk[NP], S = 0.f;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < NP; ++q) {
         wk[q] = mk[q] > -INFINITY || sk[q] != sk[q] ? sk[q] * sd_exp(mk[q] - M) : 0.f;
         S += wk[q];
     }
@@ -3673,9 +3687,9 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
         const float inv = 1.0f / S;
         const float pst = ok ? prob_exact<DT>(M, M, S, inv) : 0.f;
         int32_t cand = INT_MAX;
-        bool resc[2];
+        bool resc[NP];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NP; ++q) {
             const int k = q * kWave + lane;
             const bool in = q < npass && k < A.n_span;
             const bool qual = in && (!ok || (mk[q] > -INFINITY && prob_exact<DT>(mk[q], M, S, inv) == pst));
@@ -3688,7 +3702,7 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
         int32_t bi = INT_MAX;
         if (cand != INT_MAX) { bv = ok ? pst : -INFINITY; bi = cand; }
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NP; ++q) {
             uint64_t mask = __ballot(resc[q]);
             while (mask) {
                 const int k = q * kWave + __builtin_ctzll(mask);
@@ -3717,10 +3731,10 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
     }
     // span pick by a Gumbel race: argmax_c (m_c + ln S_c + g_c) picks span c with probability
     // S_c e^(m_c) / Σ — independent of M and S, so its wave max runs beside theirs (no fp64 scan)
-    float key[2];
+    float key[NP];
     float kmax = -INFINITY;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < NP; ++q) {
         key[q] = mk[q] > -INFINITY && sk[q] > 0.f ? mk[q] + __logf(sk[q]) + gk[q] : -INFINITY;
         kmax = fmaxf(kmax, key[q]);
     }
@@ -3728,7 +3742,7 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
     int pick = -1;
     if (kmax > -INFINITY) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NP; ++q) {
             const uint64_t hit = __ballot(key[q] == kmax);
             if (pick < 0 && hit) pick = q * kWave + __builtin_ctzll(hit);
         }
@@ -3737,8 +3751,8 @@ k_draw_lean(const char* rows, int64_t stride_bytes, int32_t V, int32_t n_span, u
     float yx = -INFINITY;
     if (pick >= 0) {
         const int q = pick / kWave, src = pick & 63;
-        x = __builtin_amdgcn_readlane(q == 0 ? jk[0] : jk[1], src);
-        yx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q == 0 ? yk[0] : yk[1]), src));
+        x = __builtin_amdgcn_readlane(q == 0 ? jk[0] : jk[NP - 1], src);
+        yx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q == 0 ? yk[0] : yk[NP - 1]), src));
     }
     if (lane == 0) {
         int32_t st = SD_ROW_DONE | xstat;
@@ -3964,7 +3978,8 @@ int resident_cap(const void* kern, int threads, size_t dyn) {
 }
 
 // the fused kernel of P's dtype and FAST case, in block-id or ticket order
-using FusedKernel = void (*)(const char*, int64_t, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, sd::Plan, int, int);
+using FusedKernel = void (*)(const char*, int64_t, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint32_t, uint32_t,
+                             uint32_t, sd::Plan, int, int);
 FusedKernel fused_kernel(const sd::Plan& P, bool ticket) {
     return dispatch_dtype(P.tdt, [&](auto dt_) {
         return dispatch_bool(P.fast(), [&](auto fast_) {
@@ -3981,7 +3996,9 @@ FusedKernel fused_kernel(const sd::Plan& P, bool ticket) {
 // SD_OPT_ARG_FAST = 0, passes a null base and the kernel looks the row up in P.trow.
 sd::SpanArgs span_args(const sd::Plan& P) {
     const int64_t esz = P.tdt == SD_F32 ? 4 : 2;
-    sd::SpanArgs fa{nullptr, 0, P.tstride * esz, P.V, P.n_chunks, P.chunk, P.n_tslots, P.xcd_affine, P.B};
+    const sd_fused_index ix = sd_fused_index_make(P.B, P.n_tslots, P.n_chunks, P.xcd_affine);
+    sd::SpanArgs fa{nullptr, 0, P.tstride * esz, P.V, P.n_chunks, P.chunk, P.n_tslots, P.xcd_affine, P.B,
+                    ix.m_per_seq, ix.m_chunks, ix.m_B};
     if (opt(g_opt_arg_fast) == 0 || P.tdt == SD_F32 || P.n_tslots < 1) return fa;
     const char* base = static_cast<const char*>(P.trow[0]);
     const int64_t d = P.n_tslots > 1 ? static_cast<const char*>(P.trow[1]) - base : 0;
@@ -4002,12 +4019,16 @@ int32_t launch_fused(const sd::Plan& P, void* stream) {
     // ticket mode: every label gets ceil(B / labels) sequences' workgroups (stats_body)
     const int64_t seqs = P.ticket ? (int64_t)P.labels * ((P.B + P.labels - 1) / P.labels) : P.B;
     const int64_t total = P.ticket ? seqs * (P.n_tslots * P.n_chunks + 1 + P.n_samp) : head + (int64_t)P.B * P.n_samp;
+    // block-id order splits the id by multiplying (sd_index.h).  Every resident grid is far inside its
+    // range (at most 1024 spans and deciders, 512 samplers a sequence: tests/test_fused_index_cpu.py),
+    // so a shape outside it is a caller's error, not a case for the two launches
+    if (!P.ticket && !sd_fused_index_ok(P.B, P.n_tslots, P.n_chunks, P.n_samp)) return SD_ERR_INVALID;
     sd::Plan Q = P;
     Q.kpoll = 1;
     const sd::SpanArgs fa = span_args(P);
     const int32_t st = launch(fused_kernel(P, P.ticket != 0), dim3((uint32_t)total), dim3(kThreads), 0, stream, fa.tbase,
                               fa.slot_stride, fa.seq_stride, fa.V, fa.n_chunks, fa.chunk, fa.n_tslots, fa.xcd_affine, fa.B,
-                              Q, 0, P.n_tslots);
+                              fa.m_per_seq, fa.m_chunks, fa.m_B, Q, 0, P.n_tslots);
     return st == SD_OK ? 1 : st;
 }
 
@@ -4145,8 +4166,8 @@ bool draw_lean_ok(const sd::Plan& P) {
     return P.t_fast() && P.tdt != SD_F32 && al && P.V >= 8 && (P.V + span - 1) / span <= 128;
 }
 
-template <int DT, int NST, bool GREEDY = false>
-int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
+template <int DT, int NST, bool GREEDY, int NP>
+int32_t launch_draw_lean_np(const sd::Plan& P, int32_t n_span, void* stream) {
     DrawLean A{};
     A.rows = static_cast<const char*>(P.trow[0]);
     A.stride_bytes = P.tstride * 2;
@@ -4156,17 +4177,30 @@ int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
     A.token_prob = P.token_prob; A.row_stats = P.row_stats; A.row_status = P.row_status; A.words_used = P.words_used;
     A.noise = P.noise;
     A.V = P.V;
-    A.n_span = (int32_t)((P.V + NST * kThreads * 8 - 1) / (NST * kThreads * 8));
+    A.n_span = n_span;
+    if (n_span < 1 || n_span > kWave * NP) return SD_ERR_INVALID;   // the tail stages 64 spans per lane pass
     A.pstride = (A.n_span + 7) & ~7;
     // poll mode needs every row's consumer resident while it waits: at most half the workgroups
     // the device holds at once (occupancy x CUs, queried once per device) are consumers
-    const int cap = resident_cap((const void*)k_draw_lean<DT, NST, GREEDY>);
+    const int cap = resident_cap((const void*)k_draw_lean<DT, NST, GREEDY, NP>);
     A.poll = cap > 0 && 2 * P.B <= cap && poll_allowed();
     A.spin_limit = P.spin_limit;
     A.status_or = P.status_or;
     A.ts = P.ts;
-    return launch(k_draw_lean<DT, NST, GREEDY>, dim3(A.n_span, P.B), dim3(kThreads), 0, stream, A.rows, A.stride_bytes,
+    return launch(k_draw_lean<DT, NST, GREEDY, NP>, dim3(A.n_span, P.B), dim3(kThreads), 0, stream, A.rows, A.stride_bytes,
                   A.V, A.n_span, A.cnt, A.poll, A.noise.seed, A.noise.offset, A.noise.offset_dev, draw_lean_rest(A));
+}
+
+// the tail's lane passes (k_draw_lean's NP): one for rows of at most 64 spans.  The greedy tail keeps
+// its two passes: a second instantiation would share greedy_rescan with the first, which the compiler
+// then no longer inlines into either.
+template <int DT, int NST, bool GREEDY = false>
+int32_t launch_draw_lean_t(const sd::Plan& P, void* stream) {
+    const int64_t span = (int64_t)NST * kThreads * 8;
+    const int32_t n_span = (int32_t)((P.V + span - 1) / span);   // the one span count: the grid's, the records', the tail's
+    if constexpr (GREEDY) return launch_draw_lean_np<DT, NST, GREEDY, 2>(P, n_span, stream);
+    else return n_span <= kWave ? launch_draw_lean_np<DT, NST, GREEDY, 1>(P, n_span, stream)
+                                : launch_draw_lean_np<DT, NST, GREEDY, 2>(P, n_span, stream);
 }
 
 // The one-launch verify of a few sequences (sd_verify_lean.inc): 1 launched, 0 not applicable (the
