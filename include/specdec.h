@@ -327,6 +327,7 @@ typedef enum {
     SD_PATH_VERIFY_TREE = 8,        /* sd_verify_tree: k_stats, k_tree_mass x (C_max+1), k_tree_walk */
     SD_PATH_VERIFY_TREE_DISTINCT = 9,   /* sd_verify_tree_distinct: k_stats, k_treed_rowsum, k_treed_walk */
     SD_PATH_VERIFY_TREE_DYNAMIC = 10,   /* sd_verify_tree_dynamic: the distinct kernels, device parents      */
+    SD_PATH_VERIFY_BLOCK = 11,      /* sd_verify_block: k_stats, k_block_mass, k_block_walk            */
     SD_PATH_SAMPLE_DRAW_LEAN = 16, /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
@@ -1119,6 +1120,95 @@ typedef struct {
 
 size_t sd_verify_tree_dynamic_workspace_size(int32_t batch, int32_t num_nodes, int32_t vocab);
 int32_t sd_verify_tree_dynamic(const sd_tree_dynamic_args* args, void* stream);
+
+/* ---- Block verification (csrc/sd_verify_block.inc; additive, ABI 12) --------------------------------
+ * One verify step of ONE drafted chain per sequence that tests the drafted block jointly (Sun,
+ * Mendlovic, Leviathan et al., "Block Verification Accelerates Speculative Decoding", ICLR 2025)
+ * instead of token by token.  It is lossless, reads the rows sd_verify reads, and never accepts fewer
+ * tokens in expectation than the token-wise rule on the same rows and drafts.  Probabilities are
+ * SD_RULE_SPEC's: P_t the processed, dtype-rounded target row t = 0..γ' (row γ' is the bonus row),
+ * Q_t that of drafter row t = 0..γ'-1, x_t = tok[t]; target and drafter rows share ONE processor and
+ * one dtype, as in sd_verify_multi.  Per sequence:
+ *
+ *   w_0 = 1
+ *   for t in 0..γ'-1:  a = P_t[x_t] / Q_t[x_t]         fp32; a NaN ratio (0/0, an id outside the
+ *                                                      vocabulary) counts as +inf: SPEC's test accepts there
+ *                      w_{t+1} = 0 if w_t == 0 else min(1, w_t * a)          fp32; never NaN
+ *   for t in 0..γ'-1:  S_t = Σ_v max(w_t * P_t[v] - Q_t[v], 0)
+ *                      each element is fmaf(w_t, P_t[v], -Q_t[v]) in fp32 (one rounding; at w_t = 1 it
+ *                      is the rounded p - q of sd_verify and sd_verify_multi), elements are summed in
+ *                      fp32 per 2048-element chunk, the chunk totals in fp64 in chunk order
+ *   h_t  = S_t / (S_t + 1 - w_t)   for 1 <= t < γ'     fp64, rounded to float; a divisor <= 0 gives 0
+ *   h_γ' = w_γ'
+ *   n = the LARGEST t in 1..γ' with not (u_t > h_t), else 0      u_t = the row's accept uniform t-1
+ *   n == γ':  x ~ P_γ'                                SD_ROW_BONUS,    resample_mass = NaN
+ *   else:     x ~ max(w_n * P_n - Q_n, 0) / S_n       SD_ROW_RESIDUAL, resample_mass = (float)S_n
+ *
+ * The tests are independent of one another (every u_t is compared, the largest passing t wins), which
+ * is what lets a rejected early draft be rescued by a later one.  With γ' = 1, h_1 = min(1, p/q), so
+ * n, the status, the stop scan and the prune lengths are sd_verify(SD_RULE_SPEC)'s; so are they for any
+ * γ' whose ratios are all >= 1.  Greedy: the same rule with x the argmax of the exit's weights, lowest
+ * index first.
+ * After the walk: the stop scan over tok[:n] (SD_ROW_STOP_IN_DRAFTS, stop_index, no token drawn,
+ * next_token = -1), the prune lengths, tokens_out / pad_token and status_or, as sd_verify_multi; an exit
+ * whose mass is zero or not finite is flagged SD_ROW_INVALID_DIST and draws nothing.
+ * Noise is SD_NOISE_PHILOX only (SD_NOISE_STREAM: SD_ERR_UNSUPPORTED): sequence b is row row_base + b,
+ * the sample is drawn by inverse CDF on the row's cdf uniform; one call consumes one offset.
+ * Limits: γ' 1..SD_MAX_GAMMA, B 1..SD_MULTI_MAX_ROWS, V as sd_verify_multi.
+ * Kernels: the row statistics of the 2γ'+1 rows per sequence, ONE launch over (sequence, t, chunk) that
+ * writes the chunk totals of every S_t and of the bonus row (each workgroup forms its own w_t from
+ * the 2t scalars it depends on), one launch that walks and samples.  Launch boundaries only.        */
+typedef struct {
+    int32_t batch;               /* B, 1..SD_MULTI_MAX_ROWS                                         */
+    int32_t gamma;               /* γ', 1..SD_MAX_GAMMA                                             */
+    int32_t vocab;
+    /* target row t of sequence b at target_rows[t] + b * target_stride_b (t = γ' is the bonus row),
+       drafter row t at draft_rows[t] + b * draft_stride_b                                          */
+    const void* target_rows[SD_MAX_GAMMA + 1];
+    int64_t target_stride_b;
+    int32_t target_dtype;        /* sd_dtype                                                       */
+    const void* draft_rows[SD_MAX_GAMMA];
+    int64_t draft_stride_b;
+    int32_t draft_dtype;         /* must equal target_dtype (SD_ERR_UNSUPPORTED otherwise)          */
+    const int64_t* draft_tokens; /* [B, >=γ'] drafted ids                                           */
+    int64_t draft_tokens_stride_b;
+    sd_processor proc;           /* the loop's logits_processor, for target and drafter rows       */
+    const int64_t* stop_tokens;  /* device [n_stop]                                                */
+    int32_t n_stop;
+    int64_t pad_token;           /* fills tokens_out past the emitted tokens                        */
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+
+    /* outputs, device, [B] */
+    int32_t* n_accepted;         /* n                                                              */
+    int64_t* next_token;         /* x, -1 if none                                                  */
+    float* resample_mass;        /* (float)S_n on a residual exit, NaN on a bonus exit (nullable)   */
+    int32_t* prune_drafter;      /* γ'-n on a residual exit, else 0 (nullable)                      */
+    int32_t* prune_target;       /* γ'-n+1 on a residual exit, else 0 (nullable)                    */
+    int32_t* stop_index;         /* position of the stop token in tok[:n], -1 (nullable)            */
+    int32_t* row_status;         /* SD_ROW_* bits                                                  */
+    /* optional (nullable): int64 [B, >=γ'+1] at tokens_out + b * tokens_out_stride_b: tok[:n], then x
+       (when one was drawn), then pad_token up to γ'+1 entries                                      */
+    int64_t* tokens_out;
+    int64_t tokens_out_stride_b;
+    /* diagnostics (nullable): w_0..w_γ' as float [B, γ'+1] at weights + b * (γ'+1); h_1..h_γ' as
+       float [B, γ'] at accept_prob + b * γ'                                                        */
+    float* weights;
+    float* accept_prob;
+
+    void* workspace;             /* sd_verify_block_workspace_size bytes, zero-filled once; shares
+                                    the other entry points' convention (counter block left at zero) */
+    size_t workspace_bytes;
+    /* optional hints (nullable), as sd_verify_multi's: drafter row t of sequence b at
+       draft_row_stats + 2 * (t * draft_row_stats_stride + b), stride >= B; draft_row_keep at the
+       same layout, needed with the stats under a top-k / nucleus processor                         */
+    const float* draft_row_stats;
+    int64_t draft_row_stats_stride;
+    const struct sd_row_keep* draft_row_keep;
+    int32_t* status_or;          /* nullable: every sequence's SD_ROW_ERROR_MASK bits ORed in       */
+} sd_block_args;
+
+size_t sd_verify_block_workspace_size(int32_t batch, int32_t gamma, int32_t vocab);
+int32_t sd_verify_block(const sd_block_args* args, void* stream);
 
 #ifdef __cplusplus
 }

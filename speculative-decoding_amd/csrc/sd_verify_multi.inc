@@ -403,6 +403,58 @@ void carve_multi(sd::Plan& P, sd::Multi& M, Carve& c, int B, int K, int gamma, i
     M.bbest = c.take<float2>((size_t)B * K * M.n_mchunks);
 }
 
+// The host set-up the chain-row verifies share (sd_verify_multi, sd_verify_block): `rows` chains of 2γ'+1
+// rows each (γ'+1 target slots, then γ' drafter slots) under one processor and one dtype, the drafts, the
+// stop list, the noise, the outputs and the drafter rows' hints of an args struct laid out as sd_multi_args
+template <class Args>
+void chain_rows_plan(sd::Plan& P, const Args* a, int rows, int64_t tstride, int64_t dstride, int64_t tok_stride) {
+    P.B = rows; P.gamma = a->gamma; P.V = a->vocab; P.rule = SD_RULE_SPEC;
+    P.n_tslots = a->gamma + 1; P.n_dslots = a->gamma;
+    P.slots = P.n_tslots + P.n_dslots;
+    P.stat_slots = P.slots;
+    P.tdt = P.ddt = a->target_dtype;
+    P.t_keep = P.d_keep = needs_keep(a->proc);
+    P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
+    P.tT = P.dT = a->proc.temperature;
+    for (int t = 0; t <= a->gamma; ++t) P.trow[t] = a->target_rows[t];
+    for (int t = 0; t < a->gamma; ++t) P.drow[t] = a->draft_rows[t];
+    P.tstride = tstride; P.dstride = dstride;
+    P.draft_tokens = a->draft_tokens; P.tok_stride = tok_stride;
+    P.stops = a->stop_tokens; P.n_stop = a->n_stop;
+    P.noise = a->noise;
+    P.n_accepted = a->n_accepted; P.next_token = a->next_token; P.next_token_stride = 1;
+    P.resample_mass = a->resample_mass; P.prune_drafter = a->prune_drafter; P.prune_target = a->prune_target;
+    P.stop_index = a->stop_index; P.row_status = a->row_status;
+    P.status_or = a->status_or;
+    // the drafter rows' statistics (and keeps) that came with the draws: a hint, as sd_verify's
+    if (a->draft_row_stats && (!P.d_keep || a->draft_row_keep)) {
+        P.dstats = reinterpret_cast<const float2*>(a->draft_row_stats);
+        P.dstats_stride = a->draft_row_stats_stride;
+        P.stat_slots = P.n_tslots;
+        if (P.d_keep) P.dkeep = reinterpret_cast<const RowKeep*>(a->draft_row_keep);
+    }
+    set_stats_chunks(P, P.B * P.stat_slots);
+}
+
+// ... and their statistics launches on the carved Plan: the threshold search when the processor keeps a
+// subset, k_stats over every row the draws did not cover, k_multi_rowstat
+int32_t launch_chain_rows_stats(sd::Plan& P, const sd_processor& proc, void* stream) {
+    if (P.t_keep) {
+        sd::Plan Q = P;                  // the drafter rows' keeps came with their draws: skip them
+        if (P.dkeep) Q.d_keep = 0;
+        if (int32_t st = launch_threshold(Q, proc, proc, stream, /*allow_poll=*/false)) return st;
+    }
+    set_rchunks(P);
+    // at most 65535 grid rows per launch
+    const int per = 65535 / P.B < 1 ? 1 : 65535 / P.B;
+    for (int lo = 0; lo < P.stat_slots; lo += per) {
+        const int cnt = P.stat_slots - lo < per ? P.stat_slots - lo : per;
+        if (int32_t st = launch_stats_group(P, P.tdt, P.t_fast(), lo, cnt, false, stream)) return st;
+    }
+    const int total_rows = P.B * P.slots, wpb = sd::kThreads / sd::kWave;
+    return launch(sd::k_multi_rowstat, dim3((total_rows + wpb - 1) / wpb), dim3(sd::kThreads), 0, stream, P);
+}
+
 // 0: a shape sd_verify_multi takes; else the status it returns for it
 int32_t multi_shape_status(int64_t B, int64_t K, int64_t gamma, int64_t vocab) {
     if (B <= 0 || K <= 0 || gamma <= 0 || vocab <= 0) return SD_ERR_INVALID;
@@ -454,31 +506,7 @@ int32_t sd_verify_multi(const sd_multi_args* a, void* stream) {
 
     sd::Plan P{};
     sd::Multi M{};
-    P.B = rows; P.gamma = a->gamma; P.V = a->vocab; P.rule = SD_RULE_SPEC;
-    P.n_tslots = a->gamma + 1; P.n_dslots = a->gamma;
-    P.slots = P.n_tslots + P.n_dslots;
-    P.stat_slots = P.slots;
-    P.tdt = P.ddt = a->target_dtype;
-    P.t_keep = P.d_keep = needs_keep(a->proc);
-    P.t_stoch = a->proc.kind != SD_PROC_GREEDY;
-    P.tT = P.dT = a->proc.temperature;
-    for (int t = 0; t <= a->gamma; ++t) P.trow[t] = a->target_rows[t];
-    for (int t = 0; t < a->gamma; ++t) P.drow[t] = a->draft_rows[t];
-    P.tstride = a->target_stride_r; P.dstride = a->draft_stride_r;
-    P.draft_tokens = a->draft_tokens; P.tok_stride = a->draft_tokens_stride_r;
-    P.stops = a->stop_tokens; P.n_stop = a->n_stop;
-    P.noise = a->noise;
-    P.n_accepted = a->n_accepted; P.next_token = a->next_token; P.next_token_stride = 1;
-    P.resample_mass = a->resample_mass; P.prune_drafter = a->prune_drafter; P.prune_target = a->prune_target;
-    P.stop_index = a->stop_index; P.row_status = a->row_status;
-    P.status_or = a->status_or;
-    // the drafter rows' statistics (and keeps) that came with the draws: a hint, as sd_verify's
-    if (a->draft_row_stats && (!P.d_keep || a->draft_row_keep)) {
-        P.dstats = reinterpret_cast<const float2*>(a->draft_row_stats);
-        P.dstats_stride = a->draft_row_stats_stride;
-        P.stat_slots = P.n_tslots;
-        if (P.d_keep) P.dkeep = reinterpret_cast<const RowKeep*>(a->draft_row_keep);
-    }
+    chain_rows_plan(P, a, rows, a->target_stride_r, a->draft_stride_r, a->draft_tokens_stride_r);
     M.B = a->batch; M.K = a->num_drafts; M.gamma = a->gamma;
     M.pad_token = a->pad_token;
     M.winner = a->winner; M.n_rejects = a->n_sibling_rejects;
@@ -488,21 +516,7 @@ int32_t sd_verify_multi(const sd_multi_args* a, void* stream) {
     carve_multi(P, M, c, a->batch, a->num_drafts, a->gamma, a->vocab);
 
     g_verify_path = SD_PATH_NONE;
-    if (P.t_keep) {
-        sd::Plan Q = P;                  // the drafter rows' keeps came with their draws: skip them
-        if (P.dkeep) Q.d_keep = 0;
-        if (int32_t st = launch_threshold(Q, a->proc, a->proc, stream, /*allow_poll=*/false)) return st;
-    }
-    set_rchunks(P);
-    // the statistics of every row the draws did not cover; at most 65535 grid rows per launch
-    const int per = 65535 / P.B < 1 ? 1 : 65535 / P.B;
-    for (int lo = 0; lo < P.stat_slots; lo += per) {
-        const int cnt = P.stat_slots - lo < per ? P.stat_slots - lo : per;
-        if (int32_t st = launch_stats_group(P, P.tdt, P.t_fast(), lo, cnt, false, stream)) return st;
-    }
-    const int total_rows = P.B * P.slots, wpb = sd::kThreads / sd::kWave;
-    if (int32_t st = launch(sd::k_multi_rowstat, dim3((total_rows + wpb - 1) / wpb), dim3(sd::kThreads), 0, stream, P))
-        return st;
+    if (int32_t st = launch_chain_rows_stats(P, a->proc, stream)) return st;
     return dispatch_dtype(P.tdt, [&](auto dt_) -> int32_t {
         constexpr int DT = decltype(dt_)::value;
         for (int j = 1; j <= M.K + 1; ++j) {

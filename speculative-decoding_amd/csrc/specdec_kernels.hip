@@ -25,6 +25,8 @@
 //
 // The multi-draft verify (sd_verify_multi, sd_verify_multi.inc): k_stats, then K + 1 mass launches over
 // every (chain, depth) row pair and one walk-and-draw launch; launch boundaries only.
+// The block verify (sd_verify_block, sd_verify_block.inc): k_stats, ONE mass launch over every (sequence, depth)
+// row pair with the prefix weight formed in the workgroup, and one walk-and-draw launch.
 // The token-tree verify (sd_verify_tree, sd_verify_tree.inc): k_stats over the tree's rows in row groups,
 // then C_max + 1 mass launches over the slots that still have a j-th child and one walk-and-draw launch.
 // Its distinct-children form (sd_verify_tree_distinct, sd_verify_tree_distinct.inc): k_stats over the
@@ -4686,6 +4688,7 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
 
 #include "sd_ngram.inc"
 #include "sd_verify_multi.inc"
+#include "sd_verify_block.inc"
 #include "sd_verify_tree.inc"
 #include "sd_verify_tree_distinct.inc"
 #include "sd_verify_tree_dynamic.inc"

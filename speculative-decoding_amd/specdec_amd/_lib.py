@@ -44,6 +44,7 @@ SD_PATH_VERIFY_VP = 7
 SD_PATH_VERIFY_TREE = 8
 SD_PATH_VERIFY_TREE_DISTINCT = 9
 SD_PATH_VERIFY_TREE_DYNAMIC = 10
+SD_PATH_VERIFY_BLOCK = 11
 SD_PATH_SAMPLE_DRAW_LEAN, SD_PATH_SAMPLE_DRAW, SD_PATH_SAMPLE_NUCLEUS, SD_PATH_SAMPLE_STREAM = 16, 17, 18, 19
 SD_PATH_SAMPLE_GREEDY_LEAN, SD_PATH_SAMPLE_MULTI = 20, 21
 PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PATH_VERIFY_FUSED: "k_verify_fused",
@@ -54,6 +55,7 @@ PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PAT
               SD_PATH_VERIFY_TREE: "k_stats+k_tree_mass+k_tree_walk",
               SD_PATH_VERIFY_TREE_DISTINCT: "k_stats+k_treed_rowsum+k_treed_walk",
               SD_PATH_VERIFY_TREE_DYNAMIC: "k_stats+k_treed_rowsum+k_treed_walk<dyn>",
+              SD_PATH_VERIFY_BLOCK: "k_stats+k_block_mass+k_block_walk",
               SD_PATH_SAMPLE_DRAW_LEAN: "k_draw_lean", SD_PATH_SAMPLE_DRAW: "k_draw", SD_PATH_SAMPLE_NUCLEUS: "k_draw_nuc",
               SD_PATH_SAMPLE_STREAM: "k_draw_stream", SD_PATH_SAMPLE_GREEDY_LEAN: "k_draw_lean<greedy>",
               SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize"}
@@ -78,7 +80,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_verify_tree_distinct_workspace_size", "sd_verify_tree_distinct",
            "sd_kv_compact",
            "sd_tree_grow_workspace_size", "sd_tree_grow", "sd_tree_select_workspace_size", "sd_tree_select",
-           "sd_verify_tree_dynamic_workspace_size", "sd_verify_tree_dynamic")
+           "sd_verify_tree_dynamic_workspace_size", "sd_verify_tree_dynamic",
+           "sd_verify_block_workspace_size", "sd_verify_block")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -229,6 +232,26 @@ class sd_multi_args(C.Structure):
         ("resample_mass", C.c_void_p), ("n_sibling_rejects", C.c_void_p), ("prune_drafter", C.c_void_p),
         ("prune_target", C.c_void_p), ("stop_index", C.c_void_p), ("row_status", C.c_void_p),
         ("tokens_out", C.c_void_p), ("tokens_out_stride_b", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("draft_row_stats", C.c_void_p), ("draft_row_stats_stride", C.c_int64), ("draft_row_keep", C.c_void_p),
+        ("status_or", C.c_void_p),
+    ]
+
+
+class sd_block_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("gamma", C.c_int32), ("vocab", C.c_int32),
+        ("target_rows", C.c_void_p * (SD_MAX_GAMMA + 1)), ("target_stride_b", C.c_int64),
+        ("target_dtype", C.c_int32),
+        ("draft_rows", C.c_void_p * SD_MAX_GAMMA), ("draft_stride_b", C.c_int64), ("draft_dtype", C.c_int32),
+        ("draft_tokens", C.c_void_p), ("draft_tokens_stride_b", C.c_int64),
+        ("proc", sd_processor), ("stop_tokens", C.c_void_p), ("n_stop", C.c_int32), ("pad_token", C.c_int64),
+        ("noise", sd_noise),
+        ("n_accepted", C.c_void_p), ("next_token", C.c_void_p), ("resample_mass", C.c_void_p),
+        ("prune_drafter", C.c_void_p), ("prune_target", C.c_void_p), ("stop_index", C.c_void_p),
+        ("row_status", C.c_void_p),
+        ("tokens_out", C.c_void_p), ("tokens_out_stride_b", C.c_int64),
+        ("weights", C.c_void_p), ("accept_prob", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("draft_row_stats", C.c_void_p), ("draft_row_stats_stride", C.c_int64), ("draft_row_keep", C.c_void_p),
         ("status_or", C.c_void_p),
@@ -409,6 +432,10 @@ def _load():
     lib.sd_verify_multi_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.sd_verify_multi.restype = C.c_int32
     lib.sd_verify_multi.argtypes = [C.POINTER(sd_multi_args), C.c_void_p]
+    lib.sd_verify_block_workspace_size.restype = C.c_size_t
+    lib.sd_verify_block_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.sd_verify_block.restype = C.c_int32
+    lib.sd_verify_block.argtypes = [C.POINTER(sd_block_args), C.c_void_p]
     lib.sd_verify_tree_workspace_size.restype = C.c_size_t
     lib.sd_verify_tree_workspace_size.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
     lib.sd_verify_tree.restype = C.c_int32

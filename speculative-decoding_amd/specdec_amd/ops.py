@@ -598,6 +598,124 @@ def verify_multi(target, draft, draft_tokens: torch.Tensor, proc, noise, num_dra
     return out
 
 
+# --------------------------------------------------------------------------- block verify
+BLOCK_FIELDS = ("n_accepted", "next_token", "resample_mass", "prune_drafter", "prune_target", "stop_index",
+                "row_status")
+
+
+@dataclass
+class BlockVerifyOut:
+    """``VerifyOut``'s per-sequence outputs of one block verify step, plus the rule's diagnostics:
+    weights fp32 [B, γ+1] (w_0..w_γ) and accept_prob fp32 [B, γ] (h_1..h_γ); tokens_out int64
+    [B, γ+1] (tok[:n], then x, then pad_token_id; None without want_tokens)."""
+    n_accepted: torch.Tensor
+    next_token: torch.Tensor
+    resample_mass: torch.Tensor
+    prune_drafter: torch.Tensor
+    prune_target: torch.Tensor
+    stop_index: torch.Tensor
+    row_status: torch.Tensor
+    weights: torch.Tensor
+    accept_prob: torch.Tensor
+    tokens_out: Optional[torch.Tensor] = None
+
+
+def verify_block(target, draft, draft_tokens: torch.Tensor, proc, noise,
+                 stop_tokens: Optional[torch.Tensor] = None, row_base: int = 0,
+                 draft_row_stats: Optional[torch.Tensor] = None, draft_row_keep: Optional[torch.Tensor] = None,
+                 status_or: Optional[torch.Tensor] = None, pad_token_id: int = 0, want_tokens: bool = True):
+    """One block verify step (sd_verify_block): the γ drafted tokens of one chain per sequence are
+    verified jointly (block verification), which is lossless and accepts at least as many tokens in
+    expectation as ``verify``'s token-wise SD_RULE_SPEC test on the same rows and drafts.
+
+    target: [B, γ+1, V] logits (or γ+1 tensors [B, V]); draft: [B, γ, V] (or γ tensors [B, V]);
+    draft_tokens: int64 [B, >=γ].  proc: one of the five processors, used for target and drafter rows
+    alike.  noise: PhiloxNoise (one offset per call).  draft_row_stats fp32 [γ, S>=B, 2] /
+    draft_row_keep int32 [γ, S, 4]: the drafter rows' statistics as ``sample_rows`` returned them with
+    the draws (hints, as ``verify``'s).  Returns a BlockVerifyOut."""
+    if _user_process(proc) is not None:
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: verify_block fuses the processing "
+                        "of target and drafter rows and cannot run a user _process")
+    spec = proc_spec(proc)
+    if not isinstance(noise, PhiloxNoise):
+        raise TypeError("verify_block needs PhiloxNoise (the rule defines no stream order)")
+    draft_rows = [draft[:, t, :] for t in range(draft.shape[1])] if torch.is_tensor(draft) else list(draft)
+    gamma = len(draft_rows)
+    target_rows = [target[:, t, :] for t in range(target.shape[1])] if torch.is_tensor(target) else list(target)
+    if len(target_rows) != gamma + 1:
+        raise ValueError(f"expected {gamma + 1} target rows, got {len(target_rows)}")
+    B, V = target_rows[0].shape
+    if not 1 <= gamma <= _lib.SD_MAX_GAMMA or not 1 <= B <= _lib.SD_MULTI_MAX_ROWS:
+        raise ValueError(f"verify_block: unsupported shape (batch {B}, gamma {gamma}): gamma in "
+                         f"1..{_lib.SD_MAX_GAMMA}, batch in 1..{_lib.SD_MULTI_MAX_ROWS}")
+    dev, tdt = target_rows[0].device, target_rows[0].dtype
+    t_stride = target_rows[0].stride(0) if B > 1 else 0
+    d_stride = draft_rows[0].stride(0) if B > 1 else 0
+    for name, rows, stride in (("target", target_rows, t_stride), ("draft", draft_rows, d_stride)):
+        for i, t in enumerate(rows):
+            _require_rows(t, f"{name}_rows[{i}]", V)
+            if t.shape[0] != B or t.dtype != tdt or (B > 1 and t.stride(0) != stride) or t.device != dev:
+                raise ValueError("target and draft rows must share batch, dtype, row stride and device")
+    if draft_tokens.dtype != torch.long or draft_tokens.dim() != 2 or draft_tokens.shape[0] != B \
+            or draft_tokens.shape[1] < gamma or draft_tokens.stride(1) != 1 or draft_tokens.device != dev:
+        raise ValueError(f"draft_tokens must be int64 [B, >={gamma}] on {dev}")
+    stops = stop_tokens if stop_tokens is not None else torch.empty(0, dtype=torch.long, device=dev)
+    if stops.dtype != torch.long or stops.device != dev or not stops.is_contiguous():
+        raise ValueError("stop_tokens must be a contiguous int64 device tensor")
+    if draft_row_stats is not None:
+        ds = draft_row_stats
+        if ds.dtype != torch.float32 or ds.dim() != 3 or ds.shape[0] < gamma or ds.shape[1] < B \
+                or ds.shape[2] != 2 or ds.stride(2) != 1 or ds.stride(1) != 2 or ds.device != dev:
+            raise ValueError(f"draft_row_stats must be fp32 [>={gamma}, >={B}, 2] with (max, sum) pairs on {dev}")
+    if draft_row_keep is not None:
+        dk = draft_row_keep
+        if draft_row_stats is None or dk.dtype != torch.int32 or dk.dim() != 3 or dk.shape[0] < gamma \
+                or dk.shape[1] < B or dk.shape[2] != 4 or dk.stride(2) != 1 or dk.stride(1) != 4 \
+                or dk.stride(0) // 4 != draft_row_stats.stride(0) // 2 or dk.device != dev:
+            raise ValueError("draft_row_keep must be int32 [>=gamma, >=B, 4] at draft_row_stats' row stride, "
+                             "and comes with draft_row_stats")
+    # one allocation: next_token (int64) first, then the six 4-byte fields and the two diagnostics
+    n4 = 6 * B + B * (gamma + 1) + B * gamma
+    buf = torch.empty(8 * B + 4 * n4, dtype=torch.uint8, device=dev)
+    nxt = buf[:8 * B].view(torch.long)
+    f4 = buf[8 * B:].view(torch.int32)
+    i32 = [f4[k * B:(k + 1) * B] for k in range(6)]
+    wts = f4[6 * B:6 * B + B * (gamma + 1)].view(torch.float32).view(B, gamma + 1)
+    acc = f4[6 * B + B * (gamma + 1):].view(torch.float32).view(B, gamma)
+    out = BlockVerifyOut(n_accepted=i32[0], next_token=nxt, resample_mass=i32[1].view(torch.float32),
+                         prune_drafter=i32[2], prune_target=i32[3], stop_index=i32[4], row_status=i32[5],
+                         weights=wts, accept_prob=acc,
+                         tokens_out=torch.empty(B, gamma + 1, dtype=torch.long, device=dev) if want_tokens else None)
+    nz, keep = _noise_struct(noise, 0, dev, row_base)
+    ws = _workspace(lib.sd_verify_block_workspace_size(B, gamma, V), dev)
+    a = _lib.sd_block_args()
+    a.batch, a.gamma, a.vocab = B, gamma, V
+    for i, t in enumerate(target_rows):
+        a.target_rows[i] = t.data_ptr()
+    for i, d in enumerate(draft_rows):
+        a.draft_rows[i] = d.data_ptr()
+    a.target_stride_b, a.draft_stride_b = t_stride, d_stride
+    a.target_dtype = a.draft_dtype = _DT[tdt]
+    a.draft_tokens, a.draft_tokens_stride_b = draft_tokens.data_ptr(), max(draft_tokens.stride(0), gamma)
+    a.proc = spec.struct()
+    a.stop_tokens, a.n_stop = (stops.data_ptr() if stops.numel() else None), stops.numel()
+    a.pad_token = int(pad_token_id)
+    a.noise = nz
+    for f in BLOCK_FIELDS + ("weights", "accept_prob"):
+        setattr(a, f, getattr(out, f).data_ptr())
+    if want_tokens:
+        a.tokens_out, a.tokens_out_stride_b = out.tokens_out.data_ptr(), gamma + 1
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if draft_row_stats is not None:
+        a.draft_row_stats, a.draft_row_stats_stride = draft_row_stats.data_ptr(), draft_row_stats.stride(0) // 2
+    if draft_row_keep is not None:
+        a.draft_row_keep = draft_row_keep.data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_verify_block(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_verify_block")
+    del keep
+    return out
+
+
 # --------------------------------------------------------------------------- token-tree verify
 TREE_FIELDS = ("n_accepted", "last_node", "next_token", "resample_mass", "n_sibling_rejects", "stop_index",
                "row_status")

@@ -94,7 +94,12 @@ def _static_caches(drafter, target, total_len):
 
 
 def _speculative_generate(noise, inputs, drafter, target, gamma, logits_processor, max_gen_len, eos_tokens_id,
-                          pad_token_id, use_cache, skip_sample_adjustment, first_target, debug, static_cache=False):
+                          pad_token_id, use_cache, skip_sample_adjustment, first_target, debug, static_cache=False,
+                          verify_step=None, trace=None):
+    """The chain loop.  verify_step: another accept rule on the same rows (block_speculative_generate's), called
+    as verify_step(target_rows, draft_rows, drafts, proc, noise, stop_tokens, draft_row_stats, status_or) and
+    returning ``verify``'s per-sequence outputs; None: ``verify`` under SD_RULE_SPEC.  trace: a list that
+    receives per verify step dict(cur, g, offset, draft_tokens [g], n, x)."""
     spec = proc_spec(logits_processor)
     # what the kernels are handed: the spec, or the processor itself when it has its own _process
     # (ops.processed_rows runs it on the rows first)
@@ -179,9 +184,14 @@ def _speculative_generate(noise, inputs, drafter, target, gamma, logits_processo
                 return input_ids[0, prompt_len:cur].tolist(), drafts_accepted / drafts_speculated
             continue
         trows = [logits[:, cur - 1 + t - start, :] for t in range(g + 1)]   # :135 and bonus row :159
-        out = verify(trows, draft_rows, input_ids[:, cur:cur + g], _lib.SD_RULE_SPEC, kproc, kproc, noise,
-                     stop_t, skip_sample_adjustment=skip_sample_adjustment,
-                     draft_row_stats=dstats[:g] if stash else None, status_or=err)
+        offset = getattr(noise, "offset", None)
+        if verify_step is None:
+            out = verify(trows, draft_rows, input_ids[:, cur:cur + g], _lib.SD_RULE_SPEC, kproc, kproc, noise,
+                         stop_t, skip_sample_adjustment=skip_sample_adjustment,
+                         draft_row_stats=dstats[:g] if stash else None, status_or=err)
+        else:
+            out = verify_step(trows, draft_rows, input_ids[:, cur:cur + g], kproc, noise, stop_t,
+                              dstats[:g] if stash else None, err)
         if err_d is not err:
             err.bitwise_or_(err_d.to(dev))
         n, x, status, stop_index, bits = (int(v) for v in torch.stack([
@@ -189,6 +199,8 @@ def _speculative_generate(noise, inputs, drafter, target, gamma, logits_processo
             err[0].long()]).tolist())
         _lib.raise_row_error(bits | status, "speculative_generate")   # a draft draw's or this verify's
         drafts_accepted += n                                     # :147
+        if trace is not None:
+            trace.append(dict(cur=cur, g=g, offset=offset, draft_tokens=input_ids[0, cur:cur + g].cpu(), n=n, x=x))
         if status & _lib.SD_ROW_STOP_IN_DRAFTS:                  # :150-155
             return input_ids[0, prompt_len:cur + stop_index + 1].tolist(), drafts_accepted / drafts_speculated
         if static:                                               # :163-165 on the device (0 = no-op)

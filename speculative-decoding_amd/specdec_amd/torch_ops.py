@@ -19,6 +19,12 @@ GPU), and callable as ``torch.ops.specdec.*``.
             prune_drafter, prune_target, stop_index, row_status int32 [B])
         One multi-draft verify step over K chains per sequence (sd_verify_multi), Philox noise.
 
+    torch.ops.specdec.verify_block(target [B, γ+1, V], draft [B, γ, V], draft_tokens int64 [B, >=γ],
+                                   stop_tokens int64 [n], kind, temperature, top_k, top_p, seed, offset, row_base)
+        -> (n_accepted int32 [B], next_token int64 [B], resample_mass fp32 [B], prune_drafter, prune_target,
+            stop_index, row_status int32 [B], weights fp32 [B, γ+1], accept_prob fp32 [B, γ])
+        One block verify step (sd_verify_block): the drafted block verified jointly, Philox noise.
+
     torch.ops.specdec.verify_tree(target [B, N+1, V], draft [B, I, V], draft_tokens int64 [B, >=N], parent int[N],
                                   stop_tokens int64 [n], kind, temperature, top_k, top_p, seed, offset, row_base)
         -> (n_accepted, last_node int32 [B], next_token int64 [B], resample_mass fp32 [B], n_sibling_rejects,
@@ -145,6 +151,26 @@ def _(target, draft, draft_tokens, stop_tokens, kind, temperature, top_k, top_p,
     B = target.shape[0]
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
     return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.MULTI_FIELDS)
+
+
+@torch.library.custom_op("specdec::verify_block", mutates_args=())
+def verify_block(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens: Tensor, kind: int,
+                 temperature: float, top_k: int, top_p: float, seed: int, offset: int,
+                 row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """One block verify step (ops.verify_block): target [B, γ+1, V], draft [B, γ, V], draft_tokens int64
+    [B, >=γ]; the seven [B] outputs in ops.BLOCK_FIELDS' order, then weights [B, γ+1] and accept_prob [B, γ]."""
+    out = ops.verify_block(target, draft, draft_tokens, _spec(kind, temperature, top_k, top_p),
+                           PhiloxNoise(seed, offset), stop_tokens=stop_tokens, row_base=row_base, want_tokens=False)
+    # views of one buffer: outputs may not alias
+    return tuple(getattr(out, f).clone() for f in ops.BLOCK_FIELDS + ("weights", "accept_prob"))
+
+
+@verify_block.register_fake
+def _(target, draft, draft_tokens, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
+    B, g = target.shape[0], draft.shape[1]
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.BLOCK_FIELDS) + (
+        target.new_empty(B, g + 1, dtype=torch.float32), target.new_empty(B, g, dtype=torch.float32))
 
 
 @torch.library.custom_op("specdec::verify_tree", mutates_args=())
