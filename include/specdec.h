@@ -409,13 +409,25 @@ int32_t sd_ngram_verify(const sd_ngram_args* args, void* stream);
  * b * len + i; update: b * k + j); the caller advances ts_base by batch * len / batch * k after
  * each call.  Tables: caller-owned device memory, zero-filled once, capacities powers of two.
  * Token ids must lie in [0, 2^17), n in [2, SD_NGRAM_MAX_N]; a full table or a bad token sets a
- * bit in *status (the call still returns SD_OK: the condition is found on the device).          */
+ * bit in *status (the call still returns SD_OK: the condition is found on the device) and the
+ * record is dropped.
+ * Two limits the reference (Python ints) does not have:
+ *   - the record clock: ts_base + the call's records must stay <= 2^27-1, so a store takes
+ *     2^27-1 records between resets; the call that would pass it returns SD_ERR_UNSUPPORTED and
+ *     records nothing.
+ *   - the best key's count field has 20 bits: the count placed in it is clamped to 2^20-1
+ *     (pair_count keeps counting) and SD_NGRAM_SATURATED is set when a pair reaches the clamp.
+ *     Until then the best token is the reference's; among tokens of one gram that all reached the
+ *     clamp it is the one with the earliest latest-ts (the first to get there, call by call),
+ *     where the reference would go on comparing counts.
+ * SD_NGRAM_SATURATED is an additive constant (no layout change): ABI 12.                         */
 #define SD_NGRAM_MAX_N 4
 #define SD_NGRAM_FULL 1
 #define SD_NGRAM_BAD_TOKEN 2
+#define SD_NGRAM_SATURATED 4     /* a (gram, token) count reached 2^20-1, the best key's clamp   */
 typedef struct {
     uint64_t* gram_keys;         /* [gram_capacity] 0 = empty                                   */
-    uint64_t* gram_best;         /* [gram_capacity] count<<44 | (2^27-1-ts)<<17 | token           */
+    uint64_t* gram_best;         /* [gram_capacity] min(count,2^20-1)<<44 | (2^27-1-ts)<<17 | token */
     int64_t gram_capacity;
     uint64_t* pair_keys;         /* [pair_capacity] (gram slot, token)                            */
     uint32_t* pair_count;        /* [pair_capacity]                                               */

@@ -15,12 +15,24 @@
 // packed (count, ~ts, token) key with one 64-bit atomicMax.  Keys only grow (counts only grow), so
 // pairs untouched by a batch keep their earlier contribution.
 //
+// Two limits, both departures from the reference (whose Python ints have none):
+//   - the record clock: ts < 2^27-1, so a store takes 2^27-1 records (positions of initialize,
+//     next tokens of update) between resets; the call that would pass it returns
+//     SD_ERR_UNSUPPORTED and records nothing.
+//   - the count field of the best key has 20 bits: the count placed in the key is clamped to
+//     2^20-1 (pair_count itself keeps counting), and SD_NGRAM_SATURATED is set in *status when a
+//     pair reaches the clamp.  Up to there the best is the reference's.  Among tokens of one gram
+//     that have all reached the clamp, the best is the one with the earliest latest-ts, that is
+//     the key offered by the call in which a token first reached the clamp (later, smaller keys of
+//     a saturated pair lose the atomicMax), where the reference would go on comparing counts.
+//
 // Layout (caller-owned device memory, zero-filled once; sd_ngram_store in specdec.h):
 //   gram table: key u64 = 1<<63 | level<<51 | t0 | t1<<17 | t2<<34 (a gram is 1..3 token ids of
 //               17 bits, level = its order j, so the orders of NGramStorage share one table);
-//               best u64 = count<<44 | (2^27-1-ts)<<17 | token
+//               best u64 = min(count, 2^20-1)<<44 | (2^27-1-ts)<<17 | token
 //   pair table: key u64 = 1<<63 | gram_slot<<17 | token; count u32; latest ts u32
-// Linear probing from a splitmix64 hash; 0 = empty.  A full table sets SD_NGRAM_FULL in *status.
+// Linear probing from a splitmix64 hash; 0 = empty.  A full table sets SD_NGRAM_FULL in *status, a
+// token id outside [0, 2^17) SD_NGRAM_BAD_TOKEN, a count at the clamp SD_NGRAM_SATURATED.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,6 +44,8 @@ constexpr int kThreads = 256;
 constexpr uint64_t kUsed = 1ull << 63;
 constexpr uint32_t kTokBits = 17, kTokMask = (1u << kTokBits) - 1;
 constexpr uint64_t kTsMax = (1ull << 27) - 1;
+constexpr uint32_t kCountShift = 44;
+constexpr uint64_t kCountMax = (1ull << (64 - kCountShift)) - 1;   // the key's count field saturates here
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 30;
@@ -150,8 +164,14 @@ __device__ __forceinline__ void apply(const sd_ngram_store& S, const Rec& R) {
         atomicAdd(S.pair_count + ps, 1u);
         atomicMax(S.pair_ts + ps, R.ts);
     } else {
-        const uint64_t cnt = S.pair_count[ps], ts = S.pair_ts[ps];
-        const uint64_t packed = (cnt << 44) | ((kTsMax - ts) << kTokBits) | (uint64_t)R.token;
+        uint64_t cnt = S.pair_count[ps];
+        const uint64_t ts = S.pair_ts[ps];
+        if (cnt >= kCountMax) {   // cnt << 44 would leave the word: clamp, and say so once
+            cnt = kCountMax;
+            if (!(__hip_atomic_load(S.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & SD_NGRAM_SATURATED))
+                atomicOr(S.status, SD_NGRAM_SATURATED);
+        }
+        const uint64_t packed = (cnt << kCountShift) | ((kTsMax - ts) << kTokBits) | (uint64_t)R.token;
         atomicMax((unsigned long long*)(S.gram_best + gs), (unsigned long long)packed);
     }
 }

@@ -113,6 +113,7 @@ SD_MT_STATE_BYTES = 624 * 4 + 16
 SD_NGRAM_MAX_N = 4
 SD_NGRAM_FULL = 1
 SD_NGRAM_BAD_TOKEN = 2
+SD_NGRAM_SATURATED = 4   # a (gram, token) count reached 2^20-1, the clamp of the best key's count field
 
 
 class sd_ngram_store(C.Structure):

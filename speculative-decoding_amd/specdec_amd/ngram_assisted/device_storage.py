@@ -65,7 +65,8 @@ class _DeviceStore(INgramStorage):
                                       self.n, self._one_level, self.vocab_size)
 
     def status(self) -> int:
-        """SD_NGRAM_* bits raised on the device (table full, token out of range); syncs."""
+        """SD_NGRAM_* bits raised on the device (table full, token out of range, a count at the
+        best key's 2^20-1 clamp); syncs."""
         return int(self._status.item())
 
     def _ids(self, x) -> torch.Tensor:

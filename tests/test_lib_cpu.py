@@ -29,6 +29,21 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib.sd_abi_version() == _lib.SD_ABI_VERSION
 
 
+def test_ngram_store_constants_match_the_header():
+    """The SD_NGRAM_* status bits and limits of the ctypes mirror are the header's; the ABI version
+    stays the header's too (SD_NGRAM_SATURATED is an additive constant, like the additive entry
+    points: no bump)."""
+    from specdec_amd import _lib
+    src = open(HEADER).read()
+    defs = dict(re.findall(r"^#define (SD_NGRAM_\w+|SD_ABI_VERSION)\s+(\d+)", src, re.M))
+    assert set(defs) == {"SD_ABI_VERSION", "SD_NGRAM_MAX_FILLER", "SD_NGRAM_MAX_N", "SD_NGRAM_FULL",
+                         "SD_NGRAM_BAD_TOKEN", "SD_NGRAM_SATURATED"}
+    for name, val in defs.items():
+        assert getattr(_lib, name) == int(val), name
+    bits = [_lib.SD_NGRAM_FULL, _lib.SD_NGRAM_BAD_TOKEN, _lib.SD_NGRAM_SATURATED]
+    assert bits == [1, 2, 4]
+
+
 C_LAYOUT = r"""
 #include <stdio.h>
 #include <stddef.h>
