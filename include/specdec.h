@@ -669,7 +669,7 @@ int32_t sd_verify_multi(const sd_multi_args* args, void* stream);
  * off_{s+1} = off_s + V_s, Σ V_s = V, V_s >= 1 (slices may be uneven and may start at any element).
  * γ' is 0..SD_MAX_GAMMA; γ' = 0 samples the one target row.  Probabilities are SPEC's
  * (round_dt(softmax(round_dt(l / T)))); processors SD_PROC_GREEDY and SD_PROC_MULTINOMIAL at any
- * temperature (top-k / nucleus: SD_ERR_UNSUPPORTED); noise SD_NOISE_PHILOX only (STREAM:
+ * temperature (top-k / nucleus: SD_ERR_UNSUPPORTED here, served by sd_vp_keep_* below); noise SD_NOISE_PHILOX only (STREAM:
  * SD_ERR_UNSUPPORTED); target and drafter rows share one dtype.  Three calls per step, with one
  * all-gather of a few hundred bytes per sequence after each of the first two; logit rows never move:
  *
@@ -784,6 +784,82 @@ size_t sd_vp_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local);
 int32_t sd_vp_stats(const sd_vp_args* args, void* stream);
 int32_t sd_vp_decide(const sd_vp_args* args, void* stream);
 int32_t sd_vp_finish(const sd_vp_args* args, void* stream);
+
+/* ---- Vocabulary-parallel verify under top-k / nucleus (csrc/vp_keep.inc; additive, ABI 12) --------
+ * The same step for SD_PROC_TOPK, SD_PROC_NUCLEUS and SD_PROC_TOPK_NUCLEUS on 16-bit rows (bf16, fp16;
+ * SD_F32: SD_ERR_UNSUPPORTED), through entry points of their own: sd_vp_stats / sd_vp_decide /
+ * sd_vp_finish keep refusing these processors.  The kept set of every row is the one sd_probs and
+ * sd_verify keep on the gathered whole row: top-k keeps x >= tau_k (all ties); the nucleus walks the
+ * order-preserving 16-bit keys downwards, a key's mass being count * p(key),
+ * p(key) = round_dt(exp(x - m) / s) at T = 1, accumulated in fp64, keeps rank 0 always and, among
+ * equal values at the cut, the first t_cut + 1 by global index (ascending shard, then local index);
+ * under top-k + nucleus the nucleus runs on the top-k-masked row.  A search over histograms whose
+ * partial results are small records, merged by every rank in ascending shard order:
+ *
+ *   sd_vp_keep_hist     one pass over the slice of each of the 2γ'+1 rows: the 65536-bin histogram of
+ *                       the keys (kept in the workspace), the local max, per high byte of the key the
+ *                       count and the fp64 masses Σ count * exp(x - m_local) at T = 1 and at the
+ *                       processor's temperature, the drafted id's raw logit and its rank among equal
+ *                       values of the slice at smaller indices -> hist_local: header, sd_vp_keep_stat[B][2γ'+1]
+ *   (exchange A)
+ *   sd_vp_keep_refine   round i = 0..sd_vp_keep_rounds(kind)-1, each followed by an all-gather of
+ *                       bins_local into bins_all[i]: 256 values per row, chosen from hist_all and the
+ *                       rounds before.  Count rounds give the slice's per-key counts of the high-byte
+ *                       bin that holds the k-th largest value (top-k) or the nucleus crossing; the mass
+ *                       round gives the slice's Σ count * p(key) of every high byte, which needs the
+ *                       global normaliser and so cannot ride in exchange A.  Top-k: one count round;
+ *                       nucleus: mass, count; top-k + nucleus: count, mass, count.
+ *   sd_vp_keep_decide   every shard alike: per row the cut key, t_cut, each shard's tie quota and the
+ *                       kept set's (m, Σexp) at temperature T from counts and bin masses alone; p and q
+ *                       of the drafts (a dropped id has probability 0), sd_vp_decide's tests, stop scan,
+ *                       local mass and candidate under the keep predicate -> cand_local (sd_vp_cand[B])
+ *   (exchange C)
+ *   sd_vp_keep_finish   sd_vp_finish's kernel on the candidate blocks.
+ *
+ * A slice holding a NaN or +inf flags its sequence SD_ROW_INVALID_DIST.  The histogram stays in the
+ * workspace from sd_vp_keep_hist to the last sd_vp_keep_refine, so every shard of a step needs a
+ * workspace of its own (shards emulated in one process included).                                  */
+#define SD_VP_KEEP_MAX_ROUNDS 3
+#define SD_VP_KEEP_NONFINITE 0x2        /* sd_vp_keep_stat.flags: the slice holds a NaN or +inf      */
+#define SD_VP_KEEP_COUNTS 1             /* sd_vp_keep_bin.kind                                       */
+#define SD_VP_KEEP_MASSES 2
+
+typedef struct sd_vp_keep_stat {        /* 5136 bytes: one per (sequence, row), exchange A           */
+    float m;                            /* max raw logit of the slice (-inf: nothing above -inf)     */
+    float x_tok;                        /* raw logit of the row's drafted id (SD_VP_STAT_OWNS)       */
+    int32_t tok_rank;                   /* elements of the slice equal to x_tok at a smaller index   */
+    int32_t flags;                      /* SD_VP_STAT_OWNS, SD_VP_KEEP_NONFINITE                     */
+    uint32_t count[256];                /* elements per high byte of the key                         */
+    double mass1[256];                  /* Σ count * exp(x - m), T = 1                               */
+    double massT[256];                  /* Σ count * exp(round_dt(x / T) - round_dt(m / T))          */
+} sd_vp_keep_stat;
+
+typedef struct sd_vp_keep_bin {         /* 2064 bytes: one per (sequence, row), every refine round   */
+    int32_t bin;                        /* count round: the high byte the counts belong to, -1 none  */
+    int32_t kind;                       /* SD_VP_KEEP_COUNTS: val[j] = count of key 256 * bin + j;
+                                           SD_VP_KEEP_MASSES: val[h] = Σ count * p(key) of high byte h */
+    int32_t pad[2];
+    double val[256];
+} sd_vp_keep_bin;
+
+typedef struct {
+    sd_vp_args vp;               /* as for sd_vp_*; stats_local / stats_all are not used            */
+    void* hist_local;            /* written by sd_vp_keep_hist: sd_vp_keep_hist_bytes bytes          */
+    const void* hist_all;        /* S blocks, shard-major: read by refine and decide                */
+    void* bins_local;            /* written by sd_vp_keep_refine: sd_vp_keep_bins_bytes bytes        */
+    const void* bins_all[SD_VP_KEEP_MAX_ROUNDS];   /* round i gathered; refine round r reads i < r   */
+    int32_t round;               /* sd_vp_keep_refine: the round to run                             */
+    int32_t reserved;
+} sd_vp_keep_args;
+
+size_t sd_vp_keep_hist_bytes(int32_t batch, int32_t gamma);
+size_t sd_vp_keep_bins_bytes(int32_t batch, int32_t gamma);
+size_t sd_vp_keep_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local);
+int32_t sd_vp_keep_rounds(int32_t proc_kind);    /* 1, 2, 3 for top-k, nucleus, top-k + nucleus; else 0 */
+int32_t sd_vp_keep_hist(const sd_vp_keep_args* args, void* stream);
+int32_t sd_vp_keep_refine(const sd_vp_keep_args* args, void* stream);
+int32_t sd_vp_keep_decide(const sd_vp_keep_args* args, void* stream);
+int32_t sd_vp_keep_finish(const sd_vp_keep_args* args, void* stream);
 
 /* ---- Token-tree speculative verification (csrc/sd_verify_tree.inc; additive, ABI 12) --------------
  * One verify step over a token tree per sequence (SpecInfer / Medusa / EAGLE): N drafted nodes with

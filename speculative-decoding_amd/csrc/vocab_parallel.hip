@@ -42,7 +42,9 @@ struct VpDecision {      // 48 bytes, one per sequence, decide -> mass -> pick (
     int32_t n, mode, status, stop_index;
     float tm, tS, dm, dS;     // the global (m, S) of the decided target row, and of drafter row n
     int32_t trow;             // the decided target row: n, or γ' on full accept
-    int32_t pad[3];
+    // keep processors (vp_keep.inc): [0] the cut keys of the target row (low half) and of drafter row n,
+    // [1], [2] the slice indices their kept ties end at; else zero
+    int32_t keep[3];
 };
 
 struct Vp {
@@ -86,6 +88,22 @@ __device__ __forceinline__ const void* vp_row(const Vp& P, int b, int r) {
 // processed value y = round_dt(x / T) (greedy / multinomial: no keep mask)
 template <int DT>
 __device__ __forceinline__ float vp_y(float x, float T) { return T != 1.0f ? round_dt<DT>(x / T) : x; }
+
+// keep processors on 16-bit rows: the order-preserving key of a value (-0 shares +0's key, as
+// sd_threshold.inc's), and the predicate of a row: above the cut key, or a tie at it up to slice index tie
+template <int DT>
+__device__ __forceinline__ uint32_t vpk_key(float x) {
+    x += 0.0f;
+    uint32_t h;
+    if constexpr (DT == SD_BF16) h = __float_as_uint(x) >> 16;
+    else h = (uint32_t)__half_as_ushort(__float2half_rn(x));
+    return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
+}
+template <int DT>
+__device__ __forceinline__ bool vpk_kept(float x, int64_t j, uint32_t cut, int32_t tie) {
+    const uint32_t k = vpk_key<DT>(x);
+    return k > cut || (k == cut && j <= (int64_t)tie);
+}
 
 // kVpEpt raw values of a slice row from slice element e0 (0 past the slice's end): 16-byte vectors
 // when the row starts on a 16-byte boundary, guarded element loads when it does not (a slice may
@@ -247,25 +265,29 @@ __global__ void __launch_bounds__(kThreads) k_vp_decide(Vp P) {
 
 // the weights of kVpEpt elements from slice element e0, given their raw values: p of the decided
 // target row, or max(p - q, 0) against drafter row n
-template <int DT>
+template <int DT, bool KEEP>
 __device__ __forceinline__ void vp_weights(const Vp& P, const VpDecision& d, int64_t e0, const float* xt, const float* xd,
                                            float* wv) {
     const bool resid = d.mode == kVpResid;
     const float invT = 1.0f / d.tS, invD = 1.0f / d.dS;
+    const uint32_t tcut = (uint32_t)d.keep[0] & 0xffffu, dcut = (uint32_t)d.keep[0] >> 16;   // KEEP only
 #pragma unroll
     for (int e = 0; e < kVpEpt; ++e) {
         float v = 0.f;
         if (e0 + e < P.Vs) {
             v = prob_exact<DT>(vp_y<DT>(xt[e], P.T), d.tm, d.tS, invT);
+            if constexpr (KEEP) v = vpk_kept<DT>(xt[e], e0 + e, tcut, d.keep[1]) ? v : 0.f;
             if (resid) {
-                const float dlt = v - prob_exact<DT>(vp_y<DT>(xd[e], P.T), d.dm, d.dS, invD);
+                float q = prob_exact<DT>(vp_y<DT>(xd[e], P.T), d.dm, d.dS, invD);
+                if constexpr (KEEP) q = vpk_kept<DT>(xd[e], e0 + e, dcut, d.keep[2]) ? q : 0.f;
+                const float dlt = v - q;
                 v = dlt > 0.f ? dlt : 0.f;
             }
         }
         wv[e] = v;
     }
 }
-template <int DT>
+template <int DT, bool KEEP>
 __device__ __forceinline__ void vp_chunk_weights(const Vp& P, const VpDecision& d, int b, int c, float* wv) {
     const int64_t e0 = (int64_t)c * kVpChunk + threadIdx.x * kVpEpt;
     const void* trow = vp_row<DT>(P, b, d.trow);
@@ -278,10 +300,10 @@ __device__ __forceinline__ void vp_chunk_weights(const Vp& P, const VpDecision& 
 #pragma unroll
         for (int e = 0; e < kVpEpt; ++e) xd[e] = 0.f;
     }
-    vp_weights<DT>(P, d, e0, xt, xd, wv);
+    vp_weights<DT, KEEP>(P, d, e0, xt, xd, wv);
 }
 
-template <int DT>
+template <int DT, bool KEEP = false>
 __global__ void __launch_bounds__(kThreads) k_vp_mass(Vp P) {
     __shared__ float lds[4];
     __shared__ int32_t ldi[4];
@@ -290,7 +312,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_mass(Vp P) {
     if (d.mode == kVpNone) return;                    // no token is drawn: k_vp_pick reads no total
     const int64_t e0 = (int64_t)c * kVpChunk + threadIdx.x * kVpEpt;
     float wv[kVpEpt];
-    vp_chunk_weights<DT>(P, d, b, c, wv);
+    vp_chunk_weights<DT, KEEP>(P, d, b, c, wv);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < kVpEpt; ++e) s += wv[e];
@@ -302,7 +324,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_mass(Vp P) {
     }
 }
 
-template <int DT>
+template <int DT, bool KEEP = false>
 __global__ void __launch_bounds__(kThreads) k_vp_pick(Vp P) {
     __shared__ float lw[kVpMaxChunks];
     __shared__ PickLds L;
@@ -338,7 +360,7 @@ __global__ void __launch_bounds__(kThreads) k_vp_pick(Vp P) {
         } else if (s_pick >= 0) {                     // the element inside the chunk, weights recomputed
             const int pick = s_pick;
             float wv[kVpEpt];
-            vp_chunk_weights<DT>(P, d, b, pick, wv);
+            vp_chunk_weights<DT, KEEP>(P, d, b, pick, wv);
             bool any;
             const int pe = pick_in_chunk<kVpEpt>(wv, s_target, L, &any);
             if (pe >= 0) {
@@ -420,6 +442,8 @@ __global__ void __launch_bounds__(kThreads) k_vp_finish(Vp P) {
 
 }  // namespace sd
 
+#include "vp_keep.inc"
+
 namespace {
 using namespace sd_host;
 
@@ -443,10 +467,20 @@ void vp_carve(sd::Vp& P, Carve& c, int B, int gamma, int vocab_local) {
 
 const dim3 kVpBlock(sd::kThreads);   // every kernel of this unit: 1-D grids of kThreads-wide workgroups
 
-enum VpPhase { kPhaseStats, kPhaseDecide, kPhaseFinish };
+// the sd_vp_keep_* workspace: sd_vp_*'s arrays first, then the rows' key histograms and records
+void vpk_carve(sd::Vp& P, sd::VpK& K, Carve& c, int B, int gamma, int vocab_local) {
+    vp_carve(P, c, B, gamma, vocab_local);
+    const size_t rows = (size_t)B * (2 * gamma + 1);
+    K.hist = c.take<uint32_t>(rows * sd::kVpkStride);
+    K.cmax = c.take<int32_t>(rows * (size_t)vp_chunks(vocab_local));
+    K.rowout = c.take<sd::VpkRowOut>(rows);
+}
 
-// the argument checks of the three entry points (host only, before any launch), then the plan
-int32_t vp_plan(const sd_vp_args* a, VpPhase phase, sd::Vp& P) {
+enum VpPhase { kPhaseStats, kPhaseDecide, kPhaseFinish, kPhaseRefine };
+
+// the argument checks of the entry points (host only, before any launch), then the plan; keep: the
+// sd_vp_keep_* calls, which take the keep processors on 16-bit rows and none of the others
+int32_t vp_plan(const sd_vp_args* a, VpPhase phase, sd::Vp& P, sd::VpK* keep = nullptr) {
     if (!a) return SD_ERR_INVALID;
     const int32_t shape = vp_shape_status(a->batch, a->gamma, a->vocab_local);
     if (shape == SD_ERR_INVALID) return SD_ERR_INVALID;
@@ -458,21 +492,27 @@ int32_t vp_plan(const sd_vp_args* a, VpPhase phase, sd::Vp& P) {
     if (a->noise.mode != SD_NOISE_STREAM && a->noise.mode != SD_NOISE_PHILOX) return SD_ERR_INVALID;
     if (a->n_stop < 0 || (a->n_stop > 0 && !a->stop_tokens)) return SD_ERR_INVALID;
     if (shape != SD_OK) return shape;
-    if (phase != kPhaseFinish) {
+    if (phase != kPhaseFinish && phase != kPhaseRefine) {
         for (int t = 0; t <= a->gamma; ++t)
             if (!a->target_rows[t]) return SD_ERR_INVALID;
         for (int t = 0; t < a->gamma; ++t)
             if (!a->draft_rows[t]) return SD_ERR_INVALID;
         if (a->gamma > 0 && !a->draft_tokens) return SD_ERR_INVALID;
     }
-    if (phase == kPhaseStats && !a->stats_local) return SD_ERR_INVALID;
-    if (phase == kPhaseDecide && (!a->stats_all || !a->cand_local)) return SD_ERR_INVALID;
+    if (phase == kPhaseStats && !keep && !a->stats_local) return SD_ERR_INVALID;
+    if (phase == kPhaseDecide && ((!keep && !a->stats_all) || !a->cand_local)) return SD_ERR_INVALID;
     if (phase == kPhaseFinish && (!a->cand_all || !a->n_accepted || !a->next_token || !a->row_status)) return SD_ERR_INVALID;
     if (a->num_shards > SD_VP_MAX_SHARDS) return SD_ERR_UNSUPPORTED;
-    if (a->proc.kind >= SD_PROC_TOPK) return SD_ERR_UNSUPPORTED;       // a sharded threshold search: not built
+    if (!keep && a->proc.kind >= SD_PROC_TOPK) return SD_ERR_UNSUPPORTED;   // the search over slices: sd_vp_keep_*
+    if (keep) {
+        if (a->proc.kind != SD_PROC_NUCLEUS && a->proc.top_k < 1) return SD_ERR_INVALID;
+        if (a->proc.kind != SD_PROC_TOPK && !(a->proc.top_p > 0.f)) return SD_ERR_INVALID;
+        if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;              // a 32-bit key needs more refine rounds
+    }
     if (a->noise.mode == SD_NOISE_STREAM) return SD_ERR_UNSUPPORTED;   // the reference's stream order needs whole rows
-    if (!a->workspace || a->workspace_bytes < sd_vp_workspace_size(a->batch, a->gamma, a->vocab_local))
-        return SD_ERR_WORKSPACE;
+    const size_t need = keep ? sd_vp_keep_workspace_size(a->batch, a->gamma, a->vocab_local)
+                             : sd_vp_workspace_size(a->batch, a->gamma, a->vocab_local);
+    if (!a->workspace || a->workspace_bytes < need) return SD_ERR_WORKSPACE;
 
     P.B = a->batch; P.gamma = a->gamma; P.V = a->vocab; P.off = a->vocab_offset; P.Vs = a->vocab_local;
     P.shard = a->shard; P.S = a->num_shards; P.n_chunks = vp_chunks(a->vocab_local);
@@ -492,7 +532,33 @@ int32_t vp_plan(const sd_vp_args* a, VpPhase phase, sd::Vp& P) {
     P.prune_drafter = a->prune_drafter; P.prune_target = a->prune_target; P.stop_index = a->stop_index;
     P.row_status = a->row_status; P.owner_shard = a->owner_shard; P.status_or = a->status_or;
     Carve c{static_cast<char*>(a->workspace)};
-    vp_carve(P, c, a->batch, a->gamma, a->vocab_local);
+    if (keep) vpk_carve(P, *keep, c, a->batch, a->gamma, a->vocab_local);
+    else vp_carve(P, c, a->batch, a->gamma, a->vocab_local);
+    return SD_OK;
+}
+
+// sd_vp_keep_*: the keep processors are checked first (the others belong to sd_vp_*), then the plan
+int32_t vpk_plan(const sd_vp_keep_args* k, VpPhase phase, sd::Vp& P, sd::VpK& K) {
+    if (!k) return SD_ERR_INVALID;
+    const sd_vp_args* a = &k->vp;
+    if (a->proc.kind >= SD_PROC_GREEDY && a->proc.kind < SD_PROC_TOPK) return SD_ERR_UNSUPPORTED;
+    const int rounds = sd_vp_keep_rounds(a->proc.kind);
+    if (phase == kPhaseStats && !k->hist_local) return SD_ERR_INVALID;
+    if (phase == kPhaseRefine && (!k->hist_all || !k->bins_local || k->round < 0 || (rounds && k->round >= rounds)))
+        return SD_ERR_INVALID;
+    if (phase == kPhaseRefine || phase == kPhaseDecide) {
+        const int n = phase == kPhaseDecide ? rounds : k->round;
+        if (!k->hist_all) return SD_ERR_INVALID;
+        for (int i = 0; i < n; ++i)
+            if (!k->bins_all[i]) return SD_ERR_INVALID;
+    }
+    if (int32_t st = vp_plan(a, phase, P, &K)) return st;
+    K.a_local = static_cast<char*>(k->hist_local); K.a_all = static_cast<const char*>(k->hist_all);
+    K.b_local = static_cast<char*>(k->bins_local);
+    for (int i = 0; i < SD_VP_KEEP_MAX_ROUNDS; ++i) K.b_all[i] = static_cast<const char*>(k->bins_all[i]);
+    K.a_bytes = (int64_t)sd_vp_keep_hist_bytes(a->batch, a->gamma);
+    K.b_bytes = (int64_t)sd_vp_keep_bins_bytes(a->batch, a->gamma);
+    K.round = k->round; K.kind = a->proc.kind; K.top_k = a->proc.top_k; K.top_p = a->proc.top_p;
     return SD_OK;
 }
 
@@ -545,6 +611,82 @@ int32_t sd_vp_decide(const sd_vp_args* a, void* stream) {
 int32_t sd_vp_finish(const sd_vp_args* a, void* stream) {
     sd::Vp P{};
     if (int32_t st = vp_plan(a, kPhaseFinish, P)) return st;
+    clear_stale_error();
+    if (int32_t st = launch(sd::k_vp_finish, dim3((P.B + sd::kThreads - 1) / sd::kThreads), kVpBlock, 0, stream, P)) return st;
+    g_verify_path = SD_PATH_VERIFY_VP;
+    return SD_OK;
+}
+
+// ---- the step under top-k / nucleus (vp_keep.inc)
+size_t sd_vp_keep_hist_bytes(int32_t batch, int32_t gamma) {
+    if (vp_shape_status(batch, gamma, 1) != SD_OK) return 0;
+    return sizeof(sd_vp_header) + (size_t)batch * (2 * (size_t)gamma + 1) * sizeof(sd_vp_keep_stat);
+}
+
+size_t sd_vp_keep_bins_bytes(int32_t batch, int32_t gamma) {
+    if (vp_shape_status(batch, gamma, 1) != SD_OK) return 0;
+    return sizeof(sd_vp_header) + (size_t)batch * (2 * (size_t)gamma + 1) * sizeof(sd_vp_keep_bin);
+}
+
+size_t sd_vp_keep_workspace_size(int32_t batch, int32_t gamma, int32_t vocab_local) {
+    if (vp_shape_status(batch, gamma, vocab_local) != SD_OK) return 0;
+    sd::Vp P{};
+    sd::VpK K{};
+    Carve c{nullptr};
+    vpk_carve(P, K, c, batch, gamma, vocab_local);
+    return c.used;
+}
+
+int32_t sd_vp_keep_rounds(int32_t kind) {
+    return kind == SD_PROC_TOPK ? 1 : kind == SD_PROC_NUCLEUS ? 2 : kind == SD_PROC_TOPK_NUCLEUS ? 3 : 0;
+}
+
+int32_t sd_vp_keep_hist(const sd_vp_keep_args* k, void* stream) {
+    sd::Vp P{};
+    sd::VpK K{};
+    if (int32_t st = vpk_plan(k, kPhaseStats, P, K)) return st;
+    clear_stale_error();
+    const int rows = P.B * (2 * P.gamma + 1);
+    const int64_t n16 = (int64_t)rows * sd::kVpkStride / 4;
+    if (int32_t st = launch(sd::k_vpk_clear, dim3((uint32_t)((n16 + sd::kThreads - 1) / sd::kThreads)), kVpBlock, 0, stream,
+                            reinterpret_cast<uint4*>(K.hist), n16))
+        return st;
+    return dispatch_dtype16(k->vp.dtype, [&](auto dt_) -> int32_t {
+        constexpr int DT = decltype(dt_)::value;
+        if (int32_t st = launch(sd::k_vpk_hist<DT>, dim3((uint32_t)((int64_t)rows * P.n_chunks)), kVpBlock, 0, stream, P, K)) return st;
+        return launch(sd::k_vpk_rowhist<DT>, dim3(rows), kVpBlock, 0, stream, P, K);
+    });
+}
+
+int32_t sd_vp_keep_refine(const sd_vp_keep_args* k, void* stream) {
+    sd::Vp P{};
+    sd::VpK K{};
+    if (int32_t st = vpk_plan(k, kPhaseRefine, P, K)) return st;
+    clear_stale_error();
+    return dispatch_dtype16(k->vp.dtype, [&](auto dt_) -> int32_t {
+        constexpr int DT = decltype(dt_)::value;
+        return launch(sd::k_vpk_refine<DT>, dim3(P.B * (2 * P.gamma + 1)), kVpBlock, 0, stream, P, K);
+    });
+}
+
+int32_t sd_vp_keep_decide(const sd_vp_keep_args* k, void* stream) {
+    sd::Vp P{};
+    sd::VpK K{};
+    if (int32_t st = vpk_plan(k, kPhaseDecide, P, K)) return st;
+    clear_stale_error();
+    return dispatch_dtype16(k->vp.dtype, [&](auto dt_) -> int32_t {
+        constexpr int DT = decltype(dt_)::value;
+        if (int32_t st = launch(sd::k_vpk_solve<DT>, dim3(P.B * (2 * P.gamma + 1)), kVpBlock, 0, stream, P, K)) return st;
+        if (int32_t st = launch(sd::k_vpk_decide<DT>, dim3(P.B), kVpBlock, 0, stream, P, K)) return st;
+        if (int32_t st = launch(sd::k_vp_mass<DT, true>, dim3((uint32_t)((int64_t)P.B * P.n_chunks)), kVpBlock, 0, stream, P)) return st;
+        return launch(sd::k_vp_pick<DT, true>, dim3(P.B), kVpBlock, 0, stream, P);
+    });
+}
+
+int32_t sd_vp_keep_finish(const sd_vp_keep_args* k, void* stream) {
+    sd::Vp P{};
+    sd::VpK K{};
+    if (int32_t st = vpk_plan(k, kPhaseFinish, P, K)) return st;
     clear_stale_error();
     if (int32_t st = launch(sd::k_vp_finish, dim3((P.B + sd::kThreads - 1) / sd::kThreads), kVpBlock, 0, stream, P)) return st;
     g_verify_path = SD_PATH_VERIFY_VP;

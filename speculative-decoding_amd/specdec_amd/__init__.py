@@ -26,11 +26,12 @@ from .ops import topk_children, verify_tree_distinct  # noqa: F401
 from .ops import BlockVerifyOut, verify_block  # noqa: F401
 from .ops import tree_grow, tree_pool, tree_select, verify_tree_dynamic  # noqa: F401
 from .tree import DynamicTreeSpec, TokenTree, dynamic_attention_inputs  # noqa: F401
-from .vocab_parallel import GroupExchange, LocalShards, VocabShard, verify_vocab_parallel  # noqa: F401
+from .vocab_parallel import (GroupExchange, LocalShards, VocabShard, verify_vocab_parallel,  # noqa: F401
+                             verify_vocab_parallel_keep)
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.specdec.sample / .verify)
 from .sampling.dynamic_tree_decoding import dynamic_tree_speculative_generate  # noqa: F401,E402
 
 __all__ = ["RowError", "get_poll_policy", "set_poll_policy", "PhiloxNoise", "StreamNoise", "default_noise", "set_noise_mode", "ProcSpec", "proc_spec",
            "probs_rows", "sample_rows", "verify", "verify_multi", "verify_block", "verify_tree", "verify_tree_distinct", "topk_children", "kv_compact", "TokenTree", "GroupExchange", "LocalShards", "VocabShard",
-           "verify_vocab_parallel", "tree_grow", "tree_pool", "tree_select", "verify_tree_dynamic", "DynamicTreeSpec",
+           "verify_vocab_parallel", "verify_vocab_parallel_keep", "tree_grow", "tree_pool", "tree_select", "verify_tree_dynamic", "DynamicTreeSpec",
            "dynamic_attention_inputs", "dynamic_tree_speculative_generate"]

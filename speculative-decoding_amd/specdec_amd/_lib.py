@@ -76,6 +76,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_verify_multi_workspace_size", "sd_verify_multi",
            "sd_vp_stats_bytes", "sd_vp_cand_bytes", "sd_vp_workspace_size", "sd_vp_stats", "sd_vp_decide",
            "sd_vp_finish",
+           "sd_vp_keep_hist_bytes", "sd_vp_keep_bins_bytes", "sd_vp_keep_workspace_size", "sd_vp_keep_rounds",
+           "sd_vp_keep_hist", "sd_vp_keep_refine", "sd_vp_keep_decide", "sd_vp_keep_finish",
            "sd_verify_tree_workspace_size", "sd_verify_tree",
            "sd_verify_tree_distinct_workspace_size", "sd_verify_tree_distinct",
            "sd_kv_compact",
@@ -87,6 +89,7 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
 SD_VP_MAGIC = 0x53445650
 SD_VP_STAT_OWNS = 0x1
+SD_VP_KEEP_MAX_ROUNDS, SD_VP_KEEP_NONFINITE, SD_VP_KEEP_COUNTS, SD_VP_KEEP_MASSES = 3, 0x2, 1, 2
 
 # multi-draft verify
 SD_MULTI_MAX_DRAFTS, SD_MULTI_MAX_NODES, SD_MULTI_MAX_ROWS = 8, 64, 16384
@@ -387,6 +390,20 @@ class sd_vp_args(C.Structure):
     ]
 
 
+class sd_vp_keep_stat(C.Structure):
+    _fields_ = [("m", C.c_float), ("x_tok", C.c_float), ("tok_rank", C.c_int32), ("flags", C.c_int32),
+                ("count", C.c_uint32 * 256), ("mass1", C.c_double * 256), ("massT", C.c_double * 256)]
+
+
+class sd_vp_keep_bin(C.Structure):
+    _fields_ = [("bin", C.c_int32), ("kind", C.c_int32), ("pad", C.c_int32 * 2), ("val", C.c_double * 256)]
+
+
+class sd_vp_keep_args(C.Structure):
+    _fields_ = [("vp", sd_vp_args), ("hist_local", C.c_void_p), ("hist_all", C.c_void_p), ("bins_local", C.c_void_p),
+                ("bins_all", C.c_void_p * SD_VP_KEEP_MAX_ROUNDS), ("round", C.c_int32), ("reserved", C.c_int32)]
+
+
 def _share_torch_hip_runtime():
     """Load PyTorch-ROCm's bundled HIP runtime first, so libspecdec.so (NEEDED libamdhip64.so.7,
     which that copy's SONAME satisfies) binds to the SAME runtime torch uses instead of loading
@@ -465,6 +482,16 @@ def _load():
     lib.sd_vp_cand_bytes.argtypes = [C.c_int32]
     lib.sd_vp_workspace_size.restype = C.c_size_t
     lib.sd_vp_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    for name in ("sd_vp_keep_hist_bytes", "sd_vp_keep_bins_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+        getattr(lib, name).argtypes = [C.c_int32, C.c_int32]
+    lib.sd_vp_keep_workspace_size.restype = C.c_size_t
+    lib.sd_vp_keep_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.sd_vp_keep_rounds.restype = C.c_int32
+    lib.sd_vp_keep_rounds.argtypes = [C.c_int32]
+    for name in ("sd_vp_keep_hist", "sd_vp_keep_refine", "sd_vp_keep_decide", "sd_vp_keep_finish"):
+        getattr(lib, name).restype = C.c_int32
+        getattr(lib, name).argtypes = [C.POINTER(sd_vp_keep_args), C.c_void_p]
     for name in ("sd_vp_stats", "sd_vp_decide", "sd_vp_finish"):
         getattr(lib, name).restype = C.c_int32
         getattr(lib, name).argtypes = [C.POINTER(sd_vp_args), C.c_void_p]

@@ -19,7 +19,8 @@ from .. import _lib
 from ..noise import PhiloxNoise
 from ..ops import sample_rows
 from ..utils.logits_processor import GreedyProcessor, LogitsProcessor
-from ..vocab_parallel import LocalShards, VocabShard, _vp_spec, verify_vocab_parallel
+from ..vocab_parallel import (LocalShards, VocabShard, _vp_keep_spec, _vp_spec, verify_vocab_parallel,
+                              verify_vocab_parallel_keep)
 
 
 @torch.no_grad()
@@ -37,6 +38,7 @@ def vocab_parallel_speculative_generate(
     first_target: bool = True,
     seed: Optional[int] = None,
     trace: Optional[list] = None,
+    sharded_keep: bool = False,
 ) -> Tuple[List[int], float]:
     """``speculative_generate`` on a vocabulary-sharded target; returns (tokens, accepted / speculated).
 
@@ -48,11 +50,15 @@ def vocab_parallel_speculative_generate(
     or multinomial at any temperature; a user ``_process`` or any other processor raises TypeError (the
     vocabulary-parallel verify has no top-k / nucleus search over slices).  trace: a list that
     receives per step ``(offset, draft tokens, n, x, status)`` (the first-target token is a step with
-    no drafts).  Every rank returns the same tokens.
+    no drafts).  Every rank returns the same tokens.  sharded_keep: the logits processor is top-k,
+    nucleus or top-k + nucleus instead (bf16 / fp16 logits) and every step runs
+    ``verify_vocab_parallel_keep``, the keep search over the slices; without it those processors raise as
+    said above.
 
     Single-GPU emulation: with ``exchange`` a ``LocalShards``, target_shard_fn is one function per
     shard (shard=None) and the S shards' steps run in lock step in this process."""
-    spec = _vp_spec(logits_processor)
+    spec = _vp_keep_spec(logits_processor) if sharded_keep else _vp_spec(logits_processor)
+    verify = verify_vocab_parallel_keep if sharded_keep else verify_vocab_parallel
     emu = isinstance(exchange, LocalShards)
     if emu:
         fns = list(target_shard_fn) if not callable(target_shard_fn) else None
@@ -96,10 +102,10 @@ def vocab_parallel_speculative_generate(
     def step(ts, ds, drafts):
         offset = noise.offset
         if emu:
-            out = verify_vocab_parallel(ts, ds, drafts, spec, noise, None, exchange, stop_tokens=stop_t, status_or=err)[0]
+            out = verify(ts, ds, drafts, spec, noise, None, exchange, stop_tokens=stop_t, status_or=err)[0]
         else:
-            out = verify_vocab_parallel(ts[0], ds[0] if ds else None, drafts, spec, noise, shard, exchange,
-                                        stop_tokens=stop_t, status_or=err)
+            out = verify(ts[0], ds[0] if ds else None, drafts, spec, noise, shard, exchange, stop_tokens=stop_t,
+                         status_or=err)
         n, x, status, stop_index, bits = (int(v) for v in torch.stack([
             out.n_accepted[0].long(), out.next_token[0], out.row_status[0].long(), out.stop_index[0].long(),
             err[0].long()]).tolist())

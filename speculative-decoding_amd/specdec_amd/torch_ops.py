@@ -66,6 +66,9 @@ GPU), and callable as ``torch.ops.specdec.*``.
             stop_index, row_status, owner_shard int32 [B])
         The three phases of the vocabulary-parallel verify on one rank's slices (sd_vp_stats / sd_vp_decide /
         sd_vp_finish; specdec_amd.vocab_parallel); the caller all-gathers the blocks between them.
+        torch.ops.specdec.vp_keep_hist / vp_keep_refine / vp_keep_decide / vp_keep_finish: the same under
+        top-k / nucleus processors (sd_vp_keep_*), with kind, temperature, top_k, top_p in place of kind,
+        temperature, and the gathered histogram block and refine rounds (a list) in place of stats_all.
 
     torch.ops.specdec.kv_compact(tensors Tensor[] ([B, H, L, D] each), path int32 [B, depth], count int32 [B], base,
                                  num_slots, node_slot int[]?, base_dev int64 [1]?) -> ()
@@ -325,6 +328,88 @@ def vp_finish(cand_all: Tensor, gamma: int, shard: int, num_shards: int, vocab_o
 
 @vp_finish.register_fake
 def _(cand_all, gamma, shard, num_shards, vocab_offset, vocab_local, vocab, kind, seed, offset, row_base):
+    B = (cand_all.shape[1] - 32) // 32
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(cand_all.new_empty(B, dtype=dt.get(f, torch.int32)) for f in vp.VP_FIELDS)
+
+
+def _vp_keep_step(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens, gathered, shard: int,
+                  num_shards: int, vocab_offset: int, vocab: int, kind: int, temperature: float, top_k: int, top_p: float,
+                  skip: bool, seed: int, offset: int, row_base: int) -> vp._KeepStep:
+    sh = vp.VocabShard(shard, num_shards, vocab_offset, target.shape[-1], vocab)
+    nz, _ = ops._noise_struct(PhiloxNoise(seed, offset), 0, target.device, row_base)
+    st = vp._step_of(target, draft if draft.shape[1] else None, draft_tokens,
+                     vp._vp_keep_spec(_spec(kind, temperature, top_k, top_p)), nz, sh, stop_tokens, skip, None, vp._KeepStep)
+    for blocks in gathered:
+        st.take(blocks)
+    return st
+
+
+def _keep_rows(target) -> int:
+    return target.shape[0] * (2 * target.shape[1] - 1)
+
+
+@torch.library.custom_op("specdec::vp_keep_hist", mutates_args=())
+def vp_keep_hist(target: Tensor, draft: Tensor, draft_tokens: Tensor, shard: int, num_shards: int, vocab_offset: int,
+                 vocab: int, kind: int, temperature: float, top_k: int, top_p: float) -> Tensor:
+    """Phase 1 of the vocabulary-parallel verify under top-k / nucleus on this rank's bf16 / fp16 slices: its
+    histogram block (the per-key histogram stays in the shard's workspace for the refine rounds)."""
+    return _vp_keep_step(target, draft, draft_tokens, None, [], shard, num_shards, vocab_offset, vocab, kind, temperature,
+                         top_k, top_p, False, 0, 0, 0).hist()
+
+
+@vp_keep_hist.register_fake
+def _(target, draft, draft_tokens, shard, num_shards, vocab_offset, vocab, kind, temperature, top_k, top_p):
+    return target.new_empty(32 + _keep_rows(target) * 5136, dtype=torch.uint8)
+
+
+@torch.library.custom_op("specdec::vp_keep_refine", mutates_args=())
+def vp_keep_refine(target: Tensor, draft: Tensor, draft_tokens: Tensor, hist_all: Tensor, bins_all: List[Tensor],
+                   shard: int, num_shards: int, vocab_offset: int, vocab: int, kind: int, temperature: float, top_k: int,
+                   top_p: float) -> Tensor:
+    """Refine round len(bins_all) (1, 2, 3 rounds for top-k, nucleus, top-k + nucleus): this rank's block."""
+    return _vp_keep_step(target, draft, draft_tokens, None, [hist_all] + list(bins_all), shard, num_shards, vocab_offset,
+                         vocab, kind, temperature, top_k, top_p, False, 0, 0, 0).refine()
+
+
+@vp_keep_refine.register_fake
+def _(target, draft, draft_tokens, hist_all, bins_all, shard, num_shards, vocab_offset, vocab, kind, temperature, top_k,
+      top_p):
+    return target.new_empty(32 + _keep_rows(target) * 2064, dtype=torch.uint8)
+
+
+@torch.library.custom_op("specdec::vp_keep_decide", mutates_args=())
+def vp_keep_decide(target: Tensor, draft: Tensor, draft_tokens: Tensor, stop_tokens: Tensor, hist_all: Tensor,
+                   bins_all: List[Tensor], shard: int, num_shards: int, vocab_offset: int, vocab: int, kind: int,
+                   temperature: float, top_k: int, top_p: float, skip_sample_adjustment: bool, seed: int, offset: int,
+                   row_base: int) -> Tensor:
+    """The decision (the same on every rank) and this rank's candidate block."""
+    return _vp_keep_step(target, draft, draft_tokens, stop_tokens, [hist_all] + list(bins_all), shard, num_shards,
+                         vocab_offset, vocab, kind, temperature, top_k, top_p, skip_sample_adjustment, seed, offset,
+                         row_base).decide()
+
+
+@vp_keep_decide.register_fake
+def _(target, draft, draft_tokens, stop_tokens, hist_all, bins_all, shard, num_shards, vocab_offset, vocab, kind,
+      temperature, top_k, top_p, skip_sample_adjustment, seed, offset, row_base):
+    return target.new_empty(32 + target.shape[0] * 32, dtype=torch.uint8)
+
+
+@torch.library.custom_op("specdec::vp_keep_finish", mutates_args=())
+def vp_keep_finish(cand_all: Tensor, gamma: int, shard: int, num_shards: int, vocab_offset: int, vocab_local: int,
+                   vocab: int, kind: int, top_k: int, top_p: float, seed: int, offset: int,
+                   row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The shard pick and the step's outputs, in vocab_parallel.VP_FIELDS' order."""
+    B = (cand_all.shape[1] - 32) // 32
+    sh = vp.VocabShard(shard, num_shards, vocab_offset, vocab_local, vocab)
+    nz, _ = ops._noise_struct(PhiloxNoise(seed, offset), 0, cand_all.device, row_base)
+    st = vp._KeepStep(B, gamma, cand_all.device, torch.bfloat16, sh, vp._vp_keep_spec(_spec(kind, 1.0, top_k, top_p)), nz)
+    out = st.finish(cand_all)
+    return tuple(getattr(out, f).clone() for f in vp.VP_FIELDS)
+
+
+@vp_keep_finish.register_fake
+def _(cand_all, gamma, shard, num_shards, vocab_offset, vocab_local, vocab, kind, top_k, top_p, seed, offset, row_base):
     B = (cand_all.shape[1] - 32) // 32
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
     return tuple(cand_all.new_empty(B, dtype=dt.get(f, torch.int32)) for f in vp.VP_FIELDS)

@@ -114,7 +114,8 @@ class GroupExchange:
 class LocalShards:
     """An EMULATION of S ranks for tests and timing on one GPU: the S shards of a step run in one
     process, on one device and stream, in lock step — phase 1 of every shard, the concatenation of
-    their blocks in shard order, phase 3 of every shard, the concatenation, phase 5 of every shard.
+    their blocks in shard order, phase 3 of every shard, the concatenation, phase 5 of every shard
+    (the keep step, ``verify_vocab_parallel_keep``, likewise with its refine rounds in between).
     Nothing is exchanged between devices.  ``verify_vocab_parallel(..., shard=None, exchange=ls)``
     takes per-shard inputs (or whole rows, which are sliced as views) and returns one output per
     shard; a serving rank uses ``GroupExchange``."""
@@ -282,6 +283,12 @@ class _Step:
         return out
 
     def finish(self, cand_all) -> VocabVerifyOut:
+        out = self._outputs(cand_all)
+        _lib.check(lib.sd_vp_finish(C.byref(self.a), self._stream()), "sd_vp_finish")
+        return out
+
+    def _outputs(self, cand_all) -> VocabVerifyOut:
+        """The output tensors of the last phase, their addresses and cand_all's set in the arguments."""
         cand_all = _check_gathered(cand_all, self.S, self.ncand, self.dev, "candidate")
         B = self.B
         # one allocation, every byte written by the kernel: next_token (int64) first, then the seven
@@ -294,12 +301,97 @@ class _Step:
         self.a.cand_all = cand_all.data_ptr()
         for f in VP_FIELDS:
             setattr(self.a, f, getattr(out, f).data_ptr())
-        _lib.check(lib.sd_vp_finish(C.byref(self.a), self._stream()), "sd_vp_finish")
+        return out
+
+
+_KEEP_WS = {}
+
+
+def release_keep_workspaces() -> None:
+    """Drop the cached workspaces of the keep step (about 257 KiB per (sequence, row) and shard: 38 MB at
+    B = 16, γ = 4; ``LocalShards`` holds one per emulated shard).  They are kept for the life of the process
+    otherwise, one per (device, stream, shard), sized by the largest step seen.  Not while a captured graph
+    that used them may still replay."""
+    _KEEP_WS.clear()
+
+
+def _keep_workspace(nbytes: int, dev, shard: int) -> torch.Tensor:
+    """The workspace of one shard's keep step.  The key histograms stay in it from sd_vp_keep_hist to
+    the last refine round, so shards emulated in one process must not share one: one per (device,
+    stream, shard), zero-filled once, grown on demand (not inside a graph capture)."""
+    if torch.cuda.is_current_stream_capturing():   # a capture runs on a stream of its own: the shard's largest
+        cands = [w for (d, _, sh), w in _KEEP_WS.items() if d == dev and sh == shard]
+        ws = max(cands, key=lambda w: w.numel()) if cands else None
+        if ws is None or ws.numel() < nbytes:
+            raise RuntimeError("specdec: a keep step captured into a hipGraph needs its workspace sized by an eager "
+                               "call of the same shape first (run it once before capturing)")
+        return ws
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, shard)
+    ws = _KEEP_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _KEEP_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+class _KeepStep(_Step):
+    """One shard's step under a top-k / nucleus processor: sd_vp_keep_args around the same sd_vp_args."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        k = _lib.sd_vp_keep_args()
+        k.vp = self.a
+        self.k, self.a = k, k.vp                      # self.a: the embedded copy (shares k's memory)
+        B, gamma = self.B, self.gamma
+        self.nhist, self.nbins = lib.sd_vp_keep_hist_bytes(B, gamma), lib.sd_vp_keep_bins_bytes(B, gamma)
+        self.rounds = lib.sd_vp_keep_rounds(self.a.proc.kind)
+        ws = _keep_workspace(lib.sd_vp_keep_workspace_size(B, gamma, self.a.vocab_local), self.dev, self.a.shard)
+        self.a.workspace, self.a.workspace_bytes = ws.data_ptr(), ws.numel()
+        self.keep = self.keep + (ws,)
+        self.gathered = []
+
+    def hist(self) -> torch.Tensor:
+        out = torch.empty(self.nhist, dtype=torch.uint8, device=self.dev)
+        self.k.hist_local = out.data_ptr()
+        _lib.check(lib.sd_vp_keep_hist(C.byref(self.k), self._stream()), "sd_vp_keep_hist")
+        return out
+
+    def take(self, gathered) -> "_KeepStep":
+        """The blocks gathered last: exchange A's first, then one refine round's after another."""
+        first = not self.gathered
+        gathered = _check_gathered(gathered, self.S, self.nhist if first else self.nbins, self.dev,
+                                   "histogram" if first else "refine")
+        if first:
+            self.k.hist_all = gathered.data_ptr()
+        else:
+            if len(self.gathered) > self.rounds:
+                raise ValueError(f"verify_vocab_parallel_keep: more than {self.rounds} refine rounds gathered")
+            self.k.bins_all[len(self.gathered) - 1] = gathered.data_ptr()
+        self.gathered.append(gathered)
+        return self
+
+    def refine(self) -> torch.Tensor:
+        """The round after the ones taken so far."""
+        out = torch.empty(self.nbins, dtype=torch.uint8, device=self.dev)
+        self.k.bins_local, self.k.round = out.data_ptr(), len(self.gathered) - 1
+        _lib.check(lib.sd_vp_keep_refine(C.byref(self.k), self._stream()), "sd_vp_keep_refine")
+        return out
+
+    def decide(self) -> torch.Tensor:
+        if len(self.gathered) != self.rounds + 1:
+            raise ValueError(f"verify_vocab_parallel_keep: the decision needs {self.rounds} gathered refine rounds")
+        out = torch.empty(self.ncand, dtype=torch.uint8, device=self.dev)
+        self.a.cand_local = out.data_ptr()
+        _lib.check(lib.sd_vp_keep_decide(C.byref(self.k), self._stream()), "sd_vp_keep_decide")
+        return out
+
+    def finish(self, cand_all) -> VocabVerifyOut:
+        out = self._outputs(cand_all)
+        _lib.check(lib.sd_vp_keep_finish(C.byref(self.k), self._stream()), "sd_vp_keep_finish")
         return out
 
 
 def _step_of(target_slices, draft_slices, draft_tokens, spec, nz, shard: VocabShard, stop_tokens=None,
-             skip: bool = False, status_or=None) -> _Step:
+             skip: bool = False, status_or=None, cls=None) -> _Step:
     """Validate one shard's inputs (host only, before any launch) and build its step."""
     Vs = shard.vocab_local
     target_slices = _rows_of(target_slices)
@@ -317,8 +409,8 @@ def _step_of(target_slices, draft_slices, draft_tokens, spec, nz, shard: VocabSh
                 or draft_tokens.shape[0] != B or draft_tokens.shape[1] < gamma or draft_tokens.stride(1) != 1 \
                 or draft_tokens.device != dev:
             raise ValueError(f"draft_tokens must be int64 [B, >={gamma}] on {dev}")
-    return _Step(B, gamma, dev, dt, shard, spec, nz, trows, t_stride, drows, d_stride, draft_tokens, stop_tokens, skip,
-                 status_or)
+    return (cls or _Step)(B, gamma, dev, dt, shard, spec, nz, trows, t_stride, drows, d_stride, draft_tokens,
+                          stop_tokens, skip, status_or)
 
 
 def _vp_step(target_slices, draft_slices, draft_tokens, spec, nz, shard: VocabShard, stop_tokens, skip: bool,
@@ -329,6 +421,29 @@ def _vp_step(target_slices, draft_slices, draft_tokens, spec, nz, shard: VocabSh
     stats_all = yield st.stats()
     cand_all = yield st.decide(stats_all)
     return st.finish(cand_all)
+
+
+def _vp_keep_step(target_slices, draft_slices, draft_tokens, spec, nz, shard: VocabShard, stop_tokens, skip: bool,
+                  status_or):
+    """Generator of the keep step: yields the histogram block, one block per refine round and the
+    candidate block, taking the gathered blocks after each; returns VocabVerifyOut."""
+    st = _step_of(target_slices, draft_slices, draft_tokens, spec, nz, shard, stop_tokens, skip, status_or, _KeepStep)
+    gathered = yield st.hist()
+    for _ in range(st.rounds):
+        gathered = yield st.take(gathered).refine()
+    cand_all = yield st.take(gathered).decide()
+    return st.finish(cand_all)
+
+
+def _vp_keep_spec(proc):
+    if _user_process(proc) is not None:
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: the vocabulary-parallel verify processes "
+                        "slices of the rows and cannot run a user _process")
+    spec = proc_spec(proc)
+    if not spec.keeps:
+        raise TypeError(f"unsupported logits processor {spec.kind}: verify_vocab_parallel_keep takes top-k, nucleus and "
+                        "top-k + nucleus processors (greedy / multinomial: verify_vocab_parallel)")
+    return spec
 
 
 def _vp_spec(proc):
@@ -361,9 +476,29 @@ def verify_vocab_parallel(target_slices, draft_slices, draft_tokens: Optional[to
     With ``exchange`` a ``LocalShards`` (single-GPU emulation; shard=None) the slices are one entry
     per shard, or whole rows [..., V] that are sliced as views, and the result is one VocabVerifyOut
     per shard."""
-    spec = _vp_spec(proc)
+    return _drive(_vp_step, _vp_spec(proc), target_slices, draft_slices, draft_tokens, noise, shard, exchange,
+                  stop_tokens, row_base, skip_sample_adjustment, status_or)
+
+
+def verify_vocab_parallel_keep(target_slices, draft_slices, draft_tokens: Optional[torch.Tensor], proc, noise,
+                               shard: Optional[VocabShard], exchange, stop_tokens: Optional[torch.Tensor] = None,
+                               row_base: int = 0, skip_sample_adjustment: bool = False,
+                               status_or: Optional[torch.Tensor] = None):
+    """``verify_vocab_parallel`` for top-k, nucleus and top-k + nucleus processors on bf16 / fp16 slices
+    (sd_vp_keep_*): the kept set of every row is the one ``ops.probs`` / ``ops.verify`` keep on the
+    gathered whole row, found by a histogram search over the slices.  Same arguments and result;
+    ``exchange`` is called once for the histogram block (about 5 KB per row), once per refine round
+    (2 KB per row; 1, 2, 3 rounds for top-k, nucleus, top-k + nucleus) and once for the candidates."""
+    return _drive(_vp_keep_step, _vp_keep_spec(proc), target_slices, draft_slices, draft_tokens, noise, shard,
+                  exchange, stop_tokens, row_base, skip_sample_adjustment, status_or)
+
+
+def _drive(_vp_step, spec, target_slices, draft_slices, draft_tokens, noise, shard, exchange, stop_tokens, row_base,
+           skip_sample_adjustment, status_or):
+    """Run one shard's step generator against ``exchange`` (or S of them in lock step: LocalShards)."""
     if not isinstance(noise, PhiloxNoise):
-        raise TypeError("verify_vocab_parallel needs PhiloxNoise (SD_NOISE_STREAM's draw order needs whole rows)")
+        raise TypeError("the vocabulary-parallel verify needs PhiloxNoise (SD_NOISE_STREAM's draw order needs whole "
+                        "rows)")
     if isinstance(exchange, LocalShards):
         ts, ds = exchange.slices(target_slices), exchange.slices(draft_slices)
         first = ts[0] if torch.is_tensor(ts[0]) else ts[0][0]
