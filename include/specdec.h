@@ -1298,6 +1298,77 @@ typedef struct {
 size_t sd_verify_block_workspace_size(int32_t batch, int32_t gamma, int32_t vocab);
 int32_t sd_verify_block(const sd_block_args* args, void* stream);
 
+/* ---- Tree attention for the cached tree forwards (csrc/tree_attention.hip; additive, ABI 12) ----------
+ * The attention of a forward that appends R new tokens (a few committed catch-up tokens, then tree
+ * nodes) to a KV cache, with NO mask tensor: row r of sequence b sees key j < kv_len when
+ *
+ *     j < kv_limit[b][r]                                  (the committed prefix), or
+ *     0 <= j - win_base < 64  and  bit (j - win_base) of win_bits[b][r] is set     (the tree's window)
+ *
+ * (a union).  A committed catch-up row r of a forward that starts at position `start` has
+ * kv_limit = start + r + 1 and no bits; node i of a tree behind `cur` committed tokens has kv_limit = cur,
+ * win_base = cur and one bit per column of its path (sd_tree_select's `anc` word as it stands).  For
+ * query head h, whose K/V head is h / (heads_q / heads_kv):
+ *
+ *     out[b, r, h, :] = sum_j softmax_j(scale * q[b, h, r, :] . k[b, kvh, j, :] over the visible j) * v[b, kvh, j, :]
+ *
+ * in fp32 from 16-bit inputs (bf16 / fp16 MFMA, fp32 accumulators; scale multiplies the fp32 score; the
+ * probabilities are rounded to the 16-bit type for the second product).  A row that sees no key gets
+ * zeros.  Visibility selects, it never multiplies: a position that NO row of its sequence sees (masked
+ * for all of them, or at or beyond kv_len) is not loaded at all, so a NaN or inf there cannot reach
+ * `out`; a key masked for one row is excluded from that row's softmax by selection.  A position that
+ * some row of the sequence sees must hold finite V for the sequence's other rows to be finite (the
+ * second product runs on the matrix units over whole key tiles).
+ *
+ * Two launches, k_tattn_partial over (split, K/V head, sequence) and k_tattn_combine; with one split the
+ * first writes `out` and the second is skipped.  The split count is a function of the shapes alone
+ * (`splits` = 0) or pinned (1..SD_TREE_ATTN_MAX_SPLITS; clamped to the number of 64-key tiles).  Launch
+ * boundaries are the only synchronisation: no atomics, no polling, no workgroup waits on another, so the
+ * call is capturable into a hipGraph and safe on a shared GPU.  Limits: dtype bf16 / fp16 (SD_F32:
+ * SD_ERR_UNSUPPORTED), head_dim 64 or 128, heads_q a multiple of heads_kv (else SD_ERR_INVALID) with at
+ * most SD_TREE_ATTN_MAX_GROUP query heads per K/V head, rows 1..SD_TREE_ATTN_MAX_ROWS, kv_len 1..2^20
+ * and <= kv_alloc; beyond them SD_ERR_UNSUPPORTED.  Every pointer and every stride must keep 16-byte
+ * alignment (strides in elements: multiples of 8), the head dimension has unit stride.                */
+#define SD_TREE_ATTN_MAX_ROWS 128
+#define SD_TREE_ATTN_MAX_GROUP 8
+#define SD_TREE_ATTN_MAX_SPLITS 64
+#define SD_TREE_ATTN_MAX_KV (1 << 20)
+
+typedef struct {
+    int32_t batch;               /* B (<= 65535)                                                    */
+    int32_t heads_q;             /* Hq                                                              */
+    int32_t heads_kv;            /* Hkv (<= 65535)                                                  */
+    int32_t rows;                /* R: new tokens of the forward, 1..SD_TREE_ATTN_MAX_ROWS           */
+    int32_t head_dim;            /* D: 64 or 128                                                    */
+    int32_t dtype;               /* SD_BF16 or SD_F16, of q, k, v and out                           */
+    int32_t kv_len;              /* valid positions of k / v, 1..SD_TREE_ATTN_MAX_KV                 */
+    int32_t kv_alloc;            /* positions k / v hold per (b, head); >= kv_len                   */
+    int32_t splits;              /* 0: by the shapes; else 1..SD_TREE_ATTN_MAX_SPLITS (tests)        */
+    float scale;
+    const void* q;               /* [B, Hq, R, D] at q + b*q_stride_b + h*q_stride_h + r*q_stride_r  */
+    int64_t q_stride_b, q_stride_h, q_stride_r;
+    const void* k;               /* [B, Hkv, kv_alloc, D], strides of batch, head and position       */
+    const void* v;
+    int64_t k_stride_b, k_stride_h, k_stride_pos;
+    int64_t v_stride_b, v_stride_h, v_stride_pos;
+    void* out;                   /* [B, R, Hq, D] at out + b*out_stride_b + r*out_stride_r + h*out_stride_h */
+    int64_t out_stride_b, out_stride_r, out_stride_h;
+    const int32_t* kv_limit;     /* device int32 [B, R], contiguous                                 */
+    const uint64_t* win_bits;    /* device uint64 [B, R], contiguous                                */
+    int64_t win_base;
+    void* workspace;             /* sd_tree_attention_workspace_size bytes; may be null when the call
+                                    runs one split.  The common counter block at its front is left
+                                    untouched; the splits' fp32 partials follow it                   */
+    size_t workspace_bytes;
+} sd_tree_attention_args;
+
+/* splits the call will run (after the clamp to the tile count), 0 for shapes it does not take        */
+int32_t sd_tree_attention_splits(int32_t batch, int32_t heads_kv, int32_t kv_len, int32_t splits);
+/* 0 for a shape sd_tree_attention does not take                                                      */
+size_t sd_tree_attention_workspace_size(int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t rows,
+                                        int32_t head_dim, int32_t kv_len, int32_t splits);
+int32_t sd_tree_attention(const sd_tree_attention_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

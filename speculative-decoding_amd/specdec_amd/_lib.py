@@ -83,7 +83,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_kv_compact",
            "sd_tree_grow_workspace_size", "sd_tree_grow", "sd_tree_select_workspace_size", "sd_tree_select",
            "sd_verify_tree_dynamic_workspace_size", "sd_verify_tree_dynamic",
-           "sd_verify_block_workspace_size", "sd_verify_block")
+           "sd_verify_block_workspace_size", "sd_verify_block",
+           "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -102,6 +103,9 @@ SD_TREE_POOL_MAX, SD_TREE_GROW_MAX_WIDTH, SD_TREE_GROW_MAX_VOCAB = 2048, 8, 5242
 
 # KV-cache compaction onto a tree path
 SD_KV_MAX_TENSORS = 256
+
+# tree attention (sd_tree_attention)
+SD_TREE_ATTN_MAX_ROWS, SD_TREE_ATTN_MAX_GROUP, SD_TREE_ATTN_MAX_SPLITS, SD_TREE_ATTN_MAX_KV = 128, 8, 64, 1 << 20
 
 # beam step (ABI 12)
 SD_BEAM_MAX_BEAMS, SD_BEAM_MAX_TOPK, SD_BEAM_MAX_CANDIDATES, SD_BEAM_MAX_VOCAB = 64, 64, 1024, 524288
@@ -359,6 +363,21 @@ class sd_kv_compact_args(C.Structure):
     ]
 
 
+class sd_tree_attention_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("heads_q", C.c_int32), ("heads_kv", C.c_int32), ("rows", C.c_int32),
+        ("head_dim", C.c_int32), ("dtype", C.c_int32), ("kv_len", C.c_int32), ("kv_alloc", C.c_int32),
+        ("splits", C.c_int32), ("scale", C.c_float),
+        ("q", C.c_void_p), ("q_stride_b", C.c_int64), ("q_stride_h", C.c_int64), ("q_stride_r", C.c_int64),
+        ("k", C.c_void_p), ("v", C.c_void_p),
+        ("k_stride_b", C.c_int64), ("k_stride_h", C.c_int64), ("k_stride_pos", C.c_int64),
+        ("v_stride_b", C.c_int64), ("v_stride_h", C.c_int64), ("v_stride_pos", C.c_int64),
+        ("out", C.c_void_p), ("out_stride_b", C.c_int64), ("out_stride_r", C.c_int64), ("out_stride_h", C.c_int64),
+        ("kv_limit", C.c_void_p), ("win_bits", C.c_void_p), ("win_base", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class sd_vp_header(C.Structure):
     _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
                 ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
@@ -464,6 +483,12 @@ def _load():
     lib.sd_verify_tree_distinct.argtypes = [C.POINTER(sd_tree_distinct_args), C.c_void_p]
     lib.sd_kv_compact.restype = C.c_int32
     lib.sd_kv_compact.argtypes = [C.POINTER(sd_kv_compact_args), C.c_void_p]
+    lib.sd_tree_attention_splits.restype = C.c_int32
+    lib.sd_tree_attention_splits.argtypes = [C.c_int32] * 4
+    lib.sd_tree_attention_workspace_size.restype = C.c_size_t
+    lib.sd_tree_attention_workspace_size.argtypes = [C.c_int32] * 7
+    lib.sd_tree_attention.restype = C.c_int32
+    lib.sd_tree_attention.argtypes = [C.POINTER(sd_tree_attention_args), C.c_void_p]
     lib.sd_tree_grow_workspace_size.restype = C.c_size_t
     lib.sd_tree_grow_workspace_size.argtypes = [C.c_int32] * 5
     lib.sd_tree_grow.restype = C.c_int32

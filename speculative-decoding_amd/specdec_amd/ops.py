@@ -1180,6 +1180,79 @@ def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, n
         _lib.check(lib.sd_kv_compact(C.byref(a), stream), "sd_kv_compact")
 
 
+# --------------------------------------------------------------------------- tree attention
+def tree_attention_splits(batch: int, heads_kv: int, kv_len: int, splits: int = 0) -> int:
+    """The split count ``tree_attention`` runs for a shape (sd_tree_attention_splits): a function of the
+    shapes alone, or ``splits`` clamped to the number of 64-key tiles; 0 for a shape it does not take."""
+    return int(lib.sd_tree_attention_splits(int(batch), int(heads_kv), int(kv_len), int(splits)))
+
+
+def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: torch.Tensor, win_bits: torch.Tensor,
+                   win_base: int, scale: Optional[float] = None, kv_len: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None, splits: int = 0, *,
+                   workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The attention of a cached tree forward without a mask tensor (sd_tree_attention, MFMA kernels).
+
+    q: [B, Hq, R, D]; k, v: [B, Hkv, L, D] (a cache layer's tensors; the first ``kv_len`` positions are
+    valid, default L); bf16 or fp16, unit stride along D, any other strides that keep 16-byte alignment.
+    kv_limit: int32 [B, R] and win_bits: int64 (or uint64) [B, R] on the device: row r sees key j < kv_len
+    when ``j < kv_limit[b, r]`` or bit ``j - win_base`` of ``win_bits[b, r]`` is set.  Returns
+    ``out`` [B, R, Hq, D] (the layout transformers' attention interface returns), softmax in fp32 with
+    ``scale`` (default D ** -0.5) applied to the fp32 score; a row that sees nothing gets zeros.
+    splits: 0 lets the shapes decide, another value pins the split-KV count (tests).  workspace: a
+    uint8 device tensor of the caller's (default: the stream's shared workspace).  Shapes and dtypes the
+    kernels do not take raise SpecdecError with the library's status."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("tree_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D]")
+    B, Hq, R, D = q.shape
+    if k.shape != v.shape or k.shape[0] != B or k.shape[3] != D:
+        raise ValueError(f"tree_attention: k / v shapes {tuple(k.shape)}, {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    Hkv, L = k.shape[1], k.shape[2]
+    dev = q.device
+    if not q.is_cuda or k.device != dev or v.device != dev:
+        raise ValueError("tree_attention: q, k and v must be tensors of one device")
+    if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("tree_attention: q, k and v must share one floating dtype")
+    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
+        raise ValueError("tree_attention: the head dimension must have unit stride")
+    kv_len = L if kv_len is None else int(kv_len)
+    if not 1 <= kv_len <= L:
+        raise ValueError(f"tree_attention: kv_len {kv_len} outside 1..{L}")
+    if kv_limit.dtype != torch.int32 or kv_limit.shape != (B, R) or not kv_limit.is_contiguous() or kv_limit.device != dev:
+        raise ValueError(f"tree_attention: kv_limit must be a contiguous int32 [{B}, {R}] on {dev}")
+    if win_bits.dtype not in (torch.int64, torch.uint64) or win_bits.shape != (B, R) or not win_bits.is_contiguous() \
+            or win_bits.device != dev:
+        raise ValueError(f"tree_attention: win_bits must be a contiguous int64 / uint64 [{B}, {R}] on {dev}")
+    if out is None:
+        out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
+    elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
+        raise ValueError(f"tree_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
+    a = _lib.sd_tree_attention_args()
+    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
+    a.kv_len, a.kv_alloc, a.splits = kv_len, L, int(splits)
+    a.scale = float(D) ** -0.5 if scale is None else float(scale)
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    # a dimension of size 1 may carry any stride: it is never stepped along
+    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.q_stride_r = a.q_stride_r or D
+    a.k_stride_b, a.k_stride_h, a.k_stride_pos = (k.stride(i) if k.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.k_stride_pos = a.k_stride_pos or D
+    a.v_stride_b, a.v_stride_h, a.v_stride_pos = (v.stride(i) if v.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.v_stride_pos = a.v_stride_pos or D
+    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.out_stride_h = a.out_stride_h or D
+    a.kv_limit, a.win_bits, a.win_base = kv_limit.data_ptr(), win_bits.data_ptr(), int(win_base)
+    need = lib.sd_tree_attention_workspace_size(B, Hq, Hkv, R, D, kv_len, int(splits))
+    if workspace is None and need and tree_attention_splits(B, Hkv, kv_len, splits) > 1:
+        workspace = _workspace(need, dev)
+    if workspace is not None:
+        if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise ValueError("tree_attention: workspace must be a contiguous uint8 tensor on the call's device")
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    _lib.check(lib.sd_tree_attention(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention")
+    return out
+
+
 # --------------------------------------------------------------------------- n-gram verify (A11)
 @dataclass
 class NgramOut:

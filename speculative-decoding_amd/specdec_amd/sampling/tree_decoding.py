@@ -16,12 +16,13 @@ by the verify's device outputs (``utils.caching.compact_cache``).
 """
 from __future__ import annotations
 
+from contextlib import nullcontext
 from typing import List, Optional, Tuple
 
 import torch
 from torch.nn import Module
 
-from .. import _lib
+from .. import _lib, tree_attention
 from ..noise import PhiloxNoise
 from ..ops import _user_process, proc_spec, sample_rows, topk_children, verify_tree, verify_tree_distinct
 from ..tree import TokenTree
@@ -52,30 +53,59 @@ def _allowed(tr: TokenTree, cur: int, start: int, nodes, col_of) -> Tuple[torch.
     return allow, torch.tensor([pos], dtype=torch.long)
 
 
+def _descriptors(tr: TokenTree, cur: int, start: int, nodes, col_of):
+    """_allowed's rows as (tree_attention.RowDescriptors, position_ids [1, R]): one integer and one 64-bit
+    word per row in place of the [R, cols] matrix, for the forwards that run on sd_tree_attention."""
+    pos = list(range(start, cur)) + [cur + tr.node_depth[i] - 1 for i in nodes]
+    return tree_attention.row_descriptors(tr, cur, start, nodes, col_of), torch.tensor([pos], dtype=torch.long)
+
+
+def _dense(dsc, cols: int) -> torch.Tensor:
+    """The allow matrix [R, cols] of row descriptors (a forward the kernel does not take)."""
+    allow = torch.zeros(len(dsc.kv_limit), cols, dtype=torch.bool)
+    for r, (lim, bits) in enumerate(zip(dsc.kv_limit, dsc.win_bits)):
+        allow[r, :lim] = True
+        allow[r, [dsc.win_base + j for j in range(64) if bits >> j & 1 and dsc.win_base + j < cols]] = True
+    return allow
+
+
 class _CachedModel:
     """A model, its KV cache and the host's copy of the cache length (the loop keeps one integer per
     model; a StaticCache's own length is a device tensor).  width: a StaticCache's max_cache_len, or
-    None for the DynamicCache the model's first forward returns."""
+    None for the DynamicCache the model's first forward returns.  attention: "mask" (a dense additive
+    mask and the model's own attention) or "kernel" (row descriptors and sd_tree_attention)."""
 
-    def __init__(self, model, dtype, width: Optional[int], dev):
+    def __init__(self, model, dtype, width: Optional[int], dev, attention: str = "mask"):
         self.model, self.dtype, self.width, self.dev = model, dtype, width, dev
+        self.rows_of = _descriptors if attention == "kernel" else _allowed
         self.cache, self.len = None, 0
         if width is not None:
             from transformers.cache_utils import StaticCache
             self.cache = StaticCache(config=model.config, max_cache_len=width)
 
-    def forward(self, tokens: torch.Tensor, allow: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None):
+    def forward(self, tokens: torch.Tensor, allow=None, pos: Optional[torch.Tensor] = None):
         """Logits [R, V] of the R new `tokens` [1, R], appended to the cache at [len, len + R).  allow /
-        pos: from _allowed; None is the plain causal forward."""
+        pos: from _allowed or _descriptors (self.rows_of); None is the plain causal forward.  Descriptors
+        run the forward on sd_tree_attention with no mask built; a forward the kernel does not take
+        (tree_attention.supported) gets their dense mask instead."""
         R = tokens.shape[1]
         kw = {}
+        on_kernel = nullcontext()
+        if isinstance(allow, tree_attention.RowDescriptors):
+            if tree_attention.supported(self.model, R):
+                on_kernel = tree_attention.descriptors(self.model, allow, self.len + R, self.dev)
+                kw.update(position_ids=pos.to(self.dev))
+                allow = None
+            else:
+                allow = _dense(allow, self.len + R)
         if allow is not None:
             mask = torch.full((R, self.width or self.len + R), torch.finfo(self.dtype).min, dtype=self.dtype)
             mask[:, :self.len + R].masked_fill_(allow, 0)          # a StaticCache's tail stays masked
             kw.update(attention_mask=mask[None, None].to(self.dev), position_ids=pos.to(self.dev))
         if self.width is not None:
             kw["cache_position"] = torch.arange(self.len, self.len + R, device=self.dev)
-        out = self.model(input_ids=tokens, past_key_values=self.cache, use_cache=True, **kw)
+        with on_kernel:
+            out = self.model(input_ids=tokens, past_key_values=self.cache, use_cache=True, **kw)
         got = getattr(out, "past_key_values", None)
         if self.width is not None:
             ok = got is self.cache and _static_lengths(got) is not None
@@ -128,7 +158,7 @@ def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, in
             row_of = {0: logits.shape[0] - 1}
         else:                                              # the nodes of the level before, under their ancestor mask
             prev = tr.levels[k - 1]
-            allow, pos = _allowed(tr, cur, cur, prev, slot)
+            allow, pos = dm.rows_of(tr, cur, cur, prev, slot)
             logits = dm.forward(drafts[:, prev], allow, pos)
             row_of = {i + 1: r for r, i in enumerate(prev)}
         for s in sorted({tr.parent[c] + 1 for c in level}):
@@ -143,7 +173,7 @@ def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, in
             toks.clamp_(0, rows.shape[-1] - 1)             # a failed row's -1 never reaches a forward
         drafts[0, torch.tensor(level, dtype=torch.long, device=dev)] = toks
     m = cur - tm.len                                       # committed tokens the target's cache lacks (the root is last)
-    allow, pos = _allowed(tr, cur, tm.len, list(range(N)), list(range(N)))
+    allow, pos = tm.rows_of(tr, cur, tm.len, list(range(N)), list(range(N)))
     tlogits = tm.forward(torch.cat([input_ids[:, tm.len:cur], drafts], 1), allow, pos)
     return tlogits[m - 1:m + N][None], draft_rows, drafts, slot
 
@@ -166,6 +196,7 @@ def tree_speculative_generate(
     tree: Optional[TokenTree] = None,
     trace: Optional[list] = None,
     children: str = "sample",
+    attention: str = "mask",
 ) -> Tuple[List[int], float]:
     """``speculative_generate`` with a token tree per step; returns (tokens, accepted / speculated
     drafts with the tree's depth speculated per step, so the rate compares with
@@ -188,7 +219,14 @@ def tree_speculative_generate(
     row and verifies with ``sd_verify_tree``.  "topk" gives child j of a slot the slot's (j+1)-th best
     drafter token (one ``topk_children`` call per level) and verifies with ``sd_verify_tree_distinct``
     (DESIGN.md §4f): distinct candidates, no drafter rows in the verify, and under greedy exactly the
-    target's greedy decode.  Pick "topk" for greedy and for peaked drafters, "sample" for flat ones."""
+    target's greedy decode.  Pick "topk" for greedy and for peaked drafters, "sample" for flat ones.
+
+    attention (``use_cache=True`` only): "mask" (the default) gives every cached tree forward a dense additive
+    mask built on the host and the model's own attention.  "kernel" hands the forwards' rows to
+    ``sd_tree_attention`` as descriptors: no mask is built, 16-bit transformers models with
+    head_dim 64 or 128; a forward the kernel does not take runs on the dense mask as before."""
+    if attention not in ("mask", "kernel"):
+        raise ValueError(f"attention must be 'mask' or 'kernel', got {attention!r}")
     if children not in ("sample", "topk"):
         raise ValueError(f"children must be 'sample' or 'topk', got {children!r}")
     topk = children == "topk"
@@ -228,7 +266,7 @@ def tree_speculative_generate(
 
     if use_cache:
         width = total_len + tree.num_nodes if static_cache else None
-        tm, dm = _CachedModel(target, t_dtype, width, dev), _CachedModel(drafter, d_dtype, width, dev)
+        tm, dm = _CachedModel(target, t_dtype, width, dev, attention), _CachedModel(drafter, d_dtype, width, dev, attention)
 
     def plain_step():
         """One token from the target's row at the last position (the first token; the last position)."""

@@ -76,6 +76,11 @@ GPU), and callable as ``torch.ops.specdec.*``.
         base + slot(path[b, d]) moves to base + d for d < count[b].  Mutates `tensors`; the sticky error
         word (status_or) stays on the Python API, ops.kv_compact.
 
+    torch.ops.specdec.tree_attention(q [B, Hq, R, D], k, v [B, Hkv, L, D], kv_limit int32 [B, R], win_bits int64 [B, R],
+                                     win_base, scale float?, kv_len int?, splits) -> out [B, R, Hq, D]
+        The attention of a cached tree forward without a mask tensor (sd_tree_attention): row r sees key j
+        below kv_limit[b, r] or where bit j - win_base of win_bits[b, r] is set.
+
 All run the same C-ABI calls as ``specdec_amd.ops`` (libspecdec.so); the parity STREAM noise
 mode keeps generator state on the host side and stays on the Python API.
 """
@@ -439,3 +444,16 @@ def kv_compact(tensors: List[Tensor], path: Tensor, count: Tensor, base: int, nu
 @kv_compact.register_fake
 def _(tensors, path, count, base, num_slots, node_slot=None, base_dev=None):
     return None
+
+
+@torch.library.custom_op("specdec::tree_attention", mutates_args=())
+def tree_attention(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_bits: Tensor, win_base: int,
+                   scale: Optional[float] = None, kv_len: Optional[int] = None, splits: int = 0) -> Tensor:
+    """ops.tree_attention: the attention of a cached tree forward, out [B, R, Hq, D]."""
+    return ops.tree_attention(q, k, v, kv_limit, win_bits, win_base, scale=scale, kv_len=kv_len, splits=splits)
+
+
+@tree_attention.register_fake
+def _(q, k, v, kv_limit, win_bits, win_base, scale=None, kv_len=None, splits=0):
+    B, Hq, R, D = q.shape
+    return q.new_empty(B, R, Hq, D)
