@@ -328,12 +328,14 @@ typedef enum {
     SD_PATH_VERIFY_TREE_DISTINCT = 9,   /* sd_verify_tree_distinct: k_stats, k_treed_rowsum, k_treed_walk */
     SD_PATH_VERIFY_TREE_DYNAMIC = 10,   /* sd_verify_tree_dynamic: the distinct kernels, device parents      */
     SD_PATH_VERIFY_BLOCK = 11,      /* sd_verify_block: k_stats, k_block_mass, k_block_walk            */
+    SD_PATH_VERIFY_TREE_SWOR = 12,  /* sd_verify_tree_swor: k_stats, k_tree_swor_mass x (C_max+1), k_tree_swor_walk */
     SD_PATH_SAMPLE_DRAW_LEAN = 16, /* k_draw_lean (PHILOX multinomial, T = 1, 16-bit)           */
     SD_PATH_SAMPLE_DRAW = 17,       /* k_draw (PHILOX, processors / fp32)                          */
     SD_PATH_SAMPLE_NUCLEUS = 18,    /* k_draw_nuc (PHILOX nucleus by rejection)                    */
     SD_PATH_SAMPLE_STREAM = 19,     /* k_draw_stream (STREAM one pass)                             */
     SD_PATH_SAMPLE_GREEDY_LEAN = 20,/* k_draw_lean<GREEDY>                                          */
     SD_PATH_SAMPLE_MULTI = 21,      /* row statistics + k_rowsample + k_sample_finalize            */
+    SD_PATH_SAMPLE_DISTINCT = 22,   /* sd_sample_distinct: row statistics, k_distinct_keys, k_distinct_merge */
 } sd_path;
 int32_t sd_last_verify_path(void);
 int32_t sd_last_sample_path(void);
@@ -1208,6 +1210,73 @@ typedef struct {
 
 size_t sd_verify_tree_dynamic_workspace_size(int32_t batch, int32_t num_nodes, int32_t vocab);
 int32_t sd_verify_tree_dynamic(const sd_tree_dynamic_args* args, void* stream);
+
+/* ---- Token trees drawn WITHOUT REPLACEMENT (csrc/sample_distinct.hip, csrc/sd_verify_tree_swor.inc;
+ * additive, ABI 12).  "Recursive Speculative Decoding" (Jeon et al., 2024): the children of a slot are
+ * drawn from the slot's drafter row without replacement (Gumbel top-k) and verified by recursive
+ * rejection sampling that renormalises the drafter row after every rejected sibling (RRSw).  Lossless
+ * for stochastic decoding, never proposes a token twice, and the accept test still reads the drafter's
+ * probabilities.
+ *
+ * sd_sample_distinct: k ordered draws without replacement from each of R rows, in one pass.  w_v is the
+ * SD_RULE_SPEC probability of element v (processor, temperature, rounded to the row's dtype: the q[v]
+ * sd_verify_tree_swor reads).  An element with 2^-126 <= w_v < inf (a normal fp32 value) has the fp32 key
+ *     key_v = ln w_v - ln(-ln u_v),   u_v = ((word >> 9) + 0.5) * 2^-23  in (0, 1),
+ * word = word (v & 3) of Philox block (row_base + r, site 5, v >> 2) at the call's offset.  tokens[r, j]
+ * is the element with the j-th largest key (lowest index first among equal keys): descending Gumbel keys
+ * are sequential sampling without replacement, so column j is the j-th draw.  A row that keeps fewer
+ * than k weighted elements fills the rest with -1 (keys: -inf); a row with none is all -1 and ORs
+ * SD_ROW_INVALID_DIST into status_or.  SD_PROC_GREEDY and SD_NOISE_STREAM: SD_ERR_UNSUPPORTED.  rows
+ * 1..SD_SAMPLE_DISTINCT_MAX_ROWS, vocab 1..SD_TREE_GROW_MAX_VOCAB, k 1..SD_TREE_MAX_CHILDREN beyond
+ * which SD_ERR_UNSUPPORTED.  One call consumes one offset.  Kernels: the row statistics (threshold
+ * search and k_stats), k_distinct_keys over (2048-element chunk, row), k_distinct_merge one wave per
+ * row; launch boundaries only (capturable).  sd_last_sample_path: SD_PATH_SAMPLE_DISTINCT.            */
+#define SD_SAMPLE_DISTINCT_MAX_ROWS 64
+
+typedef struct {
+    int32_t rows;                /* R                                                              */
+    int32_t vocab;
+    int32_t k;                   /* draws per row                                                  */
+    int32_t dtype;
+    const void* logits;          /* row r at logits + r * stride_r (elements)                      */
+    int64_t stride_r;
+    sd_processor proc;           /* multinomial, top-k, nucleus, top-k + nucleus                   */
+    sd_noise noise;              /* SD_NOISE_PHILOX                                                */
+    int64_t* tokens;             /* int64 [R, >=k] at tokens + r * tokens_stride_r                  */
+    int64_t tokens_stride_r;
+    float* keys;                 /* nullable: fp32 [R, >=k] at keys + r * keys_stride_r            */
+    int64_t keys_stride_r;
+    int32_t* status_or;          /* nullable                                                       */
+    void* workspace;             /* sd_sample_distinct_workspace_size bytes; the common convention  */
+    size_t workspace_bytes;
+} sd_sample_distinct_args;
+
+/* 0 for a shape the call does not take                                                             */
+size_t sd_sample_distinct_workspace_size(int32_t rows, int32_t vocab, int32_t k);
+int32_t sd_sample_distinct(const sd_sample_distinct_args* args, void* stream);
+
+/* sd_verify_tree_swor: sd_verify_tree for children drawn as above.  Arguments (sd_tree_args), topology,
+ * slots, limits, noise keying, outputs, stop scan and status conventions are sd_verify_tree's; only the
+ * rule at a slot differs.  SD_PROC_GREEDY: SD_ERR_UNSUPPORTED (sd_verify_tree_distinct serves it).
+ *
+ *   p = P(target row s);  q = P(drafter row s);  r = p
+ *   Zq = Σ_v q[v]            (fp32 sums of 2048-element chunks, added in fp64 in chunk order)
+ *   E = {};  Qe = 0 (fp64)
+ *   for c in C (ascending node index = draw order):
+ *       x = tok[c]
+ *       weightless = x outside [0, V) or x in E or not (q[x] > 0)
+ *       f = 0 if weightless else (float)(Zq / (Zq - Qe))                 (exactly 1 while E is empty)
+ *       q~[v] = f * q[v] * [v not in E]
+ *       if not weightless and not (u_c > r[x] / q~[x]): accept c, descend
+ *       m = Σ_v max(r[v] - q~[v], 0);  r = max(r - q~, 0) / m
+ *       if not weightless: E += {x};  Qe += q[x]
+ *   x ~ r, SD_ROW_RESIDUAL
+ *
+ * A weightless child (an id of -1, a repeat, a token the processor cut) is rejected without consulting
+ * its uniform and subtracts nothing; n_sibling_rejects counts it.  With one child per slot the call
+ * equals sd_verify_tree bit for bit.                                                               */
+size_t sd_verify_tree_swor_workspace_size(int32_t batch, int32_t num_nodes, const int32_t* parent, int32_t vocab);
+int32_t sd_verify_tree_swor(const sd_tree_args* args, void* stream);
 
 /* ---- Block verification (csrc/sd_verify_block.inc; additive, ABI 12) --------------------------------
  * One verify step of ONE drafted chain per sequence that tests the drafted block jointly (Sun,

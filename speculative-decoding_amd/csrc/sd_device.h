@@ -709,7 +709,8 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
     return c;
 }
 
-enum PhiloxSite : uint32_t { kSiteAccept = 1, kSiteSample = 2, kSiteCdf = 3 };
+enum PhiloxSite : uint32_t { kSiteAccept = 1, kSiteSample = 2, kSiteCdf = 3, kSiteGumbel = 5 };
+// (4: kSiteNuc, sd_draw_nucleus.inc; 5: the Gumbel keys of sample_distinct.hip; 8: kSiteNgram, sd_ngram.inc)
 
 // counter (idx, global row | site << 24, offset): row is the call-local row, nz.row_base its base
 __device__ __forceinline__ uint4 philox_block(const sd_noise& nz, uint32_t row, uint32_t site, uint32_t idx) {

@@ -115,12 +115,20 @@ __global__ void __launch_bounds__(kThreads) k_multi_rowstat(Plan P) {
     if ((threadIdx.x & 63) == 0) P.rowstat[r] = ms;
 }
 
-// weights of kMultiEpt elements from e0, given their raw values: p (bonus row), or max(r_nrej - q, 0)
-// of a row pair
-template <int DT>
+// What sibling i (0-based) subtracts at element v of a slot's rows: its proposal row there.  The iid rules
+// subtract the drafter row q itself at every sibling; sd_verify_tree_swor.inc's steps renormalise it and
+// drop the elder siblings' tokens.  rank(v) is formed once per element and handed back to sub().
+struct PlainSteps {
+    __device__ __forceinline__ int rank(int64_t) const { return 0; }
+    __device__ __forceinline__ float sub(int, float q, int) const { return q; }
+};
+
+// weights of kMultiEpt elements from e0, given their raw values: p (bonus row), or max(r_nrej - q~_nrej, 0)
+// of a row pair (q~_i: the steps' proposal of sibling i; PlainSteps: q)
+template <int DT, class Steps = PlainSteps>
 __device__ __forceinline__ void multi_weights(const Plan& P, const MultiRow<DT>& T, const MultiRow<DT>& D, bool resid,
                                               int nrej, const float* lmass, int64_t e0, const float* xt,
-                                              const float* xd, float* wv) {
+                                              const float* xd, float* wv, Steps st = Steps{}) {
 #pragma unroll
     for (int e = 0; e < kMultiEpt; ++e) {
         float v = 0.f;
@@ -128,7 +136,13 @@ __device__ __forceinline__ void multi_weights(const Plan& P, const MultiRow<DT>&
             v = multi_prob<DT>(P, T, xt[e], e0 + e);
             if (resid) {
                 const float q = multi_prob<DT>(P, D, xd[e], e0 + e);
-                const float dlt = multi_resid(v, q, nrej, lmass) - q;
+                const int rk = st.rank(e0 + e);
+                float r = v;
+                for (int i = 0; i < nrej; ++i) {
+                    const float dl = r - st.sub(i, q, rk);
+                    r = (dl > 0.f ? dl : 0.f) / lmass[i];
+                }
+                const float dlt = r - st.sub(nrej, q, rk);
                 v = dlt > 0.f ? dlt : 0.f;
             }
         }
@@ -199,11 +213,12 @@ __device__ __forceinline__ bool walk_drawn(const WalkLds& L) {
 // The draw of sd_verify_multi and sd_verify_tree into L.x: under greedy the argmax over the exit's chunk
 // argmaxes `best`; else by inverse CDF, the chunk from the exit's chunk partials `part` (the last
 // residual's, or a target row's), the element from that one chunk, its weights recomputed from the rows
-// rows(false) (target) and, for a residual, rows(true) (drafter).  A picked chunk without a weighted element
+// rows(false) (target) and, for a residual, rows(true) (drafter) under the siblings' steps st.  A picked chunk without a weighted element
 // leaves L.x = -1.
-template <int DT, class Rows>
+template <int DT, class Rows, class Steps = PlainSteps>
 __device__ __forceinline__ void walk_draw(const Plan& P, WalkLds& L, DrawLds& D, int b, int nmc, const float* part,
-                                          const float2* best, bool resid, int nrej, const float* lmass, Rows rows) {
+                                          const float2* best, bool resid, int nrej, const float* lmass, Rows rows,
+                                          Steps st = Steps{}) {
     const int tid = threadIdx.x;
     if (!P.t_stoch) {
         float bv;
@@ -238,7 +253,7 @@ __device__ __forceinline__ void walk_draw(const Plan& P, WalkLds& L, DrawLds& D,
                 Dr = rows(true);
                 multi_load<DT>(Dr, e0, P.V, xd);
             }
-            multi_weights<DT>(P, Tr, Dr, resid, nrej - 1, lmass, e0, xt, xd, wv);
+            multi_weights<DT>(P, Tr, Dr, resid, nrej - 1, lmass, e0, xt, xd, wv, st);
             bool any;
             const int pe = pick_in_chunk<kMultiEpt>(wv, L.target, L.pick, &any);
             if (pe >= 0) L.x = e0 + pe;

@@ -414,6 +414,31 @@ void tree_stats_plan(sd::Plan& Q, const Args* a, int rows, int64_t stride, Row r
     set_rchunks(Q);
 }
 
+// What sd_verify_tree and sd_verify_tree_swor do alike once their arguments are checked and the workspace is
+// carved: T's shape, rows, child lists and outputs, and every k_stats group's Plan
+void tree_rows_and_plans(const sd_tree_args* a, const TreeTopo& t, sd::Tree& T, sd::Plan* G, int ng, const int* row0,
+                         const int* rows) {
+    const int N = t.N;
+    T.B = a->batch; T.N = N; T.R = N + 1 + t.n_int;
+    T.depth = t.depth; T.n_int = t.n_int; T.n_leaf = t.n_leaf;
+    T.tstride = a->target_stride_b; T.dstride = a->draft_stride_b;
+    int int_slot[sd::kTreeSlots];
+    for (int s = 0; s <= N; ++s) {
+        T.trow[s] = a->target_rows[s];
+        T.drow[s] = t.nchild[s] ? a->draft_rows[s] : nullptr;
+        T.idx[s] = (uint8_t)t.idx[s];
+        T.order[s] = (uint8_t)t.order[s];
+        if (t.nchild[s]) int_slot[t.idx[s]] = s;
+    }
+    tree_child_lists(T, t, a->parent);
+    T.out = tree_out(a);
+    for (int g = 0; g < ng; ++g) {
+        const int r0 = row0[g];
+        if (r0 <= N) tree_stats_plan(G[g], a, rows[g], a->target_stride_b, [&](int i) { return a->target_rows[r0 + i]; });
+        else tree_stats_plan(G[g], a, rows[g], a->draft_stride_b, [&](int i) { return a->draft_rows[int_slot[r0 - (N + 1) + i]]; });
+    }
+}
+
 // every group's statistics into the tree's row table [b][R]: the threshold search when the processor keeps
 // a subset, k_stats, k_tree_rowstat
 int32_t launch_tree_stats(const sd::Plan* G, int ng, const int* row0, float2* rowstat, RowKeep* keep, int R,
@@ -468,30 +493,12 @@ int32_t sd_verify_tree(const sd_tree_args* a, void* stream) {
     const int B = a->batch, N = t.N;
     const sd::Plan P = tree_walk_plan(a);
     sd::Tree T{};
-    T.B = B; T.N = N; T.R = N + 1 + t.n_int;
-    T.depth = t.depth; T.n_int = t.n_int; T.n_leaf = t.n_leaf;
-    T.tstride = a->target_stride_b; T.dstride = a->draft_stride_b;
-    int int_slot[sd::kTreeSlots];
-    for (int s = 0; s <= N; ++s) {
-        T.trow[s] = a->target_rows[s];
-        T.drow[s] = t.nchild[s] ? a->draft_rows[s] : nullptr;
-        T.idx[s] = (uint8_t)t.idx[s];
-        T.order[s] = (uint8_t)t.order[s];
-        if (t.nchild[s]) int_slot[t.idx[s]] = s;
-    }
-    tree_child_lists(T, t, a->parent);
-    T.out = tree_out(a);
-
     sd::Plan G[sd::kTreeGroups] = {};
     int row0[sd::kTreeGroups], rows[sd::kTreeGroups];
     const int ng = tree_groups(t, true, row0, rows);
     Carve c{static_cast<char*>(a->workspace)};
     carve_tree(G, T, c, B, t, a->vocab);
-    for (int g = 0; g < ng; ++g) {
-        const int r0 = row0[g];
-        if (r0 <= N) tree_stats_plan(G[g], a, rows[g], a->target_stride_b, [&](int i) { return a->target_rows[r0 + i]; });
-        else tree_stats_plan(G[g], a, rows[g], a->draft_stride_b, [&](int i) { return a->draft_rows[int_slot[r0 - (N + 1) + i]]; });
-    }
+    tree_rows_and_plans(a, t, T, G, ng, row0, rows);
 
     g_verify_path = SD_PATH_NONE;
     if (int32_t st = launch_tree_stats(G, ng, row0, T.rowstat, T.keep, T.R, a->proc, stream)) return st;

@@ -33,6 +33,9 @@
 // target rows, ONE launch of per-chunk row sums and one walk-and-draw launch.  With one topology per
 // sequence, read from device memory (sd_verify_tree_dynamic, sd_verify_tree_dynamic.inc): the same launches,
 // the walk building its child lists in LDS.
+// For children drawn without replacement (sd_verify_tree_swor, sd_verify_tree_swor.inc): sd_verify_tree's
+// launches with the drafter row renormalised after every rejected sibling, and one small launch that forms
+// each slot's steps.  sd_row_table.inc hands the rows' statistics to sample_distinct.hip, which draws them.
 // These walks and the vocabulary-parallel pick (vocab_parallel.hip) draw by one rule, defined once in sd_pick.h.
 //
 // Every logit row is read once by the statistics pass (the algorithmic bytes); the sampling pass
@@ -53,6 +56,7 @@
 #include "sd_host.h"
 #include "sd_index.h"
 #include "sd_pick.h"
+#include "sd_rows.h"
 
 namespace sd {
 
@@ -4690,5 +4694,7 @@ int32_t sd_probs(const sd_probs_args* a, void* stream) {
 #include "sd_verify_multi.inc"
 #include "sd_verify_block.inc"
 #include "sd_verify_tree.inc"
+#include "sd_row_table.inc"
+#include "sd_verify_tree_swor.inc"
 #include "sd_verify_tree_distinct.inc"
 #include "sd_verify_tree_dynamic.inc"

@@ -45,8 +45,10 @@ SD_PATH_VERIFY_TREE = 8
 SD_PATH_VERIFY_TREE_DISTINCT = 9
 SD_PATH_VERIFY_TREE_DYNAMIC = 10
 SD_PATH_VERIFY_BLOCK = 11
+SD_PATH_VERIFY_TREE_SWOR = 12
 SD_PATH_SAMPLE_DRAW_LEAN, SD_PATH_SAMPLE_DRAW, SD_PATH_SAMPLE_NUCLEUS, SD_PATH_SAMPLE_STREAM = 16, 17, 18, 19
 SD_PATH_SAMPLE_GREEDY_LEAN, SD_PATH_SAMPLE_MULTI = 20, 21
+SD_PATH_SAMPLE_DISTINCT = 22
 PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PATH_VERIFY_FUSED: "k_verify_fused",
               SD_PATH_VERIFY_FUSED_TICKET: "k_verify_fused(ticket)",
               SD_PATH_VERIFY_TWO_LAUNCH: "k_stats+k_sample", SD_PATH_VERIFY_STREAM: "stream",
@@ -58,7 +60,9 @@ PATH_NAMES = {SD_PATH_NONE: "none", SD_PATH_VERIFY_LEAN: "k_verify_lean", SD_PAT
               SD_PATH_VERIFY_BLOCK: "k_stats+k_block_mass+k_block_walk",
               SD_PATH_SAMPLE_DRAW_LEAN: "k_draw_lean", SD_PATH_SAMPLE_DRAW: "k_draw", SD_PATH_SAMPLE_NUCLEUS: "k_draw_nuc",
               SD_PATH_SAMPLE_STREAM: "k_draw_stream", SD_PATH_SAMPLE_GREEDY_LEAN: "k_draw_lean<greedy>",
-              SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize"}
+              SD_PATH_SAMPLE_MULTI: "k_stats+k_rowsample+k_sample_finalize",
+              SD_PATH_VERIFY_TREE_SWOR: "k_stats+k_tree_swor_mass+k_tree_swor_steps+k_tree_swor_walk",
+              SD_PATH_SAMPLE_DISTINCT: "k_stats+k_distinct_keys+k_distinct_merge"}
 
 # SPECDEC_LIB selects another in-tree build of the same ABI (e.g. the phase-timing variant)
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get("SPECDEC_LIB", "libspecdec.so"))
@@ -84,6 +88,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_tree_grow_workspace_size", "sd_tree_grow", "sd_tree_select_workspace_size", "sd_tree_select",
            "sd_verify_tree_dynamic_workspace_size", "sd_verify_tree_dynamic",
            "sd_verify_block_workspace_size", "sd_verify_block",
+           "sd_sample_distinct_workspace_size", "sd_sample_distinct",
+           "sd_verify_tree_swor_workspace_size", "sd_verify_tree_swor",
            "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention")
 
 # vocabulary-parallel verify
@@ -100,6 +106,9 @@ SD_TREE_MAX_NODES, SD_TREE_MAX_CHILDREN, SD_TREE_MAX_BATCH = 64, 8, 16384
 
 # dynamic draft trees (sd_tree_grow / sd_tree_select)
 SD_TREE_POOL_MAX, SD_TREE_GROW_MAX_WIDTH, SD_TREE_GROW_MAX_VOCAB = 2048, 8, 524288
+
+# draws without replacement (sd_sample_distinct)
+SD_SAMPLE_DISTINCT_MAX_ROWS = 64
 
 # KV-cache compaction onto a tree path
 SD_KV_MAX_TENSORS = 256
@@ -283,6 +292,18 @@ class sd_tree_args(C.Structure):
         ("tokens_out", C.c_void_p), ("tokens_out_stride_b", C.c_int64),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("status_or", C.c_void_p),
+    ]
+
+
+class sd_sample_distinct_args(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int32), ("vocab", C.c_int32), ("k", C.c_int32), ("dtype", C.c_int32),
+        ("logits", C.c_void_p), ("stride_r", C.c_int64),
+        ("proc", sd_processor), ("noise", sd_noise),
+        ("tokens", C.c_void_p), ("tokens_stride_r", C.c_int64),
+        ("keys", C.c_void_p), ("keys_stride_r", C.c_int64),
+        ("status_or", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
     ]
 
 
@@ -479,6 +500,14 @@ def _load():
     lib.sd_verify_tree.argtypes = [C.POINTER(sd_tree_args), C.c_void_p]
     lib.sd_verify_tree_distinct_workspace_size.restype = C.c_size_t
     lib.sd_verify_tree_distinct_workspace_size.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    lib.sd_verify_tree_swor_workspace_size.restype = C.c_size_t
+    lib.sd_verify_tree_swor_workspace_size.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    lib.sd_verify_tree_swor.restype = C.c_int32
+    lib.sd_verify_tree_swor.argtypes = [C.POINTER(sd_tree_args), C.c_void_p]
+    lib.sd_sample_distinct_workspace_size.restype = C.c_size_t
+    lib.sd_sample_distinct_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.sd_sample_distinct.restype = C.c_int32
+    lib.sd_sample_distinct.argtypes = [C.POINTER(sd_sample_distinct_args), C.c_void_p]
     lib.sd_verify_tree_distinct.restype = C.c_int32
     lib.sd_verify_tree_distinct.argtypes = [C.POINTER(sd_tree_distinct_args), C.c_void_p]
     lib.sd_kv_compact.restype = C.c_int32

@@ -782,13 +782,37 @@ def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
     n_sibling_rejects, stop_index, row_status, of path int32 [B, depth] (the node accepted at each
     depth, -1 beyond n) and tokens_out int64 [B, depth+1] (the path's tokens, then x, then
     pad_token_id; None without want_tokens)."""
+    return _verify_tree("sd_verify_tree", target, draft, draft_tokens, parent, proc, noise, stop_tokens, row_base,
+                        status_or, pad_token_id, want_tokens)
+
+
+def verify_tree_swor(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
+                     stop_tokens: Optional[torch.Tensor] = None, row_base: int = 0,
+                     status_or: Optional[torch.Tensor] = None, pad_token_id: int = 0, want_tokens: bool = True):
+    """One token-tree verify step for children drawn WITHOUT replacement (sd_verify_tree_swor): the
+    children of a slot, in ascending node index, are ``sample_distinct``'s draws of the slot's drafter
+    row, and each is tested against the drafter row renormalised over the tokens its elder siblings did
+    not take, so the emitted tokens keep the target's distribution exactly.  A child of
+    -1, a repeated token or a token the processor cut is rejected and costs nothing.  Arguments and the
+    returned namespace are ``verify_tree``'s; GreedyProcessor is not taken (``verify_tree_distinct``
+    serves it)."""
+    if not proc_spec(proc).stochastic:
+        raise ValueError("verify_tree_swor needs a stochastic processor (greedy: verify_tree_distinct)")
+    return _verify_tree("sd_verify_tree_swor", target, draft, draft_tokens, parent, proc, noise, stop_tokens, row_base,
+                        status_or, pad_token_id, want_tokens)
+
+
+def _verify_tree(entry: str, target, draft, draft_tokens, parent, proc, noise, stop_tokens, row_base, status_or,
+                 pad_token_id, want_tokens):
+    """verify_tree / verify_tree_swor: one argument struct (sd_tree_args), two entry points."""
     from types import SimpleNamespace
+    name = entry[3:]
     if _user_process(proc) is not None:
-        raise TypeError(f"unsupported logits processor {type(proc).__name__}: verify_tree fuses the processing "
+        raise TypeError(f"unsupported logits processor {type(proc).__name__}: {name} fuses the processing "
                         "of target and drafter rows and cannot run a user _process")
     spec = proc_spec(proc)
     if not isinstance(noise, PhiloxNoise):
-        raise TypeError("verify_tree needs PhiloxNoise (the rule defines no stream order for this step)")
+        raise TypeError(f"{name} needs PhiloxNoise (the rule defines no stream order for this step)")
     tree = _tree_of(parent)
     N, depth = tree.num_nodes, tree.depth
     internal = tree.internal_slots
@@ -796,7 +820,7 @@ def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
     t_ptrs, t_stride, B, V, tdt, dev = _slot_rows(target, "target", list(range(N + 1)), N + 1, None)
     d_ptrs, d_stride, _, _, _, _ = _slot_rows(draft, "draft", internal, N + 1, (B, V, tdt, dev))
     if not 1 <= B <= _lib.SD_TREE_MAX_BATCH:
-        raise ValueError(f"verify_tree: batch must be in 1..{_lib.SD_TREE_MAX_BATCH}, got {B}")
+        raise ValueError(f"{name}: batch must be in 1..{_lib.SD_TREE_MAX_BATCH}, got {B}")
     if draft_tokens.dtype != torch.long or draft_tokens.dim() != 2 or draft_tokens.shape[0] != B \
             or draft_tokens.shape[1] < N or draft_tokens.stride(1) != 1 or draft_tokens.device != dev:
         raise ValueError(f"draft_tokens must be int64 [B, >={N}] on {dev}")
@@ -816,7 +840,7 @@ def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
     par = getattr(tree, "_c_parent", None)
     if par is None:
         par = tree._c_parent = (C.c_int32 * _lib.SD_TREE_MAX_NODES)(*tree.parent)
-    ws = _workspace(lib.sd_verify_tree_workspace_size(B, N, par, V), dev)
+    ws = _workspace(getattr(lib, entry + "_workspace_size")(B, N, par, V), dev)
     a = _lib.sd_tree_args()
     a.batch, a.num_nodes, a.vocab = B, N, V
     a.parent = par
@@ -837,7 +861,7 @@ def verify_tree(target, draft, draft_tokens: torch.Tensor, parent, proc, noise,
         a.tokens_out, a.tokens_out_stride_b = out.tokens_out.data_ptr(), depth + 1
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     a.status_or = _status_or_ptr(status_or, dev)
-    _lib.check(lib.sd_verify_tree(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_verify_tree")
+    _lib.check(getattr(lib, entry)(C.byref(a), C.c_void_p(_stream_ptr(dev))), entry)
     del keep
     return out
 
@@ -1109,6 +1133,45 @@ def topk_children(logits_rows: torch.Tensor, k: int) -> torch.Tensor:
     the top-k of the raw logits is the top-k under any temperature and softmax, so no processor is
     applied.  R <= 64, k <= 64."""
     return beam_topk(logits_rows, int(k))[1]
+
+
+def sample_distinct(logits_rows: torch.Tensor, k: int, proc, noise, tokens_out: Optional[torch.Tensor] = None,
+                    keys_out: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None, row_base: int = 0):
+    """k ordered draws WITHOUT replacement from every row of logits [R, V] under ``proc`` (sd_sample_distinct,
+    Gumbel top-k in one pass): int64 [R, k], column j the j-th draw; a row that keeps fewer than k tokens
+    with weight ends in -1.  The weights are the probabilities ``verify_tree_swor`` reads as the drafter's,
+    which is what makes the pair lossless.  Returns (tokens, keys): keys fp32 [R, k] are the winners'
+    Gumbel keys (-inf beside a -1).  proc: a stochastic processor; noise: PhiloxNoise (one offset per call).
+    R <= 64, k <= 8, V <= 524288."""
+    spec = proc_spec(proc)
+    if not spec.stochastic:
+        raise ValueError("sample_distinct needs a stochastic processor (greedy: topk_children)")
+    if not isinstance(noise, PhiloxNoise):
+        raise TypeError("sample_distinct needs PhiloxNoise (the draw defines no stream order)")
+    R, V = logits_rows.shape
+    _require_rows(logits_rows, "logits_rows", V)
+    k = int(k)
+    if not 1 <= R <= _lib.SD_SAMPLE_DISTINCT_MAX_ROWS or not 1 <= k <= _lib.SD_TREE_MAX_CHILDREN \
+            or V > _lib.SD_TREE_GROW_MAX_VOCAB:
+        raise ValueError(f"sample_distinct: rows in 1..{_lib.SD_SAMPLE_DISTINCT_MAX_ROWS}, k in 1.."
+                         f"{_lib.SD_TREE_MAX_CHILDREN}, vocab <= {_lib.SD_TREE_GROW_MAX_VOCAB}; got {R}, {k}, {V}")
+    logits_rows = processed_rows(proc, logits_rows)
+    dev = logits_rows.device
+    tokens = tokens_out if tokens_out is not None else torch.empty(R, k, dtype=torch.long, device=dev)
+    keys = keys_out if keys_out is not None else torch.empty(R, k, dtype=torch.float32, device=dev)
+    for t, dt, nm in ((tokens, torch.long, "tokens_out"), (keys, torch.float32, "keys_out")):
+        if t.dtype != dt or t.shape != (R, k) or t.stride(1) != 1 or t.device != dev:
+            raise ValueError(f"{nm} must be a {dt} [{R}, {k}] tensor on {dev} with a contiguous last axis")
+    nz, keep = _noise_struct(noise, 0, dev, row_base)
+    ws = _workspace(lib.sd_sample_distinct_workspace_size(R, V, k), dev)
+    a = _lib.sd_sample_distinct_args(R, V, k, _DT[logits_rows.dtype], logits_rows.data_ptr(),
+                                     logits_rows.stride(0) if R > 1 else V, spec.struct(), nz,
+                                     tokens.data_ptr(), tokens.stride(0) if R > 1 else k,
+                                     keys.data_ptr(), keys.stride(0) if R > 1 else k,
+                                     _status_or_ptr(status_or, dev), ws.data_ptr(), ws.numel())
+    _lib.check(lib.sd_sample_distinct(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_sample_distinct")
+    del keep
+    return tokens, keys
 
 
 # --------------------------------------------------------------------------- KV-cache compaction

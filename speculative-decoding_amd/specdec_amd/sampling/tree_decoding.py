@@ -24,7 +24,8 @@ from torch.nn import Module
 
 from .. import _lib, tree_attention
 from ..noise import PhiloxNoise
-from ..ops import _user_process, proc_spec, sample_rows, topk_children, verify_tree, verify_tree_distinct
+from ..ops import (_user_process, proc_spec, sample_distinct, sample_rows, topk_children, verify_tree, verify_tree_distinct,
+                   verify_tree_swor)
 from ..tree import TokenTree
 from ..utils.caching import DynamicCache, _static_lengths, compact_cache
 from ..utils.logits_processor import GreedyProcessor, LogitsProcessor
@@ -140,6 +141,20 @@ def _topk_level(logits: torch.Tensor, row_of, tr: TokenTree, level) -> torch.Ten
     return best[torch.tensor(r, dtype=torch.long, device=dev), torch.tensor(j, dtype=torch.long, device=dev)]
 
 
+def _distinct_level(logits: torch.Tensor, row_of, tr: TokenTree, level, spec, noise, err) -> torch.Tensor:
+    """The tokens of a level's nodes under ``children="distinct"``: ONE ``sample_distinct`` call over the rows
+    of the level's distinct parent slots, k the level's largest child count; child j of a slot, in ascending
+    node index, takes draw j (-1 where the slot's row keeps fewer tokens with weight)."""
+    slots = sorted({tr.parent[c] + 1 for c in level})
+    dev = logits.device
+    k = max(len(tr.children[s]) for s in slots)
+    at = torch.tensor([row_of[s] for s in slots], dtype=torch.long, device=dev)
+    draws, _ = sample_distinct(logits.index_select(0, at), k, spec, noise, status_or=err)
+    r = [slots.index(tr.parent[c] + 1) for c in level]
+    j = [tr.children[tr.parent[c] + 1].index(c) for c in level]
+    return draws[torch.tensor(r, dtype=torch.long, device=dev), torch.tensor(j, dtype=torch.long, device=dev)]
+
+
 def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, input_ids, spec, noise, err, pad_token_id,
                  children: str = "sample"):
     """One step's drafting and target forward on the caches: the uncached loop's draws (one sample_rows call
@@ -152,6 +167,8 @@ def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, in
         slot[i] = k
     drafts = torch.full((1, N), pad_token_id, dtype=torch.long, device=dev)
     draft_rows = [None] * (N + 1)
+    # "distinct": a -1 (no token left with weight) stays in the drafts for the verify, the forwards get 0
+    fed = (lambda t: t.clamp(min=0)) if children == "distinct" else (lambda t: t)
     for k, level in enumerate(tr.levels):
         if k == 0:                                         # the committed tokens the cache lacks; the root's row is last
             logits = dm.forward(input_ids[:, dm.len:cur])
@@ -159,12 +176,14 @@ def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, in
         else:                                              # the nodes of the level before, under their ancestor mask
             prev = tr.levels[k - 1]
             allow, pos = dm.rows_of(tr, cur, cur, prev, slot)
-            logits = dm.forward(drafts[:, prev], allow, pos)
+            logits = dm.forward(fed(drafts[:, prev]), allow, pos)
             row_of = {i + 1: r for r, i in enumerate(prev)}
         for s in sorted({tr.parent[c] + 1 for c in level}):
             draft_rows[s] = logits[row_of[s]:row_of[s] + 1, :]
         if children == "topk":
             toks = _topk_level(logits, row_of, tr, level)
+        elif children == "distinct":
+            toks = _distinct_level(logits, row_of, tr, level, spec, noise, err)
         else:
             at = torch.tensor([row_of[tr.parent[c] + 1] for c in level], dtype=torch.long, device=dev)
             rows = logits.index_select(0, at)
@@ -174,7 +193,7 @@ def _cached_rows(tm: _CachedModel, dm: _CachedModel, tr: TokenTree, cur: int, in
         drafts[0, torch.tensor(level, dtype=torch.long, device=dev)] = toks
     m = cur - tm.len                                       # committed tokens the target's cache lacks (the root is last)
     allow, pos = tm.rows_of(tr, cur, tm.len, list(range(N)), list(range(N)))
-    tlogits = tm.forward(torch.cat([input_ids[:, tm.len:cur], drafts], 1), allow, pos)
+    tlogits = tm.forward(torch.cat([input_ids[:, tm.len:cur], fed(drafts)], 1), allow, pos)
     return tlogits[m - 1:m + N][None], draft_rows, drafts, slot
 
 
@@ -220,6 +239,11 @@ def tree_speculative_generate(
     drafter token (one ``topk_children`` call per level) and verifies with ``sd_verify_tree_distinct``
     (DESIGN.md §4f): distinct candidates, no drafter rows in the verify, and under greedy exactly the
     target's greedy decode.  Pick "topk" for greedy and for peaked drafters, "sample" for flat ones.
+    "distinct" draws the children of a slot from the slot's drafter row WITHOUT replacement (one
+    ``sample_distinct`` call per level over the level's distinct parent slots, child j taking draw j) and
+    verifies with ``sd_verify_tree_swor``: lossless for stochastic processors, no token proposed
+    twice, the drafter's probabilities still in the accept test.  With ``GreedyProcessor`` it raises ValueError:
+    use "topk" there.
 
     attention (``use_cache=True`` only): "mask" (the default) gives every cached tree forward a dense additive
     mask built on the host and the model's own attention.  "kernel" hands the forwards' rows to
@@ -227,10 +251,13 @@ def tree_speculative_generate(
     head_dim 64 or 128; a forward the kernel does not take runs on the dense mask as before."""
     if attention not in ("mask", "kernel"):
         raise ValueError(f"attention must be 'mask' or 'kernel', got {attention!r}")
-    if children not in ("sample", "topk"):
-        raise ValueError(f"children must be 'sample' or 'topk', got {children!r}")
-    topk = children == "topk"
+    if children not in ("sample", "topk", "distinct"):
+        raise ValueError(f"children must be 'sample', 'topk' or 'distinct', got {children!r}")
+    topk, distinct = children == "topk", children == "distinct"
     spec = proc_spec(logits_processor)             # TypeError for __call__ / sample overrides
+    if distinct and not spec.stochastic:
+        raise ValueError("children='distinct' draws without replacement and needs a stochastic processor: a greedy "
+                         "row has one token with weight; use children=\"topk\" with GreedyProcessor")
     if _user_process(logits_processor) is not None:
         raise TypeError(f"unsupported logits processor {type(logits_processor).__name__}: the tree verify "
                         "fuses the rows' processing and cannot run a user _process")
@@ -304,6 +331,7 @@ def tree_speculative_generate(
         else:
             seq = torch.cat([input_ids[:, :cur], torch.full((1, N), pad_token_id, dtype=torch.long, device=dev)], 1)
             draft_rows = [None] * (N + 1)
+            raw = torch.full((1, N), pad_token_id, dtype=torch.long, device=dev)   # "distinct": the drafts with their -1
             placed = 0                                 # nodes whose tokens are drawn: those of the levels so far
             for level in tr.levels:                    # one drafter forward and one draw per level
                 logits = _tree_forward(drafter, seq, tr, cur, placed, d_dtype)
@@ -312,6 +340,10 @@ def tree_speculative_generate(
                     draft_rows[s] = logits[cur - 1 + s:cur + s, :]
                 if topk:
                     toks = _topk_level(logits, {s: cur - 1 + s for s in slots}, tr, level)
+                elif distinct:
+                    toks = _distinct_level(logits, {s: cur - 1 + s for s in slots}, tr, level, spec, noise, err)
+                    raw[0, torch.tensor(level, dtype=torch.long, device=dev)] = toks
+                    toks = toks.clamp(min=0)           # a -1 never reaches a forward
                 else:
                     # the parent's row once per child: every child is an independent draw (its own noise row)
                     at = torch.tensor([cur - 1 + tr.parent[c] + 1 for c in level], dtype=torch.long, device=dev)
@@ -322,7 +354,7 @@ def tree_speculative_generate(
                 seq[0, cur + torch.tensor(level, dtype=torch.long, device=dev)] = toks
                 placed = max(placed, max(level) + 1)
             tlogits = _tree_forward(target, seq, tr, cur, N, t_dtype)
-            drafts = seq[:, cur:cur + N].contiguous()
+            drafts = raw if distinct else seq[:, cur:cur + N].contiguous()
             target_rows = tlogits[cur - 1:cur + N][None]
         speculated += depth
         offset = noise.offset
@@ -330,8 +362,8 @@ def tree_speculative_generate(
             out = verify_tree_distinct(target_rows, drafts, tr, spec, noise, stop_tokens=stop_t, status_or=err,
                                        pad_token_id=pad_token_id)
         else:
-            out = verify_tree(target_rows, draft_rows, drafts, tr, spec, noise, stop_tokens=stop_t,
-                              status_or=err, pad_token_id=pad_token_id)
+            out = (verify_tree_swor if distinct else verify_tree)(target_rows, draft_rows, drafts, tr, spec, noise,
+                                                                  stop_tokens=stop_t, status_or=err, pad_token_id=pad_token_id)
         input_ids[0, cur:cur + depth + 1] = out.tokens_out[0]          # the path's tokens, x, pad
         n, x, status, stop_index, rejects, bits = (int(v) for v in torch.stack([
             out.n_accepted[0].long(), out.next_token[0], out.row_status[0].long(), out.stop_index[0].long(),

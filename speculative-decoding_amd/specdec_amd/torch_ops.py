@@ -38,6 +38,13 @@ GPU), and callable as ``torch.ops.specdec.*``.
         One token-tree verify step whose children are distinct candidates, e.g. the drafter's top-c tokens
         (sd_verify_tree_distinct): no drafter rows, Philox noise.
 
+    torch.ops.specdec.sample_distinct(logits [R, V], k, kind, temperature, top_k, top_p, seed, offset, row_base)
+        -> (tokens int64 [R, k], keys fp32 [R, k])
+        k ordered draws without replacement per row (sd_sample_distinct, Gumbel top-k), -1 past a row's support.
+    torch.ops.specdec.verify_tree_swor(...verify_tree's arguments...) -> verify_tree's outputs
+        verify_tree for children drawn by sample_distinct (sd_verify_tree_swor): the drafter row renormalised
+        after every rejected sibling.
+
     torch.ops.specdec.tree_grow(logits [B, F, V], level, width, branch, pool_token int64 [B, P], pool_score fp32 [B, P],
                                 pool_parent int32 [B, P], frontier_in int32 [B, F]?)
         -> (frontier_token int64 [B, F'], frontier_pool int32 [B, F'], frontier_parent_rank int32 [B, F'],
@@ -200,6 +207,40 @@ def _(target, draft, draft_tokens, parent, stop_tokens, kind, temperature, top_k
     dt = {"next_token": torch.long, "resample_mass": torch.float32}
     return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.TREE_FIELDS) + (
         target.new_empty(B, TokenTree(list(parent)).depth, dtype=torch.int32),)
+
+
+@torch.library.custom_op("specdec::verify_tree_swor", mutates_args=())
+def verify_tree_swor(target: Tensor, draft: Tensor, draft_tokens: Tensor, parent: List[int], stop_tokens: Tensor, kind: int,
+                     temperature: float, top_k: int, top_p: float, seed: int, offset: int,
+                     row_base: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """verify_tree for children drawn without replacement (ops.verify_tree_swor): the same arguments and outputs."""
+    out = ops.verify_tree_swor(target, draft, draft_tokens, list(parent), _spec(kind, temperature, top_k, top_p),
+                               PhiloxNoise(seed, offset), stop_tokens=stop_tokens, row_base=row_base, want_tokens=False)
+    # views of one buffer: outputs may not alias
+    return tuple(getattr(out, f).clone() for f in ops.TREE_FIELDS) + (out.path.clone(),)
+
+
+@verify_tree_swor.register_fake
+def _(target, draft, draft_tokens, parent, stop_tokens, kind, temperature, top_k, top_p, seed, offset, row_base):
+    from .tree import TokenTree
+    B = target.shape[0]
+    dt = {"next_token": torch.long, "resample_mass": torch.float32}
+    return tuple(target.new_empty(B, dtype=dt.get(f, torch.int32)) for f in ops.TREE_FIELDS) + (
+        target.new_empty(B, TokenTree(list(parent)).depth, dtype=torch.int32),)
+
+
+@torch.library.custom_op("specdec::sample_distinct", mutates_args=())
+def sample_distinct(logits: Tensor, k: int, kind: int, temperature: float, top_k: int, top_p: float, seed: int,
+                    offset: int, row_base: int) -> Tuple[Tensor, Tensor]:
+    """k ordered draws without replacement per row (ops.sample_distinct): tokens int64 [R, k], keys fp32 [R, k]."""
+    return ops.sample_distinct(logits, k, _spec(kind, temperature, top_k, top_p), PhiloxNoise(seed, offset),
+                               row_base=row_base)
+
+
+@sample_distinct.register_fake
+def _(logits, k, kind, temperature, top_k, top_p, seed, offset, row_base):
+    R = logits.shape[0]
+    return logits.new_empty(R, k, dtype=torch.long), logits.new_empty(R, k, dtype=torch.float32)
 
 
 @torch.library.custom_op("specdec::verify_tree_distinct", mutates_args=())
