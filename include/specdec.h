@@ -1076,6 +1076,10 @@ typedef struct {
 } sd_kv_compact_args;
 
 int32_t sd_kv_compact(const sd_kv_compact_args* args, void* stream);
+/* The same call for a ragged batch: base_dev (required) is a device int64 [B] and base_b = base +
+ * base_dev[b].  Bounds and status are per sequence as above: a sequence whose window leaves the cache
+ * moves nothing and raises the bit, the others move.                                                 */
+int32_t sd_kv_compact_ragged(const sd_kv_compact_args* args, void* stream);
 
 /* ---- Dynamic draft trees: growth on the device (csrc/tree_grow.hip; additive, ABI 12) -----------------
  * EAGLE-2 style context-dependent trees without a host read of the drafter's scores.  The host knows
@@ -1437,6 +1441,70 @@ int32_t sd_tree_attention_splits(int32_t batch, int32_t heads_kv, int32_t kv_len
 size_t sd_tree_attention_workspace_size(int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t rows,
                                         int32_t head_dim, int32_t kv_len, int32_t splits);
 int32_t sd_tree_attention(const sd_tree_attention_args* args, void* stream);
+
+/* ---- Tree attention over a ragged batch: lengths read on the device (csrc/tree_attention.hip; additive, ABI 12)
+ * sd_tree_attention with the valid length and the window base PER SEQUENCE, in device memory, so that a
+ * batch whose sequences hold different numbers of committed tokens is one call and a captured call follows
+ * the cache as it grows.  For sequence b
+ *
+ *     len_b      = clamp(kv_len_dev[b] + kv_len_add, 0, kv_cap)
+ *     win_base_b = win_base_dev[b] + win_base_add
+ *
+ * and row r of b sees key j when j < len_b and (j < kv_limit[b][r] or bit j - win_base_b of win_bits[b][r]
+ * is set): the rule above with (len_b, win_base_b) for (kv_len, win_base).  Both arrays are int64 so that a
+ * cache's `cumulative_length` tensor is passed as it stands; the host addends say whether the R new rows are
+ * counted in it already.  kv_cap (host) bounds every length: 1 <= kv_cap <= kv_alloc, and nothing at or
+ * beyond kv_cap is read.  A sum outside [0, kv_cap] is clamped and ORs SD_ROW_INVALID_DIST into status_or.
+ * A sequence with len_b = 0, like a row that sees nothing, gets zeros; a position no row of its sequence
+ * sees, or at or beyond len_b, is never loaded.
+ *
+ * The host cannot see the lengths, so the keys are cut into CHUNKS of a fixed number of 64-key tiles
+ * (`chunk_tiles`: 0 lets (batch, heads_kv, kv_cap) decide, another value pins it), C = ceil(ceil(kv_cap / 64)
+ * / chunk_tiles) <= SD_TREE_ATTN_MAX_SPLITS chunk slots (a pinned value that needs more: SD_ERR_UNSUPPORTED).
+ * k_tattn_ragged_partial runs on (C, K/V head, sequence); a workgroup whose chunk starts at or beyond len_b
+ * leaves at once and writes nothing, so the work follows each sequence's own length.  With C = 1 it writes
+ * `out` and no workspace is needed; else k_tattn_ragged_combine merges, in ascending order, exactly the
+ * chunks len_b reaches.  Launch boundaries are the only synchronisation (capturable, safe on a shared GPU).
+ * A sequence's output is a function of its own inputs, kv_cap and the chunk length alone: the other sequences
+ * of the batch never change a bit of it.  Limits, alignment and statuses otherwise as sd_tree_attention;
+ * kv_len_dev and win_base_dev must be given and 8-byte aligned.                                          */
+typedef struct {
+    int32_t batch;               /* B (<= 65535)                                                    */
+    int32_t heads_q;             /* Hq                                                              */
+    int32_t heads_kv;            /* Hkv (<= 65535)                                                  */
+    int32_t rows;                /* R, 1..SD_TREE_ATTN_MAX_ROWS                                      */
+    int32_t head_dim;            /* D: 64 or 128                                                    */
+    int32_t dtype;               /* SD_BF16 or SD_F16                                               */
+    int32_t kv_cap;              /* upper bound of every len_b, 1..SD_TREE_ATTN_MAX_KV               */
+    int32_t kv_alloc;            /* positions k / v hold per (b, head); >= kv_cap                   */
+    int32_t chunk_tiles;         /* 0: by the shapes; else the 64-key tiles of a chunk (tests)       */
+    float scale;
+    const void* q;               /* as sd_tree_attention_args                                       */
+    int64_t q_stride_b, q_stride_h, q_stride_r;
+    const void* k;
+    const void* v;
+    int64_t k_stride_b, k_stride_h, k_stride_pos;
+    int64_t v_stride_b, v_stride_h, v_stride_pos;
+    void* out;
+    int64_t out_stride_b, out_stride_r, out_stride_h;
+    const int32_t* kv_limit;     /* device int32 [B, R], contiguous                                 */
+    const uint64_t* win_bits;    /* device uint64 [B, R], contiguous                                */
+    const int64_t* kv_len_dev;   /* device int64 [B]                                                */
+    int64_t kv_len_add;
+    const int64_t* win_base_dev; /* device int64 [B]                                                */
+    int64_t win_base_add;
+    int32_t* status_or;          /* nullable device int32 [1]                                       */
+    void* workspace;             /* sd_tree_attention_ragged_workspace_size bytes; may be null when
+                                    the call runs one chunk slot                                    */
+    size_t workspace_bytes;
+} sd_tree_attention_ragged_args;
+
+/* chunk slots C the call runs (its grid), 0 for shapes it does not take                              */
+int32_t sd_tree_attention_ragged_chunks(int32_t batch, int32_t heads_kv, int32_t kv_cap, int32_t chunk_tiles);
+/* 0 for a shape sd_tree_attention_ragged does not take                                               */
+size_t sd_tree_attention_ragged_workspace_size(int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t rows,
+                                               int32_t head_dim, int32_t kv_cap, int32_t chunk_tiles);
+int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,8 @@
 //                     arguments.  A thread owns ONE 16-byte range of the rows of one (tensor, b, head)
 //                     for all depths and copies it in W-byte accesses (W = 16, 8, 4 or 2, the widest
 //                     the pointers, strides and row_bytes are all multiples of).
+//   k_kv_compact_ragged<W>   the same body with one base per sequence, base + base_dev[b]
+//                     (sd_kv_compact_ragged): a batch whose sequences hold different numbers of tokens.
 //
 // The in-place hazard.  slot(path[d]) >= d (checked on the device), so dst = base + d <= src, but
 // depth d's destination can be depth d-1's source (path [1, 2, 3] shifts everything by one).  A
@@ -34,7 +36,7 @@ struct KvCompact {
     int32_t has_slots;
     int32_t batch, heads, chunks, max_depth, num_slots, row_bytes;
     int64_t stride_b, stride_h, stride_pos, num_positions, base;
-    const int64_t* base_dev;
+    const int64_t* base_dev;   // [1], or [B] for k_kv_compact_ragged
     const int32_t* path;
     int64_t path_stride_b;
     const int32_t* count;
@@ -50,8 +52,9 @@ template <> struct KvVec<8> { using type = kv_u32x2; };
 template <> struct KvVec<4> { using type = uint32_t; };
 template <> struct KvVec<2> { using type = uint16_t; };
 
-template <int W>
-__global__ void __launch_bounds__(kKvThreads) k_kv_compact(KvCompact P) {
+// PER_SEQ: base_dev holds one base per sequence (sd_kv_compact_ragged), else one for the batch
+template <int W, bool PER_SEQ>
+__device__ __forceinline__ void kv_compact_body(const KvCompact& P) {
     using V = typename KvVec<W>::type;
     constexpr int NV = kKvChunk / W;
     // the slot map into LDS by constant indices (a dynamic index into the arguments would spill them)
@@ -71,7 +74,7 @@ __global__ void __launch_bounds__(kKvThreads) k_kv_compact(KvCompact P) {
     const int32_t cnt = P.count[b];
     const int lim = cnt < P.max_depth ? (cnt > 0 ? cnt : 0) : P.max_depth;
     if (lim == 0) return;
-    const int64_t base = P.base + (P.base_dev ? *P.base_dev : 0);
+    const int64_t base = P.base + (PER_SEQ ? P.base_dev[b] : (P.base_dev ? *P.base_dev : 0));
     if (base < 0 || base > P.num_positions - P.num_slots) {           // the window leaves the cache
         if (reporter && P.status_or) atomicOr(P.status_or, SD_ROW_INVALID_DIST);
         return;
@@ -123,9 +126,21 @@ __global__ void __launch_bounds__(kKvThreads) k_kv_compact(KvCompact P) {
     if (bad && reporter && P.status_or) atomicOr(P.status_or, SD_ROW_INVALID_DIST);
 }
 
+template <int W>
+__global__ void __launch_bounds__(kKvThreads) k_kv_compact(KvCompact P) {
+    kv_compact_body<W, false>(P);
+}
+
+template <int W>
+__global__ void __launch_bounds__(kKvThreads) k_kv_compact_ragged(KvCompact P) {
+    kv_compact_body<W, true>(P);
+}
+
 }  // namespace sd
 
-extern "C" int32_t sd_kv_compact(const sd_kv_compact_args* a, void* stream) {
+// sd_kv_compact (per_seq false: base_dev nullable, one element) and sd_kv_compact_ragged (true: base_dev
+// given, one element per sequence)
+static int32_t kv_compact_call(const sd_kv_compact_args* a, void* stream, bool per_seq) {
     using namespace sd_host;
     if (!a || !a->tensors) return SD_ERR_INVALID;
     if (a->n_tensors < 1) return SD_ERR_INVALID;
@@ -136,6 +151,7 @@ extern "C" int32_t sd_kv_compact(const sd_kv_compact_args* a, void* stream) {
     if (a->max_depth < 1 || a->num_slots < 1) return SD_ERR_INVALID;
     if (a->max_depth > SD_MAX_GAMMA || a->num_slots > SD_TREE_MAX_NODES) return SD_ERR_UNSUPPORTED;
     if (a->num_positions < a->num_slots) return SD_ERR_INVALID;
+    if (per_seq && !a->base_dev) return SD_ERR_INVALID;
     if (!a->base_dev && (a->base < 0 || a->base > a->num_positions - a->num_slots)) return SD_ERR_INVALID;
     if (!a->path || !a->count || a->path_stride_b < a->max_depth) return SD_ERR_INVALID;
     if ((reinterpret_cast<uintptr_t>(a->path) | reinterpret_cast<uintptr_t>(a->count) |
@@ -177,6 +193,15 @@ extern "C" int32_t sd_kv_compact(const sd_kv_compact_args* a, void* stream) {
     clear_stale_error();
     const dim3 grid((unsigned)blocks, (unsigned)a->n_tensors);
     return dispatch_int<16, 8, 4, 2>(width, [&](auto w) {
+        if (per_seq) return launch(sd::k_kv_compact_ragged<decltype(w)::value>, grid, dim3(sd::kKvThreads), 0, stream, P);
         return launch(sd::k_kv_compact<decltype(w)::value>, grid, dim3(sd::kKvThreads), 0, stream, P);
     });
+}
+
+extern "C" int32_t sd_kv_compact(const sd_kv_compact_args* a, void* stream) {
+    return kv_compact_call(a, stream, false);
+}
+
+extern "C" int32_t sd_kv_compact_ragged(const sd_kv_compact_args* a, void* stream) {
+    return kv_compact_call(a, stream, true);
 }

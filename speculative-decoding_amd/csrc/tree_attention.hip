@@ -32,6 +32,16 @@
 //   k_tattn_combine<dtype>      one thread per (b, h, r, 4 head-dim elements): the splits' partials
 //       merged in ascending split order, out = sum_s 2^(m_s - m) O_s / sum_s 2^(m_s - m) l_s.
 //
+// Ragged batches (sd_tree_attention_ragged): every sequence has its own valid length and window base, in
+// device memory, so the host can neither derive spans from a length nor size the grid by one.
+//   k_tattn_ragged_partial<dtype, D>   grid (C, Hkv, B).  The keys are cut into C chunk slots of a FIXED
+//       number of tiles, chosen from (B, Hkv, kv_cap) alone; workgroup (c, hkv, b) reads len_b and win_base_b
+//       (two scalar loads), leaves at once when its chunk starts at or beyond len_b, and else runs the same
+//       tile body (csrc/tattn_tile.inc, compiled once per kernel) over its chunk cut off at len_b.
+//   k_tattn_ragged_combine<dtype>      k_tattn_combine over the chunks len_b reaches, and no others: a
+//       slot beyond them was not written in this call.  A sequence's result depends on its own inputs,
+//       kv_cap and the chunk length only.
+//
 // Launch boundaries are the only synchronisation.  The workspace's common counter block is skipped.
 #include "sd_device.h"
 #include "sd_host.h"
@@ -113,239 +123,103 @@ struct TaParams {
 
 template <int DT, int D>
 __global__ void __launch_bounds__(kTaThreads) k_tattn_partial(TaParams P) {
-    using T = TaType<DT>;
-    using E = typename T::elem;
-    using V8 = typename T::vec8;
-    constexpr int CH = D / 8;         // 16-byte chunks of a K/V row
-    constexpr int KQ = CH + 1;        // 16-byte units of a K row in LDS (one of padding)
-    constexpr int KL = CH / 4;        // K chunks a thread loads per tile
-    constexpr int VL = CH / 8;        // (key pair, chunk) units a thread loads per tile
+#define TA_KV_LEN P.kv_len
+#define TA_WIN_BASE P.win_base
+#define TA_T_BEGIN (int)((int64_t)split * n_tiles / P.splits)
+#define TA_T_END (int)((int64_t)(split + 1) * n_tiles / P.splits)
+#include "tattn_tile.inc"
+#undef TA_KV_LEN
+#undef TA_WIN_BASE
+#undef TA_T_BEGIN
+#undef TA_T_END
+}
+
+// What sd_tree_attention_ragged adds to TaParams (whose kv_len and win_base it leaves unused; P.splits
+// holds the chunk slots C): the per-sequence lengths and window bases, read when the kernels run.
+struct TaRagged {
+    const int64_t* kv_len_dev;    // [B]
+    const int64_t* win_base_dev;  // [B]
+    int64_t kv_len_add, win_base_add;
+    int32_t* status_or;           // nullable
+    int32_t kv_cap, chunk_tiles;
+};
+
+// len_b = clamp(kv_len_dev[b] + kv_len_add, 0, kv_cap); *bad: the sum lay outside [0, kv_cap]
+__device__ __forceinline__ int32_t ta_ragged_len(const TaRagged& Rg, int64_t b, bool* bad) {
+    const int64_t len = (int64_t)((uint64_t)Rg.kv_len_dev[b] + (uint64_t)Rg.kv_len_add);
+    *bad = len < 0 || len > Rg.kv_cap;
+    return (int32_t)(len < 0 ? 0 : (len > Rg.kv_cap ? Rg.kv_cap : len));
+}
+
+// grid (C, Hkv, B).  Chunk c of a sequence is the tiles [c * chunk_tiles, (c + 1) * chunk_tiles) cut off
+// at the sequence's own tile count: a chunk that starts at or beyond len_b leaves before any barrier or
+// K/V load and writes nothing (k_tattn_ragged_combine does not read it).  With C = 1 the one chunk always
+// runs, so that a sequence of length 0 gets its zeros here.
+template <int DT, int D>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_partial(TaParams P, TaRagged Rg) {
+    const int c = blockIdx.x, b = blockIdx.z;
+    bool bad;
+    const int32_t len = ta_ragged_len(Rg, b, &bad);
+    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
+    // chunk c starts at tile c * chunk_tiles (< 2^14 tiles: no overflow)
+    if ((int64_t)c * Rg.chunk_tiles * kTaTile >= len && P.part_ml != nullptr) return;
+    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
+    {
+#define TA_KV_LEN len
+#define TA_WIN_BASE rg_win_base
+#define TA_T_BEGIN split * Rg.chunk_tiles
+#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+#include "tattn_tile.inc"
+#undef TA_KV_LEN
+#undef TA_WIN_BASE
+#undef TA_T_BEGIN
+#undef TA_T_END
+    }
+}
+
+// k_tattn_combine over the chunks a sequence's own length reaches: chunks 0 .. ceil(tiles_b / chunk_tiles) - 1
+// were written by this call's k_tattn_ragged_partial, the slots behind them were not and are not read.
+template <int DT>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_combine(TaParams P, TaRagged Rg, int64_t total) {
+    using E = typename TaType<DT>::elem;
     constexpr float kNegInf = -__builtin_inff();
-    __shared__ ta_u32x4 s_k[kTaTile * KQ];
-    __shared__ uint32_t s_vt[D * kTaVtWords];
-    __shared__ int32_t s_lim[SD_TREE_ATTN_MAX_ROWS];
-    __shared__ uint64_t s_bits[SD_TREE_ATTN_MAX_ROWS];
-    __shared__ int32_t s_any_lim[2];
-    __shared__ uint64_t s_any_bits[2];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, col = lane & 31;
-    const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
-    const int R = P.rows, G = P.group, M = R * G;
-    const int64_t win_base = P.win_base;
-
-    // the rows' descriptors, clamped to the valid keys, and their union over the sequence
-    if (tid < SD_TREE_ATTN_MAX_ROWS) {
-        int32_t lim = 0;
-        uint64_t bits = 0;
-        if (tid < R) {
-            lim = P.kv_limit[(int64_t)b * R + tid];
-            lim = lim < 0 ? 0 : (lim > P.kv_len ? P.kv_len : lim);
-            bits = P.win_bits[(int64_t)b * R + tid] & ta_range_mask(-win_base, (int64_t)P.kv_len - win_base);
-        }
-        s_lim[tid] = lim;
-        s_bits[tid] = bits;
-        for (int o = 32; o; o >>= 1) {
-            const int32_t l2 = __shfl_xor(lim, o);
-            lim = l2 > lim ? l2 : lim;
-            bits |= (uint64_t)__shfl_xor((unsigned long long)bits, o);
-        }
-        if (lane == 0) { s_any_lim[wave] = lim; s_any_bits[wave] = bits; }
+    const int64_t idx = (int64_t)blockIdx.x * kTaThreads + threadIdx.x;
+    if (idx >= total) return;
+    const int D = P.head_dim, R = P.rows, G = P.group, M = R * G;
+    const int q4 = D / 4;
+    const int d = (int)(idx % q4) * 4;
+    const int64_t row = idx / q4;
+    const int r = (int)(row % R);
+    const int64_t bh = row / R;
+    const int heads_q = P.heads_kv * G;
+    const int hq = (int)(bh % heads_q);
+    const int64_t b = bh / heads_q;
+    const int hkv = hq / G, m = (hq - hkv * G) * R + r;
+    bool bad;
+    const int32_t len = ta_ragged_len(Rg, b, &bad);
+    const int n_tiles = (len + kTaTile - 1) / kTaTile;
+    const int chunks = (n_tiles + Rg.chunk_tiles - 1) / Rg.chunk_tiles;     // <= P.splits, 0 for an empty sequence
+    const int64_t prow0 = ((b * P.heads_kv + hkv) * P.splits) * M + m;     // chunk c: + c * M
+    float mx = kNegInf;
+    for (int c = 0; c < chunks; ++c) mx = fmaxf(mx, P.part_ml[2 * (prow0 + (int64_t)c * M)]);
+    ta_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int c = 0; c < chunks; ++c) {            // ascending: the sum's order never depends on timing
+        const int64_t prow = prow0 + (int64_t)c * M;
+        const float ms = P.part_ml[2 * prow];
+        if (ms == kNegInf) continue;              // an empty partial: its O was never written
+        const float w = ta_exp2(ms - mx);
+        l += w * P.part_ml[2 * prow + 1];
+        const ta_f32x4 y = *reinterpret_cast<const ta_f32x4*>(P.part_o + prow * D + d);
+        acc += w * y;
     }
-    __syncthreads();
-    const int32_t any_lim = s_any_lim[0] > s_any_lim[1] ? s_any_lim[0] : s_any_lim[1];
-    const uint64_t any_bits = s_any_bits[0] | s_any_bits[1];
-
-    const int n_tiles = (P.kv_len + kTaTile - 1) / kTaTile;
-    const int t_begin = (int)((int64_t)split * n_tiles / P.splits);
-    const int t_end = (int)((int64_t)(split + 1) * n_tiles / P.splits);
-    // the first tile at or after t that some row of the sequence can see (t_end: none)
-    auto next_tile = [&](int t) {
-        for (; t < t_end; ++t) {
-            const int64_t t0 = (int64_t)t * kTaTile;
-            if (t0 < any_lim || (any_bits & ta_range_mask(t0 - win_base, t0 + kTaTile - win_base))) break;
-        }
-        return t;
-    };
-
-    const E* kb = static_cast<const E*>(P.k) + b * P.k_sb + hkv * P.k_sh;
-    const E* vb = static_cast<const E*>(P.v) + b * P.v_sb + hkv * P.v_sh;
-    ta_u32x4 kreg[KL], vreg[VL][2];
-    const ta_u32x4 zero4 = {0u, 0u, 0u, 0u};
-    // a tile's K and V into registers; a key no row sees is not read
-    auto load_tile = [&](int t) {
+    typedef E vec4 __attribute__((ext_vector_type(4)));
+    vec4 y;
+    const float inv = l > 0.f ? 1.f / l : 0.f;
 #pragma unroll
-        for (int it = 0; it < KL; ++it) {
-            const int idx = it * kTaThreads + tid, key = idx / CH, c = idx % CH;
-            const int32_t kj = t * kTaTile + key;
-            kreg[it] = zero4;
-            if (ta_visible(kj, any_lim, any_bits, win_base))
-                kreg[it] = *reinterpret_cast<const ta_u32x4*>(kb + kj * P.k_sp + c * 8);
-        }
-#pragma unroll
-        for (int it = 0; it < VL; ++it) {
-            const int idx = it * kTaThreads + tid, pair = idx / CH, c = idx % CH;
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int32_t kj = t * kTaTile + 2 * pair + e;
-                vreg[it][e] = zero4;
-                if (ta_visible(kj, any_lim, any_bits, win_base))
-                    vreg[it][e] = *reinterpret_cast<const ta_u32x4*>(vb + kj * P.v_sp + c * 8);
-            }
-        }
-    };
-    // the registers into LDS: K as it is, V transposed with the two keys of a pair in one dword
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int it = 0; it < KL; ++it) {
-            const int idx = it * kTaThreads + tid, key = idx / CH, c = idx % CH;
-            s_k[key * KQ + c] = kreg[it];
-        }
-#pragma unroll
-        for (int it = 0; it < VL; ++it) {
-            const int idx = it * kTaThreads + tid, pair = idx / CH, c = idx % CH;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const uint32_t e0 = (vreg[it][0][i >> 1] >> (16 * (i & 1))) & 0xffffu;
-                const uint32_t e1 = (vreg[it][1][i >> 1] >> (16 * (i & 1))) & 0xffffu;
-                s_vt[(c * 8 + i) * kTaVtWords + pair] = e0 | (e1 << 16);
-            }
-        }
-    };
-
-    const int n_pass = (M + 4 * kTaRowTile - 1) / (4 * kTaRowTile);
-#pragma unroll 1
-    for (int pass = 0; pass < n_pass; ++pass) {
-        const int m = (pass * 4 + wave) * kTaRowTile + col;     // the lane's query row of the group
-        const bool wave_rows = (pass * 4 + wave) * kTaRowTile < M;
-        const bool valid = m < M;
-        const int g = valid ? m / R : 0, r = valid ? m - g * R : 0;
-        const int hq = hkv * G + g;
-        const int32_t my_lim = valid ? s_lim[r] : 0;
-        const uint64_t my_bits = valid ? s_bits[r] : 0;
-
-        // Q^T as the first product's B operand: row `col`, head-dim elements 16s + 8 half .. + 7
-        V8 qreg[D / 16];
-        {
-            const E* qrow = static_cast<const E*>(P.q) + b * P.q_sb + hq * P.q_sh + r * P.q_sr + 8 * half;
-#pragma unroll
-            for (int s = 0; s < D / 16; ++s) {
-                ta_u32x4 w = zero4;
-                if (valid) w = *reinterpret_cast<const ta_u32x4*>(qrow + 16 * s);
-                qreg[s] = __builtin_bit_cast(V8, w);
-            }
-        }
-        ta_f32x16 o[D / 32];
-#pragma unroll
-        for (int dm = 0; dm < D / 32; ++dm)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) o[dm][i] = 0.f;
-        float m_run = kNegInf, l_run = 0.f;
-
-        int t = next_tile(t_begin);
-        if (t < t_end) load_tile(t);
-#pragma unroll 1
-        while (t < t_end) {
-            __syncthreads();          // the tile before is read by every wave
-            store_tile();
-            __syncthreads();
-            const int tc = t;
-            t = next_tile(t + 1);
-            if (t < t_end) load_tile(t);    // in flight under this tile's arithmetic
-            if (!wave_rows) continue;
-
-            // S^T[key][row] = K . Q^T: the lane holds row `col`, keys 32 mt + 8 (i / 4) + 4 half + i % 4
-            ta_f32x16 sacc[2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sacc[mt][i] = 0.f;
-#pragma unroll
-                for (int s = 0; s < D / 16; ++s) {
-                    const V8 a = __builtin_bit_cast(V8, s_k[(32 * mt + col) * KQ + 2 * s + half]);
-                    sacc[mt] = T::mfma(a, qreg[s], sacc[mt]);
-                }
-            }
-            float t_max = kNegInf;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int32_t kj = tc * kTaTile + 32 * mt + 8 * (i >> 2) + 4 * half + (i & 3);
-                    const float x = ta_visible(kj, my_lim, my_bits, win_base) ? sacc[mt][i] * P.scale_log2 : kNegInf;
-                    sacc[mt][i] = x;
-                    t_max = fmaxf(t_max, x);
-                }
-            t_max = fmaxf(t_max, __shfl_xor(t_max, 32));
-            const float m_new = fmaxf(m_run, t_max);
-            const bool none = m_new == kNegInf;                  // the row has seen no key yet
-            const float alpha = none ? 1.f : ta_exp2(m_run - m_new);
-            const float m_sub = none ? 0.f : m_new;
-            float p_sum = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float p = ta_exp2(sacc[mt][i] - m_sub);   // a masked key: 2^-inf = 0
-                    sacc[mt][i] = p;
-                    p_sum += p;
-                }
-            p_sum += __shfl_xor(p_sum, 32);
-            l_run = l_run * alpha + p_sum;
-            m_run = m_new;
-#pragma unroll
-            for (int dm = 0; dm < D / 32; ++dm)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) o[dm][i] *= alpha;
-            // O^T[d][row] += V^T . P^T over 4 steps of 16 keys; step s takes the keys 16 s + 8 j + 4 half + e
-            // (j = 0, 1; e = 0..3), which the lane holds as sacc[s / 2][8 (s % 2) + 4 j + e]
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                V8 pb;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) pb[i] = (E)sacc[s >> 1][8 * (s & 1) + i];
-#pragma unroll
-                for (int dm = 0; dm < D / 32; ++dm) {
-                    const uint32_t* vrow = s_vt + (32 * dm + col) * kTaVtWords + 8 * s + 2 * half;
-                    const ta_u32x4 w = {vrow[0], vrow[1], vrow[4], vrow[5]};
-                    o[dm] = T::mfma(__builtin_bit_cast(V8, w), pb, o[dm]);
-                }
-            }
-        }
-
-        if (!valid) continue;
-        // the lane holds O[row][32 dm + 8 (i / 4) + 4 half + i % 4]: four consecutive elements per i / 4
-        if (P.part_ml == nullptr) {
-            const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-            E* orow = static_cast<E*>(P.out) + b * P.o_sb + r * P.o_sr + hq * P.o_sh + 4 * half;
-#pragma unroll
-            for (int dm = 0; dm < D / 32; ++dm)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    typedef E vec4 __attribute__((ext_vector_type(4)));
-                    vec4 y;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) y[e] = l_run > 0.f ? (E)(o[dm][4 * j + e] * inv) : (E)0.f;
-                    *reinterpret_cast<ta_u32x2*>(orow + 32 * dm + 8 * j) = __builtin_bit_cast(ta_u32x2, y);
-                }
-        } else {
-            const int64_t prow = (((int64_t)b * P.heads_kv + hkv) * P.splits + split) * M + m;
-            if (half == 0) {
-                P.part_ml[2 * prow] = m_run;
-                P.part_ml[2 * prow + 1] = l_run;
-            }
-            if (m_run != kNegInf) {      // the combine never reads the O of an empty partial
-                float* po = P.part_o + prow * D + 4 * half;
-#pragma unroll
-                for (int dm = 0; dm < D / 32; ++dm)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const ta_f32x4 y = {o[dm][4 * j], o[dm][4 * j + 1], o[dm][4 * j + 2], o[dm][4 * j + 3]};
-                        *reinterpret_cast<ta_f32x4*>(po + 32 * dm + 8 * j) = y;
-                    }
-            }
-        }
-    }
+    for (int e = 0; e < 4; ++e) y[e] = l > 0.f ? (E)(acc[e] * inv) : (E)0.f;
+    E* o = static_cast<E*>(P.out) + b * P.o_sb + r * P.o_sr + hq * P.o_sh + d;
+    *reinterpret_cast<ta_u32x2*>(o) = __builtin_bit_cast(ta_u32x2, y);
 }
 
 template <int DT>
@@ -402,6 +276,31 @@ static int ta_splits(int64_t batch, int64_t heads_kv, int32_t kv_len, int32_t sp
     return splits < tiles ? splits : tiles;
 }
 
+// The 64-key tiles of a chunk of sd_tree_attention_ragged: a function of the host-known bounds alone,
+// since the lengths are on the device.  Auto (0): ta_splits' reasoning carried over to kv_cap — as many
+// chunk slots as fill the device (kTaFill over B * Hkv) but no chunk shorter than kTaTilesPerSplit
+// tiles — then lengthened until the slots fit SD_TREE_ATTN_MAX_SPLITS.  A first choice, not a tuned
+// one: it sizes the grid for sequences as long as kv_cap, which a ragged batch's are not.
+static int ta_chunk_tiles(int64_t batch, int64_t heads_kv, int32_t kv_cap, int32_t chunk_tiles) {
+    const int tiles = (kv_cap + kTaTile - 1) / kTaTile;
+    if (chunk_tiles != 0) return chunk_tiles < tiles ? chunk_tiles : tiles;     // pinned
+    const int64_t heads = batch * heads_kv;
+    const int64_t by_fill = (kTaFill + heads - 1) / heads;                 // chunk slots that fill the device
+    int64_t ct = (tiles + by_fill - 1) / by_fill;
+    if (ct < kTaTilesPerSplit) ct = kTaTilesPerSplit;
+    const int64_t by_slots = (tiles + SD_TREE_ATTN_MAX_SPLITS - 1) / SD_TREE_ATTN_MAX_SPLITS;
+    if (ct < by_slots) ct = by_slots;
+    return (int)(ct < tiles ? ct : tiles);
+}
+
+// the chunk slots C of a call (its grid.x), 0 when a pinned chunk length needs more than the limit
+static int ta_chunks(int64_t batch, int64_t heads_kv, int32_t kv_cap, int32_t chunk_tiles) {
+    const int tiles = (kv_cap + kTaTile - 1) / kTaTile;
+    const int ct = ta_chunk_tiles(batch, heads_kv, kv_cap, chunk_tiles);
+    const int64_t c = ((int64_t)tiles + ct - 1) / ct;
+    return c > SD_TREE_ATTN_MAX_SPLITS ? 0 : (int)c;
+}
+
 // SD_OK when sd_tree_attention takes the shape
 static int32_t ta_check_shape(int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t rows, int32_t head_dim,
                               int32_t kv_len, int32_t splits) {
@@ -437,6 +336,44 @@ static TaWorkspace ta_carve(void* base, int64_t batch, int64_t heads_q, int64_t 
     return w;
 }
 
+// the tensor fields sd_tree_attention_args and sd_tree_attention_ragged_args share: SD_OK when the
+// pointers are given and every address the kernels form from them keeps its alignment
+template <typename A>
+static int32_t ta_check_tensors(const A* a) {
+    if (!a->q || !a->k || !a->v || !a->out || !a->kv_limit || !a->win_bits) return SD_ERR_INVALID;
+    if (!(a->scale == a->scale)) return SD_ERR_INVALID;
+    // 16-byte accesses: every address the kernels form is a multiple of 16 bytes (8 elements)
+    const int64_t strides[] = {a->q_stride_b, a->q_stride_h, a->q_stride_r, a->k_stride_b, a->k_stride_h, a->k_stride_pos,
+                               a->v_stride_b, a->v_stride_h, a->v_stride_pos, a->out_stride_b, a->out_stride_r,
+                               a->out_stride_h};
+    for (int64_t s : strides)
+        if (s < 0 || (s & 7)) return SD_ERR_INVALID;
+    if (a->q_stride_r < a->head_dim || a->k_stride_pos < a->head_dim || a->v_stride_pos < a->head_dim ||
+        a->out_stride_h < a->head_dim)
+        return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
+         reinterpret_cast<uintptr_t>(a->out)) & 15)
+        return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a->kv_limit) & 3) || (reinterpret_cast<uintptr_t>(a->win_bits) & 7)) return SD_ERR_INVALID;
+    return SD_OK;
+}
+
+// the fields both argument structs share, into the kernels' parameters
+template <typename A>
+static TaParams ta_params(const A* a, const TaWorkspace& w, int splits) {
+    TaParams P{};
+    P.q = a->q; P.k = a->k; P.v = a->v; P.out = a->out; P.kv_limit = a->kv_limit; P.win_bits = a->win_bits;
+    P.part_ml = w.ml; P.part_o = w.o;
+    P.q_sb = a->q_stride_b; P.q_sh = a->q_stride_h; P.q_sr = a->q_stride_r;
+    P.k_sb = a->k_stride_b; P.k_sh = a->k_stride_h; P.k_sp = a->k_stride_pos;
+    P.v_sb = a->v_stride_b; P.v_sh = a->v_stride_h; P.v_sp = a->v_stride_pos;
+    P.o_sb = a->out_stride_b; P.o_sr = a->out_stride_r; P.o_sh = a->out_stride_h;
+    P.rows = a->rows; P.group = a->heads_q / a->heads_kv; P.heads_kv = a->heads_kv;
+    P.splits = splits; P.head_dim = a->head_dim;
+    P.scale_log2 = a->scale * 1.4426950408889634f;
+    return P;
+}
+
 }  // namespace sd
 
 extern "C" int32_t sd_tree_attention_splits(int32_t batch, int32_t heads_kv, int32_t kv_len, int32_t splits) {
@@ -460,21 +397,8 @@ extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stre
     const int32_t shape = sd::ta_check_shape(a->batch, a->heads_q, a->heads_kv, a->rows, a->head_dim, a->kv_len, a->splits);
     if (shape != SD_OK) return shape;
     if (a->kv_alloc < a->kv_len) return SD_ERR_INVALID;
-    if (!a->q || !a->k || !a->v || !a->out || !a->kv_limit || !a->win_bits) return SD_ERR_INVALID;
-    if (!(a->scale == a->scale)) return SD_ERR_INVALID;
-    // 16-byte accesses: every address the kernels form is a multiple of 16 bytes (8 elements)
-    const int64_t strides[] = {a->q_stride_b, a->q_stride_h, a->q_stride_r, a->k_stride_b, a->k_stride_h, a->k_stride_pos,
-                               a->v_stride_b, a->v_stride_h, a->v_stride_pos, a->out_stride_b, a->out_stride_r,
-                               a->out_stride_h};
-    for (int64_t s : strides)
-        if (s < 0 || (s & 7)) return SD_ERR_INVALID;
-    if (a->q_stride_r < a->head_dim || a->k_stride_pos < a->head_dim || a->v_stride_pos < a->head_dim ||
-        a->out_stride_h < a->head_dim)
-        return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
-         reinterpret_cast<uintptr_t>(a->out)) & 15)
-        return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->kv_limit) & 3) || (reinterpret_cast<uintptr_t>(a->win_bits) & 7)) return SD_ERR_INVALID;
+    const int32_t tensors = sd::ta_check_tensors(a);
+    if (tensors != SD_OK) return tensors;
     const int splits = sd::ta_splits(a->batch, a->heads_kv, a->kv_len, a->splits);
     sd::TaWorkspace w{nullptr, nullptr, 0};
     if (splits > 1) {
@@ -482,17 +406,8 @@ extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stre
         if (!a->workspace || a->workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
         if (reinterpret_cast<uintptr_t>(a->workspace) & 255) return SD_ERR_INVALID;
     }
-    sd::TaParams P{};
-    P.q = a->q; P.k = a->k; P.v = a->v; P.out = a->out; P.kv_limit = a->kv_limit; P.win_bits = a->win_bits;
-    P.part_ml = w.ml; P.part_o = w.o;
-    P.q_sb = a->q_stride_b; P.q_sh = a->q_stride_h; P.q_sr = a->q_stride_r;
-    P.k_sb = a->k_stride_b; P.k_sh = a->k_stride_h; P.k_sp = a->k_stride_pos;
-    P.v_sb = a->v_stride_b; P.v_sh = a->v_stride_h; P.v_sp = a->v_stride_pos;
-    P.o_sb = a->out_stride_b; P.o_sr = a->out_stride_r; P.o_sh = a->out_stride_h;
-    P.win_base = a->win_base;
-    P.rows = a->rows; P.group = a->heads_q / a->heads_kv; P.heads_kv = a->heads_kv; P.kv_len = a->kv_len;
-    P.splits = splits; P.head_dim = a->head_dim;
-    P.scale_log2 = a->scale * 1.4426950408889634f;
+    sd::TaParams P = sd::ta_params(a, w, splits);
+    P.win_base = a->win_base; P.kv_len = a->kv_len;
     clear_stale_error();
     const dim3 grid((unsigned)splits, (unsigned)a->heads_kv, (unsigned)a->batch);
     int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
@@ -506,5 +421,62 @@ extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stre
     const dim3 cgrid((unsigned)((total + sd::kTaThreads - 1) / sd::kTaThreads));
     return dispatch_dtype16(a->dtype, [&](auto dt) {
         return launch(sd::k_tattn_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, total);
+    });
+}
+
+// ---- ragged batches: per-sequence lengths and window bases read on the device ---------------------------
+extern "C" int32_t sd_tree_attention_ragged_chunks(int32_t batch, int32_t heads_kv, int32_t kv_cap, int32_t chunk_tiles) {
+    if (batch < 1 || heads_kv < 1 || kv_cap < 1 || kv_cap > SD_TREE_ATTN_MAX_KV || chunk_tiles < 0) return 0;
+    return sd::ta_chunks(batch, heads_kv, kv_cap, chunk_tiles);
+}
+
+extern "C" size_t sd_tree_attention_ragged_workspace_size(int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t rows,
+                                                          int32_t head_dim, int32_t kv_cap, int32_t chunk_tiles) {
+    if (chunk_tiles < 0 || sd::ta_check_shape(batch, heads_q, heads_kv, rows, head_dim, kv_cap, 0) != SD_OK) return 0;
+    const int chunks = sd::ta_chunks(batch, heads_kv, kv_cap, chunk_tiles);
+    return chunks ? sd::ta_carve(nullptr, batch, heads_q, rows, head_dim, chunks).bytes : 0;
+}
+
+extern "C" int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args* a, void* stream) {
+    using namespace sd_host;
+    if (!a) return SD_ERR_INVALID;
+    if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
+    if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;
+    if (a->chunk_tiles < 0) return SD_ERR_INVALID;
+    const int32_t shape = sd::ta_check_shape(a->batch, a->heads_q, a->heads_kv, a->rows, a->head_dim, a->kv_cap, 0);
+    if (shape != SD_OK) return shape;
+    if (a->kv_alloc < a->kv_cap) return SD_ERR_INVALID;
+    const int32_t tensors = sd::ta_check_tensors(a);
+    if (tensors != SD_OK) return tensors;
+    if (!a->kv_len_dev || !a->win_base_dev) return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a->kv_len_dev) | reinterpret_cast<uintptr_t>(a->win_base_dev)) & 7) return SD_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(a->status_or) & 3) return SD_ERR_INVALID;
+    const int chunks = sd::ta_chunks(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
+    if (chunks == 0) return SD_ERR_UNSUPPORTED;             // a pinned chunk length that needs too many slots
+    sd::TaWorkspace w{nullptr, nullptr, 0};
+    if (chunks > 1) {
+        w = sd::ta_carve(a->workspace, a->batch, a->heads_q, a->rows, a->head_dim, chunks);
+        if (!a->workspace || a->workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(a->workspace) & 255) return SD_ERR_INVALID;
+    }
+    const sd::TaParams P = sd::ta_params(a, w, chunks);
+    sd::TaRagged Rg{};
+    Rg.kv_len_dev = a->kv_len_dev; Rg.win_base_dev = a->win_base_dev;
+    Rg.kv_len_add = a->kv_len_add; Rg.win_base_add = a->win_base_add;
+    Rg.status_or = a->status_or; Rg.kv_cap = a->kv_cap;
+    Rg.chunk_tiles = sd::ta_chunk_tiles(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
+    clear_stale_error();
+    const dim3 grid((unsigned)chunks, (unsigned)a->heads_kv, (unsigned)a->batch);
+    int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
+        return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
+            return launch(sd::k_tattn_ragged_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
+                          0, stream, P, Rg);
+        });
+    });
+    if (st != SD_OK || chunks == 1) return st;
+    const int64_t total = (int64_t)a->batch * a->heads_q * a->rows * (a->head_dim / 4);
+    const dim3 cgrid((unsigned)((total + sd::kTaThreads - 1) / sd::kTaThreads));
+    return dispatch_dtype16(a->dtype, [&](auto dt) {
+        return launch(sd::k_tattn_ragged_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, Rg, total);
     });
 }

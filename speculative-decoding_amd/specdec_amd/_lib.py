@@ -84,13 +84,14 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_vp_keep_hist", "sd_vp_keep_refine", "sd_vp_keep_decide", "sd_vp_keep_finish",
            "sd_verify_tree_workspace_size", "sd_verify_tree",
            "sd_verify_tree_distinct_workspace_size", "sd_verify_tree_distinct",
-           "sd_kv_compact",
+           "sd_kv_compact", "sd_kv_compact_ragged",
            "sd_tree_grow_workspace_size", "sd_tree_grow", "sd_tree_select_workspace_size", "sd_tree_select",
            "sd_verify_tree_dynamic_workspace_size", "sd_verify_tree_dynamic",
            "sd_verify_block_workspace_size", "sd_verify_block",
            "sd_sample_distinct_workspace_size", "sd_sample_distinct",
            "sd_verify_tree_swor_workspace_size", "sd_verify_tree_swor",
-           "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention")
+           "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention",
+           "sd_tree_attention_ragged_chunks", "sd_tree_attention_ragged_workspace_size", "sd_tree_attention_ragged")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -399,6 +400,24 @@ class sd_tree_attention_args(C.Structure):
     ]
 
 
+class sd_tree_attention_ragged_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("heads_q", C.c_int32), ("heads_kv", C.c_int32), ("rows", C.c_int32),
+        ("head_dim", C.c_int32), ("dtype", C.c_int32), ("kv_cap", C.c_int32), ("kv_alloc", C.c_int32),
+        ("chunk_tiles", C.c_int32), ("scale", C.c_float),
+        ("q", C.c_void_p), ("q_stride_b", C.c_int64), ("q_stride_h", C.c_int64), ("q_stride_r", C.c_int64),
+        ("k", C.c_void_p), ("v", C.c_void_p),
+        ("k_stride_b", C.c_int64), ("k_stride_h", C.c_int64), ("k_stride_pos", C.c_int64),
+        ("v_stride_b", C.c_int64), ("v_stride_h", C.c_int64), ("v_stride_pos", C.c_int64),
+        ("out", C.c_void_p), ("out_stride_b", C.c_int64), ("out_stride_r", C.c_int64), ("out_stride_h", C.c_int64),
+        ("kv_limit", C.c_void_p), ("win_bits", C.c_void_p),
+        ("kv_len_dev", C.c_void_p), ("kv_len_add", C.c_int64),
+        ("win_base_dev", C.c_void_p), ("win_base_add", C.c_int64),
+        ("status_or", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class sd_vp_header(C.Structure):
     _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
                 ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
@@ -518,6 +537,14 @@ def _load():
     lib.sd_tree_attention_workspace_size.argtypes = [C.c_int32] * 7
     lib.sd_tree_attention.restype = C.c_int32
     lib.sd_tree_attention.argtypes = [C.POINTER(sd_tree_attention_args), C.c_void_p]
+    lib.sd_kv_compact_ragged.restype = C.c_int32
+    lib.sd_kv_compact_ragged.argtypes = [C.POINTER(sd_kv_compact_args), C.c_void_p]
+    lib.sd_tree_attention_ragged_chunks.restype = C.c_int32
+    lib.sd_tree_attention_ragged_chunks.argtypes = [C.c_int32] * 4
+    lib.sd_tree_attention_ragged_workspace_size.restype = C.c_size_t
+    lib.sd_tree_attention_ragged_workspace_size.argtypes = [C.c_int32] * 7
+    lib.sd_tree_attention_ragged.restype = C.c_int32
+    lib.sd_tree_attention_ragged.argtypes = [C.POINTER(sd_tree_attention_ragged_args), C.c_void_p]
     lib.sd_tree_grow_workspace_size.restype = C.c_size_t
     lib.sd_tree_grow_workspace_size.argtypes = [C.c_int32] * 5
     lib.sd_tree_grow.restype = C.c_int32

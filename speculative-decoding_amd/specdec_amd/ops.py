@@ -1185,7 +1185,9 @@ def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, n
     returns them (``path``, ``n_accepted``): nothing is read back.  slot(i) is ``node_slot[i]`` (a host
     sequence: node index -> the order in which the node entered the cache) or i.  base_dev: an int64
     device tensor of one element added to ``base`` when the kernel runs (a StaticLayer's
-    ``cumulative_length``), so a captured step needs no host value.  Only positions
+    ``cumulative_length``), so a captured step needs no host value; with B > 1 elements it holds one base
+    per sequence (sd_kv_compact_ragged: a batch whose sequences hold different numbers of tokens, bounds and
+    status per sequence).  Only positions
     [base, base + num_slots) are read or written; a path entry that leaves the window ends its
     sequence's moves and ORs SD_ROW_INVALID_DIST into ``status_or``.  More than SD_KV_MAX_TENSORS
     tensors take one launch per 256, on the current stream."""
@@ -1217,8 +1219,11 @@ def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, n
     if base_dev is None:
         if not 0 <= base <= L - num_slots:
             raise ValueError(f"kv_compact: positions [{base}, {base + num_slots}) leave the cache's {L}")
-    elif base_dev.dtype != torch.int64 or base_dev.numel() != 1 or base_dev.device != dev:
-        raise ValueError("kv_compact: base_dev must be an int64 tensor of one element on the tensors' device")
+    elif base_dev.dtype != torch.int64 or base_dev.numel() not in (1, B) or base_dev.device != dev \
+            or not base_dev.is_contiguous():
+        raise ValueError("kv_compact: base_dev must be a contiguous int64 tensor of one or B elements on the tensors' device")
+    per_seq = base_dev is not None and B > 1 and base_dev.numel() == B     # a base per sequence: sd_kv_compact_ragged
+    call, name = (lib.sd_kv_compact_ragged, "sd_kv_compact_ragged") if per_seq else (lib.sd_kv_compact, "sd_kv_compact")
     slots = None
     if node_slot is not None:
         node_slot = [int(s) for s in node_slot]
@@ -1240,7 +1245,7 @@ def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, n
         part = tensors[i:i + _lib.SD_KV_MAX_TENSORS]
         table = (C.c_void_p * len(part))(*(t.data_ptr() for t in part))
         a.n_tensors, a.tensors = len(part), table
-        _lib.check(lib.sd_kv_compact(C.byref(a), stream), "sd_kv_compact")
+        _lib.check(call(C.byref(a), stream), name)
 
 
 # --------------------------------------------------------------------------- tree attention
@@ -1250,10 +1255,75 @@ def tree_attention_splits(batch: int, heads_kv: int, kv_len: int, splits: int = 
     return int(lib.sd_tree_attention_splits(int(batch), int(heads_kv), int(kv_len), int(splits)))
 
 
+def tree_attention_chunks(batch: int, heads_kv: int, kv_cap: int, chunk_tiles: int = 0) -> int:
+    """The chunk slots a ragged ``tree_attention`` call runs (sd_tree_attention_ragged_chunks): a function of
+    the host-known bounds alone; 0 for a shape it does not take or a pinned chunk length that needs more
+    than SD_TREE_ATTN_MAX_SPLITS slots."""
+    return int(lib.sd_tree_attention_ragged_chunks(int(batch), int(heads_kv), int(kv_cap), int(chunk_tiles)))
+
+
+def _ta_tensors(a, q, k, v, out, kv_limit, win_bits, D):
+    """The tensor fields sd_tree_attention_args and sd_tree_attention_ragged_args share."""
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    # a dimension of size 1 may carry any stride: it is never stepped along
+    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.q_stride_r = a.q_stride_r or D
+    a.k_stride_b, a.k_stride_h, a.k_stride_pos = (k.stride(i) if k.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.k_stride_pos = a.k_stride_pos or D
+    a.v_stride_b, a.v_stride_h, a.v_stride_pos = (v.stride(i) if v.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.v_stride_pos = a.v_stride_pos or D
+    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.out_stride_h = a.out_stride_h or D
+    a.kv_limit, a.win_bits = kv_limit.data_ptr(), win_bits.data_ptr()
+
+
+def _ta_workspace(a, workspace, need, dev):
+    if workspace is None and need:
+        workspace = _workspace(need, dev)
+    if workspace is not None:
+        if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise ValueError("tree_attention: workspace must be a contiguous uint8 tensor on the call's device")
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    return workspace
+
+
+def _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles, kv_len_add,
+                           win_base_add, status_or, workspace):
+    """tree_attention with a device tensor for kv_len and / or win_base (sd_tree_attention_ragged)."""
+    B, Hq, R, D = q.shape
+    Hkv, L, dev = k.shape[1], k.shape[2], q.device
+    kv_cap = L if kv_cap is None else int(kv_cap)
+    if not 1 <= kv_cap <= L:
+        raise ValueError(f"tree_attention: kv_cap {kv_cap} outside 1..{L}")
+    per_seq = []
+    for name, x, default in (("kv_len", kv_len, kv_cap), ("win_base", win_base, 0)):
+        if not torch.is_tensor(x):                     # a host value, expanded on the device: nothing is read back
+            x = torch.full((B,), default if x is None else int(x), dtype=torch.int64, device=dev)
+        elif x.dtype != torch.int64 or x.shape != (B,) or x.device != dev or not x.is_contiguous():
+            raise ValueError(f"tree_attention: a {name} tensor must be a contiguous int64 [{B}] on {dev}")
+        per_seq.append(x)
+    a = _lib.sd_tree_attention_ragged_args()
+    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
+    a.kv_cap, a.kv_alloc, a.chunk_tiles = kv_cap, L, int(chunk_tiles)
+    a.scale = float(D) ** -0.5 if scale is None else float(scale)
+    _ta_tensors(a, q, k, v, out, kv_limit, win_bits, D)
+    a.kv_len_dev, a.kv_len_add = per_seq[0].data_ptr(), int(kv_len_add)
+    a.win_base_dev, a.win_base_add = per_seq[1].data_ptr(), int(win_base_add)
+    a.status_or = _status_or_ptr(status_or, dev)
+    need = lib.sd_tree_attention_ragged_workspace_size(B, Hq, Hkv, R, D, kv_cap, int(chunk_tiles))
+    one = tree_attention_chunks(B, Hkv, kv_cap, chunk_tiles) <= 1
+    keep = _ta_workspace(a, workspace, 0 if one else need, dev)
+    _lib.check(lib.sd_tree_attention_ragged(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention_ragged")
+    del keep, per_seq
+    return out
+
+
 def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: torch.Tensor, win_bits: torch.Tensor,
-                   win_base: int, scale: Optional[float] = None, kv_len: Optional[int] = None,
+                   win_base, scale: Optional[float] = None, kv_len=None,
                    out: Optional[torch.Tensor] = None, splits: int = 0, *,
-                   workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   workspace: Optional[torch.Tensor] = None, kv_cap: Optional[int] = None, chunk_tiles: int = 0,
+                   kv_len_add: int = 0, win_base_add: int = 0,
+                   status_or: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The attention of a cached tree forward without a mask tensor (sd_tree_attention, MFMA kernels).
 
     q: [B, Hq, R, D]; k, v: [B, Hkv, L, D] (a cache layer's tensors; the first ``kv_len`` positions are
@@ -1264,7 +1334,17 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     ``scale`` (default D ** -0.5) applied to the fp32 score; a row that sees nothing gets zeros.
     splits: 0 lets the shapes decide, another value pins the split-KV count (tests).  workspace: a
     uint8 device tensor of the caller's (default: the stream's shared workspace).  Shapes and dtypes the
-    kernels do not take raise SpecdecError with the library's status."""
+    kernels do not take raise SpecdecError with the library's status.
+
+    Ragged batches: ``kv_len`` and / or ``win_base`` may be an int64 device tensor [B] (a cache's
+    ``cumulative_length`` as it stands); the call then runs sd_tree_attention_ragged, which reads the
+    lengths on the device, so a batch of sequences of different lengths is one call and a captured call
+    follows the cache.  An int given for the other is expanded on the device, nothing is read back.
+    Sequence b's length is ``clamp(kv_len[b] + kv_len_add, 0, kv_cap)`` and its window starts at
+    ``win_base[b] + win_base_add``.  kv_cap (default L): the host's bound on every length; nothing at or
+    beyond it is read.  chunk_tiles: 0 lets (B, Hkv, kv_cap) decide the fixed chunk length, another value
+    pins its 64-key tiles (tests); ``splits`` is not used.  status_or: int32 [1], gets SD_ROW_INVALID_DIST
+    when a length had to be clamped.  A sequence's output does not depend on the batch's other sequences."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("tree_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D]")
     B, Hq, R, D = q.shape
@@ -1278,9 +1358,14 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
         raise ValueError("tree_attention: q, k and v must share one floating dtype")
     if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
         raise ValueError("tree_attention: the head dimension must have unit stride")
-    kv_len = L if kv_len is None else int(kv_len)
-    if not 1 <= kv_len <= L:
-        raise ValueError(f"tree_attention: kv_len {kv_len} outside 1..{L}")
+    ragged = torch.is_tensor(kv_len) or torch.is_tensor(win_base)
+    if not ragged:
+        if kv_cap is not None or chunk_tiles or kv_len_add or win_base_add or status_or is not None:
+            raise ValueError("tree_attention: kv_cap, chunk_tiles, the addends and status_or go with a kv_len or "
+                             "win_base tensor")
+        kv_len = L if kv_len is None else int(kv_len)
+        if not 1 <= kv_len <= L:
+            raise ValueError(f"tree_attention: kv_len {kv_len} outside 1..{L}")
     if kv_limit.dtype != torch.int32 or kv_limit.shape != (B, R) or not kv_limit.is_contiguous() or kv_limit.device != dev:
         raise ValueError(f"tree_attention: kv_limit must be a contiguous int32 [{B}, {R}] on {dev}")
     if win_bits.dtype not in (torch.int64, torch.uint64) or win_bits.shape != (B, R) or not win_bits.is_contiguous() \
@@ -1290,28 +1375,17 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
         out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
     elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
         raise ValueError(f"tree_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
+    if ragged:
+        return _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles,
+                                      kv_len_add, win_base_add, status_or, workspace)
     a = _lib.sd_tree_attention_args()
     a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
     a.kv_len, a.kv_alloc, a.splits = kv_len, L, int(splits)
     a.scale = float(D) ** -0.5 if scale is None else float(scale)
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    # a dimension of size 1 may carry any stride: it is never stepped along
-    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.q_stride_r = a.q_stride_r or D
-    a.k_stride_b, a.k_stride_h, a.k_stride_pos = (k.stride(i) if k.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.k_stride_pos = a.k_stride_pos or D
-    a.v_stride_b, a.v_stride_h, a.v_stride_pos = (v.stride(i) if v.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.v_stride_pos = a.v_stride_pos or D
-    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.out_stride_h = a.out_stride_h or D
-    a.kv_limit, a.win_bits, a.win_base = kv_limit.data_ptr(), win_bits.data_ptr(), int(win_base)
+    _ta_tensors(a, q, k, v, out, kv_limit, win_bits, D)
+    a.win_base = int(win_base)
     need = lib.sd_tree_attention_workspace_size(B, Hq, Hkv, R, D, kv_len, int(splits))
-    if workspace is None and need and tree_attention_splits(B, Hkv, kv_len, splits) > 1:
-        workspace = _workspace(need, dev)
-    if workspace is not None:
-        if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
-            raise ValueError("tree_attention: workspace must be a contiguous uint8 tensor on the call's device")
-        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    workspace = _ta_workspace(a, workspace, need if tree_attention_splits(B, Hkv, kv_len, splits) > 1 else 0, dev)
     _lib.check(lib.sd_tree_attention(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention")
     return out
 

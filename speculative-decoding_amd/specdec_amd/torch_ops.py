@@ -88,6 +88,12 @@ GPU), and callable as ``torch.ops.specdec.*``.
         The attention of a cached tree forward without a mask tensor (sd_tree_attention): row r sees key j
         below kv_limit[b, r] or where bit j - win_base of win_bits[b, r] is set.
 
+    torch.ops.specdec.tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base int64 [B], kv_len int64 [B], scale float?,
+                                            kv_cap int?, chunk_tiles, kv_len_add, win_base_add) -> out [B, R, Hq, D]
+        The same attention over a ragged batch (sd_tree_attention_ragged): sequence b's valid length
+        kv_len[b] + kv_len_add (clamped to kv_cap) and window base win_base[b] + win_base_add are read on the
+        device, so a captured call follows the cache.
+
 All run the same C-ABI calls as ``specdec_amd.ops`` (libspecdec.so); the parity STREAM noise
 mode keeps generator state on the host side and stays on the Python API.
 """
@@ -496,5 +502,21 @@ def tree_attention(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_bits: 
 
 @tree_attention.register_fake
 def _(q, k, v, kv_limit, win_bits, win_base, scale=None, kv_len=None, splits=0):
+    B, Hq, R, D = q.shape
+    return q.new_empty(B, R, Hq, D)
+
+
+@torch.library.custom_op("specdec::tree_attention_ragged", mutates_args=())
+def tree_attention_ragged(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_bits: Tensor, win_base: Tensor,
+                          kv_len: Tensor, scale: Optional[float] = None, kv_cap: Optional[int] = None,
+                          chunk_tiles: int = 0, kv_len_add: int = 0, win_base_add: int = 0) -> Tensor:
+    """ops.tree_attention with per-sequence device lengths and window bases (int64 [B]), out [B, R, Hq, D]."""
+    return ops.tree_attention(q, k, v, kv_limit, win_bits, win_base, scale=scale, kv_len=kv_len, kv_cap=kv_cap,
+                              chunk_tiles=chunk_tiles, kv_len_add=kv_len_add, win_base_add=win_base_add)
+
+
+@tree_attention_ragged.register_fake
+def _(q, k, v, kv_limit, win_bits, win_base, kv_len, scale=None, kv_cap=None, chunk_tiles=0, kv_len_add=0,
+      win_base_add=0):
     B, Hq, R, D = q.shape
     return q.new_empty(B, R, Hq, D)

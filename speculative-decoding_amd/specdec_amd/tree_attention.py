@@ -6,6 +6,8 @@ A forward run under ``descriptors(model, ...)`` takes every layer's attention th
 per-row ``(kv_limit, win_bits)`` on the device and the host integer ``win_base``, all query heads of a
 GQA group read one K/V stream, and transformers builds no mask at all.  Outside ``descriptors`` the name
 behaves as the stock ``"sdpa"`` attention with the stock mask, so switching a model to it is harmless.
+``descriptors_ragged`` is the same for a batch of sequences of different lengths: per-sequence device
+tensors for the window base and the valid length, read by sd_tree_attention_ragged when it runs.
 
     dsc = row_descriptors(tree, cur, start, nodes, col_of)          # host lists, no [R, width] tensor
     if supported(model, len(dsc.kv_limit)):
@@ -40,10 +42,11 @@ class RowDescriptors:
 
 @dataclass
 class _Active:
-    kv_limit: torch.Tensor      # int32 [1, R] on the device
+    kv_limit: torch.Tensor      # int32 [1, R] on the device ([B, R] under descriptors_ragged)
     win_bits: torch.Tensor      # int64 [1, R]
-    win_base: int
-    kv_len: int
+    win_base: object            # int; int64 [B] on the device under descriptors_ragged
+    kv_len: object
+    kv_cap: Optional[int] = None   # descriptors_ragged: the host's bound on every length
 
 
 _active: Optional[_Active] = None
@@ -94,6 +97,27 @@ def descriptors(model, dsc: RowDescriptors, kv_len: int, device):
         _active = outer
 
 
+@contextmanager
+def descriptors_ragged(model, kv_limit: torch.Tensor, win_bits: torch.Tensor, win_base: torch.Tensor, kv_len: torch.Tensor,
+                       kv_cap: int):
+    """``descriptors`` for a ragged batch, with everything on the device: kv_limit int32 [B, R], win_bits
+    int64 [B, R], win_base and kv_len int64 [B] (sequence b's window base and valid length, the R new rows
+    counted), kv_cap the host's bound on every length.  Every attention call inside runs
+    sd_tree_attention_ragged, which reads them when its kernels run: the tensors may be overwritten in
+    place between the replays of a captured forward."""
+    global _active
+    if not register():
+        raise RuntimeError("specdec_amd.tree_attention needs a transformers with AttentionInterface")
+    cfg, before, outer = model.config, model.config._attn_implementation, _active
+    _active = _Active(kv_limit, win_bits, win_base, kv_len, int(kv_cap))
+    cfg._attn_implementation = NAME
+    try:
+        yield
+    finally:
+        cfg._attn_implementation = before
+        _active = outer
+
+
 def _attention(module, query, key, value, attention_mask, scaling=None, dropout=0.0, **kwargs):
     """The ``AttentionInterface`` entry.  With descriptors: the kernel, out [B, R, Hq, D].  Without: the
     stock sdpa attention with the mask it was given."""
@@ -103,7 +127,11 @@ def _attention(module, query, key, value, attention_mask, scaling=None, dropout=
         counts["stock"] += 1
         return ALL_ATTENTION_FUNCTIONS["sdpa"](module, query, key, value, attention_mask, scaling=scaling,
                                                dropout=dropout, **kwargs)
-    out = ops.tree_attention(query, key, value, d.kv_limit, d.win_bits, d.win_base, scale=scaling, kv_len=d.kv_len)
+    if d.kv_cap is not None:
+        out = torch.ops.specdec.tree_attention_ragged(query, key, value, d.kv_limit, d.win_bits, d.win_base, d.kv_len,
+                                                      scaling, min(d.kv_cap, key.shape[2]))
+    else:
+        out = ops.tree_attention(query, key, value, d.kv_limit, d.win_bits, d.win_base, scale=scaling, kv_len=d.kv_len)
     counts["kernel"] += 1
     return out, None
 
