@@ -1506,6 +1506,113 @@ size_t sd_tree_attention_ragged_workspace_size(int32_t batch, int32_t heads_q, i
                                                int32_t head_dim, int32_t kv_cap, int32_t chunk_tiles);
 int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args* args, void* stream);
 
+/* ---- Tree attention over an FP8 KV cache (csrc/tree_attention.hip, csrc/tattn_fp8_tile.inc; additive, ABI 12)
+ * sd_tree_attention and sd_tree_attention_ragged with K and V stored as OCP e4m3 bytes (torch.float8_e4m3fn)
+ * and one fp32 dequantisation scale per K/V head and tensor, in device memory, read when the kernels run:
+ *
+ *     k[b, kvh, j, :] stands for k_scale[kvh] * e4m3(k bytes),   v[b, kvh, j, :] for v_scale[kvh] * e4m3(v bytes)
+ *
+ * and everything else — visibility, positions that are never loaded (an e4m3 NaN byte behind the mask never
+ * reaches `out`), zeros for a row that sees nothing, GQA sharing, the split and chunk rules, determinism,
+ * capturability — is as stated above.  `dtype` names the type of q and out (SD_BF16 / SD_F16).  The bytes are
+ * converted EXACTLY to that type for the matrix products (every finite e4m3 value is a bf16 and an fp16
+ * value); k_scale multiplies the fp32 score and v_scale the fp32 result, so the rounding is that of the
+ * 16-bit entries on the dequantised values.  k / v strides are in elements (= bytes) and, like the pointers,
+ * multiples of 16.  A scale that is not finite and positive is the caller's error (undefined result, no
+ * fault).  The splits, chunks and workspace sizes are those of the 16-bit entries for the same shape
+ * (sd_tree_attention_splits / _workspace_size, sd_tree_attention_ragged_chunks / _workspace_size).  Statuses
+ * as the 16-bit entries; a null or misaligned scale pointer: SD_ERR_INVALID.                              */
+typedef struct {
+    int32_t batch, heads_q, heads_kv, rows, head_dim;
+    int32_t dtype;               /* SD_BF16 or SD_F16, of q and out                                  */
+    int32_t kv_len, kv_alloc, splits;
+    float scale;
+    const void* q;
+    int64_t q_stride_b, q_stride_h, q_stride_r;
+    const void* k;               /* e4m3 bytes [B, Hkv, kv_alloc, D]                                  */
+    const void* v;
+    int64_t k_stride_b, k_stride_h, k_stride_pos;
+    int64_t v_stride_b, v_stride_h, v_stride_pos;
+    void* out;
+    int64_t out_stride_b, out_stride_r, out_stride_h;
+    const int32_t* kv_limit;
+    const uint64_t* win_bits;
+    int64_t win_base;
+    void* workspace;
+    size_t workspace_bytes;
+    const float* k_scale;        /* device fp32 [Hkv]                                                */
+    const float* v_scale;        /* device fp32 [Hkv]                                                */
+} sd_tree_attention_fp8_args;
+
+int32_t sd_tree_attention_fp8(const sd_tree_attention_fp8_args* args, void* stream);
+
+typedef struct {
+    int32_t batch, heads_q, heads_kv, rows, head_dim;
+    int32_t dtype;               /* SD_BF16 or SD_F16, of q and out                                  */
+    int32_t kv_cap, kv_alloc, chunk_tiles;
+    float scale;
+    const void* q;
+    int64_t q_stride_b, q_stride_h, q_stride_r;
+    const void* k;               /* e4m3 bytes [B, Hkv, kv_alloc, D]                                  */
+    const void* v;
+    int64_t k_stride_b, k_stride_h, k_stride_pos;
+    int64_t v_stride_b, v_stride_h, v_stride_pos;
+    void* out;
+    int64_t out_stride_b, out_stride_r, out_stride_h;
+    const int32_t* kv_limit;
+    const uint64_t* win_bits;
+    const int64_t* kv_len_dev;
+    int64_t kv_len_add;
+    const int64_t* win_base_dev;
+    int64_t win_base_add;
+    int32_t* status_or;
+    void* workspace;
+    size_t workspace_bytes;
+    const float* k_scale;        /* device fp32 [Hkv]                                                */
+    const float* v_scale;        /* device fp32 [Hkv]                                                */
+} sd_tree_attention_ragged_fp8_args;
+
+int32_t sd_tree_attention_ragged_fp8(const sd_tree_attention_ragged_fp8_args* args, void* stream);
+
+/* ---- Quantising K/V store into an FP8 cache (csrc/kv_store_fp8.hip; additive, ABI 12) --------------------
+ * The new K and V rows of one layer, [B, H, R, D] in bf16 / fp16, written into the e4m3 caches [B, H, L, D]
+ * the entries above read, in ONE launch for both tensors.  Row r of sequence b lands at position
+ *
+ *     p = pos + (pos_dev ? pos_dev[pos_per_seq ? b : 0] : 0) + r
+ *
+ * and a row with p outside [0, L) is not written and ORs SD_ROW_INVALID_DIST into status_or.  Every element is
+ * y = clamp(fp32(x) / scale[h], -448, 448) with a correctly rounded fp32 division, converted to e4m3 with
+ * round-to-nearest-even; NaN stays NaN (0x7f / 0xff), +-inf and overflow saturate to +-448, -0 stays -0: the
+ * bytes of torch's (x.float() / scale).clamp(-448, 448).to(torch.float8_e4m3fn).  The scales are read when
+ * the kernel runs.  Source strides are in elements and multiples of 8, cache strides in bytes and multiples
+ * of 16, pointers 16-byte aligned, the head dimension has unit stride and is a multiple of 16 (16..1024);
+ * else SD_ERR_INVALID (SD_ERR_UNSUPPORTED for a head dimension or dtype outside the limits).  No workspace,
+ * nothing read back: capturable.                                                                        */
+typedef struct {
+    int32_t batch;               /* B                                                              */
+    int32_t heads;               /* H (K/V heads)                                                  */
+    int32_t rows;                /* R new positions per sequence                                    */
+    int32_t head_dim;            /* D: a multiple of 16, 16..1024                                   */
+    int32_t dtype;               /* SD_BF16 or SD_F16, of k_new / v_new                             */
+    int32_t pos_per_seq;         /* nonzero: pos_dev holds B elements, else one                     */
+    const void* k_new;           /* [B, H, R, D] at k_new + b*stride_b + h*stride_h + r*stride_r     */
+    const void* v_new;
+    int64_t kn_stride_b, kn_stride_h, kn_stride_r;
+    int64_t vn_stride_b, vn_stride_h, vn_stride_r;
+    void* k_cache;               /* e4m3 bytes [B, H, L, D], strides of batch, head and position     */
+    void* v_cache;
+    int64_t kc_stride_b, kc_stride_h, kc_stride_pos;
+    int64_t vc_stride_b, vc_stride_h, vc_stride_pos;
+    int64_t num_positions;       /* L                                                              */
+    int64_t pos;                 /* host part of the first position                                 */
+    const int64_t* pos_dev;      /* nullable device int64 [1] or [B], added when the kernel runs      */
+    const float* k_scale;        /* device fp32 [H]                                                 */
+    const float* v_scale;
+    int32_t* status_or;          /* nullable device int32 [1]                                       */
+} sd_kv_store_fp8_args;
+
+int32_t sd_kv_store_fp8(const sd_kv_store_fp8_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

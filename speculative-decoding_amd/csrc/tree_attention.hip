@@ -42,6 +42,13 @@
 //       slot beyond them was not written in this call.  A sequence's result depends on its own inputs,
 //       kv_cap and the chunk length only.
 //
+// FP8 caches (sd_tree_attention_fp8, sd_tree_attention_ragged_fp8): K/V as OCP e4m3 bytes with one fp32
+// dequantisation scale per K/V head and tensor, q / out in the 16-bit type.
+//   k_tattn_fp8_partial<dtype, D>, k_tattn_fp8_ragged_partial<dtype, D>   the grids and the wave ownership of the
+//       16-bit partials over a tile body of their own (csrc/tattn_fp8_tile.inc): bytes in the prefetch registers
+//       and in LDS, converted exactly to the 16-bit type when a wave forms an MFMA operand; the scales stay in
+//       fp32 outside the products.  The partials are the same fp32 records, so both combines serve as they are.
+//
 // Launch boundaries are the only synchronisation.  The workspace's common counter block is skipped.
 #include "sd_device.h"
 #include "sd_host.h"
@@ -54,6 +61,7 @@ constexpr int kTaRowTile = 32;         // query rows per wave (the MFMA's N)
 constexpr int kTaTilesPerSplit = 4;    // a split is worth its fp32 partials from about this many tiles on
 constexpr int kTaFill = 256;           // workgroups the auto split count aims at (the CUs of an MI355X)
 constexpr int kTaVtWords = 33;         // dwords per V^T row: 32 key pairs + 1 (odd: rows start in different banks)
+constexpr int kTaVt8Words = 18;        // dwords per V^T row of e4m3 bytes: 16 key quads + 2 (tattn_fp8_tile.inc)
 
 typedef uint32_t ta_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t ta_u32x2 __attribute__((ext_vector_type(2)));
@@ -91,6 +99,48 @@ __device__ __forceinline__ float ta_exp2(float x) {   // v_exp_f32: 2^-inf = 0, 
     return exp2f(x);
 #endif
 }
+
+// v_perm_b32: byte i of the result is byte sel_i of the eight bytes hi:lo (0..3 lo, 4..7 hi)
+__device__ __forceinline__ uint32_t ta_perm(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t both = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int i = 0; i < 4; ++i) r |= (uint32_t)((both >> (8 * ((sel >> (8 * i)) & 7))) & 0xffu) << (8 * i);
+    return r;
+#endif
+}
+
+// Eight e4m3 bytes (w0: elements 0..3, w1: 4..7) as an MFMA operand of the 16-bit type.  The conversion is
+// exact (scale operand 1.0): e4m3 has 3 mantissa bits and exponents -9..8, inside bf16 and fp16 alike.
+template <int DT> struct TaFp8Cvt;
+template <> struct TaFp8Cvt<SD_BF16> {
+    template <bool HI> static __device__ __forceinline__ uint32_t pair(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+#else
+        return w;
+#endif
+    }
+    static __device__ __forceinline__ TaType<SD_BF16>::vec8 vec8(uint32_t w0, uint32_t w1) {
+        const ta_u32x4 x = {pair<false>(w0), pair<true>(w0), pair<false>(w1), pair<true>(w1)};
+        return __builtin_bit_cast(TaType<SD_BF16>::vec8, x);
+    }
+};
+template <> struct TaFp8Cvt<SD_F16> {
+    template <bool HI> static __device__ __forceinline__ uint32_t pair(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
+#else
+        return w;
+#endif
+    }
+    static __device__ __forceinline__ TaType<SD_F16>::vec8 vec8(uint32_t w0, uint32_t w1) {
+        const ta_u32x4 x = {pair<false>(w0), pair<true>(w0), pair<false>(w1), pair<true>(w1)};
+        return __builtin_bit_cast(TaType<SD_F16>::vec8, x);
+    }
+};
 
 // bits j of [a, b) that lie in [0, 64)
 __host__ __device__ __forceinline__ uint64_t ta_range_mask(int64_t a, int64_t b) {
@@ -170,6 +220,49 @@ __global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_partial(TaParams P,
 #define TA_T_BEGIN split * Rg.chunk_tiles
 #define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
 #include "tattn_tile.inc"
+#undef TA_KV_LEN
+#undef TA_WIN_BASE
+#undef TA_T_BEGIN
+#undef TA_T_END
+    }
+}
+
+// What the FP8 entries add to TaParams (whose k / v then point at e4m3 bytes, strides in bytes): one fp32
+// dequantisation scale per K/V head for K and for V, read when the kernels run.
+struct TaFp8 {
+    const float* k_scale;   // [Hkv]
+    const float* v_scale;   // [Hkv]
+};
+
+// k_tattn_partial over an e4m3 cache
+template <int DT, int D>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_partial(TaParams P, TaFp8 Fs) {
+#define TA_KV_LEN P.kv_len
+#define TA_WIN_BASE P.win_base
+#define TA_T_BEGIN (int)((int64_t)split * n_tiles / P.splits)
+#define TA_T_END (int)((int64_t)(split + 1) * n_tiles / P.splits)
+#include "tattn_fp8_tile.inc"
+#undef TA_KV_LEN
+#undef TA_WIN_BASE
+#undef TA_T_BEGIN
+#undef TA_T_END
+}
+
+// k_tattn_ragged_partial over an e4m3 cache: the same early exits, so k_tattn_ragged_combine reads what it reads
+template <int DT, int D>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_ragged_partial(TaParams P, TaRagged Rg, TaFp8 Fs) {
+    const int c = blockIdx.x, b = blockIdx.z;
+    bool bad;
+    const int32_t len = ta_ragged_len(Rg, b, &bad);
+    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
+    if ((int64_t)c * Rg.chunk_tiles * kTaTile >= len && P.part_ml != nullptr) return;
+    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
+    {
+#define TA_KV_LEN len
+#define TA_WIN_BASE rg_win_base
+#define TA_T_BEGIN split * Rg.chunk_tiles
+#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+#include "tattn_fp8_tile.inc"
 #undef TA_KV_LEN
 #undef TA_WIN_BASE
 #undef TA_T_BEGIN
@@ -358,6 +451,18 @@ static int32_t ta_check_tensors(const A* a) {
     return SD_OK;
 }
 
+// what the FP8 argument structs add to ta_check_tensors: k / v are bytes, so their strides (in elements) must
+// themselves be multiples of 16, and the scales must be given
+template <typename A>
+static int32_t ta_check_fp8(const A* a) {
+    if (!a->k_scale || !a->v_scale) return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a->k_scale) | reinterpret_cast<uintptr_t>(a->v_scale)) & 3) return SD_ERR_INVALID;
+    const int64_t strides[] = {a->k_stride_b, a->k_stride_h, a->k_stride_pos, a->v_stride_b, a->v_stride_h, a->v_stride_pos};
+    for (int64_t s : strides)
+        if (s & 15) return SD_ERR_INVALID;
+    return SD_OK;
+}
+
 // the fields both argument structs share, into the kernels' parameters
 template <typename A>
 static TaParams ta_params(const A* a, const TaWorkspace& w, int splits) {
@@ -389,7 +494,10 @@ extern "C" size_t sd_tree_attention_workspace_size(int32_t batch, int32_t heads_
     return sd::ta_carve(nullptr, batch, heads_q, rows, head_dim, sd::ta_splits(batch, heads_kv, kv_len, splits)).bytes;
 }
 
-extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stream) {
+// sd_tree_attention (fs null) and sd_tree_attention_fp8 (fs: the scales), whose argument structs share every
+// other field
+template <typename A>
+static int32_t ta_call(const A* a, void* stream, const sd::TaFp8* fs) {
     using namespace sd_host;
     if (!a) return SD_ERR_INVALID;
     if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
@@ -412,6 +520,9 @@ extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stre
     const dim3 grid((unsigned)splits, (unsigned)a->heads_kv, (unsigned)a->batch);
     int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
         return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
+            if (fs)
+                return launch(sd::k_tattn_fp8_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
+                              0, stream, P, *fs);
             return launch(sd::k_tattn_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads), 0,
                           stream, P);
         });
@@ -422,6 +533,18 @@ extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stre
     return dispatch_dtype16(a->dtype, [&](auto dt) {
         return launch(sd::k_tattn_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, total);
     });
+}
+
+extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stream) {
+    return ta_call(a, stream, nullptr);
+}
+
+extern "C" int32_t sd_tree_attention_fp8(const sd_tree_attention_fp8_args* a, void* stream) {
+    if (!a) return SD_ERR_INVALID;
+    const int32_t st = sd::ta_check_fp8(a);
+    if (st != SD_OK) return st;
+    const sd::TaFp8 fs{a->k_scale, a->v_scale};
+    return ta_call(a, stream, &fs);
 }
 
 // ---- ragged batches: per-sequence lengths and window bases read on the device ---------------------------
@@ -437,7 +560,9 @@ extern "C" size_t sd_tree_attention_ragged_workspace_size(int32_t batch, int32_t
     return chunks ? sd::ta_carve(nullptr, batch, heads_q, rows, head_dim, chunks).bytes : 0;
 }
 
-extern "C" int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args* a, void* stream) {
+// sd_tree_attention_ragged (fs null) and sd_tree_attention_ragged_fp8 (fs: the scales)
+template <typename A>
+static int32_t ta_ragged_call(const A* a, void* stream, const sd::TaFp8* fs) {
     using namespace sd_host;
     if (!a) return SD_ERR_INVALID;
     if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
@@ -469,6 +594,9 @@ extern "C" int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args*
     const dim3 grid((unsigned)chunks, (unsigned)a->heads_kv, (unsigned)a->batch);
     int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
         return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
+            if (fs)
+                return launch(sd::k_tattn_fp8_ragged_partial<decltype(dt)::value, decltype(d)::value>, grid,
+                              dim3(sd::kTaThreads), 0, stream, P, Rg, *fs);
             return launch(sd::k_tattn_ragged_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
                           0, stream, P, Rg);
         });
@@ -479,4 +607,16 @@ extern "C" int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args*
     return dispatch_dtype16(a->dtype, [&](auto dt) {
         return launch(sd::k_tattn_ragged_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, Rg, total);
     });
+}
+
+extern "C" int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args* a, void* stream) {
+    return ta_ragged_call(a, stream, nullptr);
+}
+
+extern "C" int32_t sd_tree_attention_ragged_fp8(const sd_tree_attention_ragged_fp8_args* a, void* stream) {
+    if (!a) return SD_ERR_INVALID;
+    const int32_t st = sd::ta_check_fp8(a);
+    if (st != SD_OK) return st;
+    const sd::TaFp8 fs{a->k_scale, a->v_scale};
+    return ta_ragged_call(a, stream, &fs);
 }

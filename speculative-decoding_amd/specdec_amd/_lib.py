@@ -91,7 +91,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_sample_distinct_workspace_size", "sd_sample_distinct",
            "sd_verify_tree_swor_workspace_size", "sd_verify_tree_swor",
            "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention",
-           "sd_tree_attention_ragged_chunks", "sd_tree_attention_ragged_workspace_size", "sd_tree_attention_ragged")
+           "sd_tree_attention_ragged_chunks", "sd_tree_attention_ragged_workspace_size", "sd_tree_attention_ragged",
+           "sd_tree_attention_fp8", "sd_tree_attention_ragged_fp8", "sd_kv_store_fp8")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -418,6 +419,30 @@ class sd_tree_attention_ragged_args(C.Structure):
     ]
 
 
+# the FP8-cache entries: the 16-bit structs plus the two dequantisation scales (device fp32 [Hkv])
+class sd_tree_attention_fp8_args(C.Structure):
+    _fields_ = sd_tree_attention_args._fields_ + [("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+
+
+class sd_tree_attention_ragged_fp8_args(C.Structure):
+    _fields_ = sd_tree_attention_ragged_args._fields_ + [("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+
+
+class sd_kv_store_fp8_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("heads", C.c_int32), ("rows", C.c_int32), ("head_dim", C.c_int32),
+        ("dtype", C.c_int32), ("pos_per_seq", C.c_int32),
+        ("k_new", C.c_void_p), ("v_new", C.c_void_p),
+        ("kn_stride_b", C.c_int64), ("kn_stride_h", C.c_int64), ("kn_stride_r", C.c_int64),
+        ("vn_stride_b", C.c_int64), ("vn_stride_h", C.c_int64), ("vn_stride_r", C.c_int64),
+        ("k_cache", C.c_void_p), ("v_cache", C.c_void_p),
+        ("kc_stride_b", C.c_int64), ("kc_stride_h", C.c_int64), ("kc_stride_pos", C.c_int64),
+        ("vc_stride_b", C.c_int64), ("vc_stride_h", C.c_int64), ("vc_stride_pos", C.c_int64),
+        ("num_positions", C.c_int64), ("pos", C.c_int64), ("pos_dev", C.c_void_p),
+        ("k_scale", C.c_void_p), ("v_scale", C.c_void_p), ("status_or", C.c_void_p),
+    ]
+
+
 class sd_vp_header(C.Structure):
     _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
                 ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
@@ -545,6 +570,12 @@ def _load():
     lib.sd_tree_attention_ragged_workspace_size.argtypes = [C.c_int32] * 7
     lib.sd_tree_attention_ragged.restype = C.c_int32
     lib.sd_tree_attention_ragged.argtypes = [C.POINTER(sd_tree_attention_ragged_args), C.c_void_p]
+    lib.sd_tree_attention_fp8.restype = C.c_int32
+    lib.sd_tree_attention_fp8.argtypes = [C.POINTER(sd_tree_attention_fp8_args), C.c_void_p]
+    lib.sd_tree_attention_ragged_fp8.restype = C.c_int32
+    lib.sd_tree_attention_ragged_fp8.argtypes = [C.POINTER(sd_tree_attention_ragged_fp8_args), C.c_void_p]
+    lib.sd_kv_store_fp8.restype = C.c_int32
+    lib.sd_kv_store_fp8.argtypes = [C.POINTER(sd_kv_store_fp8_args), C.c_void_p]
     lib.sd_tree_grow_workspace_size.restype = C.c_size_t
     lib.sd_tree_grow_workspace_size.argtypes = [C.c_int32] * 5
     lib.sd_tree_grow.restype = C.c_int32

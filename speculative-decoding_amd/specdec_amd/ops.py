@@ -1288,8 +1288,9 @@ def _ta_workspace(a, workspace, need, dev):
 
 
 def _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles, kv_len_add,
-                           win_base_add, status_or, workspace):
-    """tree_attention with a device tensor for kv_len and / or win_base (sd_tree_attention_ragged)."""
+                           win_base_add, status_or, workspace, scales=None):
+    """tree_attention with a device tensor for kv_len and / or win_base (sd_tree_attention_ragged; with
+    `scales`, the (k_scale, v_scale) of an FP8 cache, sd_tree_attention_ragged_fp8)."""
     B, Hq, R, D = q.shape
     Hkv, L, dev = k.shape[1], k.shape[2], q.device
     kv_cap = L if kv_cap is None else int(kv_cap)
@@ -1302,7 +1303,11 @@ def _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, s
         elif x.dtype != torch.int64 or x.shape != (B,) or x.device != dev or not x.is_contiguous():
             raise ValueError(f"tree_attention: a {name} tensor must be a contiguous int64 [{B}] on {dev}")
         per_seq.append(x)
-    a = _lib.sd_tree_attention_ragged_args()
+    a = _lib.sd_tree_attention_ragged_args() if scales is None else _lib.sd_tree_attention_ragged_fp8_args()
+    call, name = (lib.sd_tree_attention_ragged, "sd_tree_attention_ragged") if scales is None else \
+        (lib.sd_tree_attention_ragged_fp8, "sd_tree_attention_ragged_fp8")
+    if scales is not None:
+        a.k_scale, a.v_scale = scales[0].data_ptr(), scales[1].data_ptr()
     a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
     a.kv_cap, a.kv_alloc, a.chunk_tiles = kv_cap, L, int(chunk_tiles)
     a.scale = float(D) ** -0.5 if scale is None else float(scale)
@@ -1313,7 +1318,7 @@ def _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, s
     need = lib.sd_tree_attention_ragged_workspace_size(B, Hq, Hkv, R, D, kv_cap, int(chunk_tiles))
     one = tree_attention_chunks(B, Hkv, kv_cap, chunk_tiles) <= 1
     keep = _ta_workspace(a, workspace, 0 if one else need, dev)
-    _lib.check(lib.sd_tree_attention_ragged(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention_ragged")
+    _lib.check(call(C.byref(a), C.c_void_p(_stream_ptr(dev))), name)
     del keep, per_seq
     return out
 
@@ -1323,7 +1328,8 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
                    out: Optional[torch.Tensor] = None, splits: int = 0, *,
                    workspace: Optional[torch.Tensor] = None, kv_cap: Optional[int] = None, chunk_tiles: int = 0,
                    kv_len_add: int = 0, win_base_add: int = 0,
-                   status_or: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   status_or: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                   v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The attention of a cached tree forward without a mask tensor (sd_tree_attention, MFMA kernels).
 
     q: [B, Hq, R, D]; k, v: [B, Hkv, L, D] (a cache layer's tensors; the first ``kv_len`` positions are
@@ -1344,7 +1350,13 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     ``win_base[b] + win_base_add``.  kv_cap (default L): the host's bound on every length; nothing at or
     beyond it is read.  chunk_tiles: 0 lets (B, Hkv, kv_cap) decide the fixed chunk length, another value
     pins its 64-key tiles (tests); ``splits`` is not used.  status_or: int32 [1], gets SD_ROW_INVALID_DIST
-    when a length had to be clamped.  A sequence's output does not depend on the batch's other sequences."""
+    when a length had to be clamped.  A sequence's output does not depend on the batch's other sequences.
+
+    FP8 caches: k and v may be ``torch.float8_e4m3fn`` (q bf16 or fp16) with ``k_scale`` and ``v_scale``, contiguous
+    fp32 [Hkv] device tensors: key j of K/V head h then stands for ``k_scale[h] * k[b, h, j].float()``, likewise V
+    (sd_tree_attention_fp8 / sd_tree_attention_ragged_fp8).  The scales are read when the kernels run; the bytes
+    are converted exactly and the scales applied in fp32, so the result is that of the 16-bit path on the
+    dequantised values.  k / v strides must then be multiples of 16.  ``kv_store_fp8`` writes such a cache."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("tree_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D]")
     B, Hq, R, D = q.shape
@@ -1354,8 +1366,18 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     dev = q.device
     if not q.is_cuda or k.device != dev or v.device != dev:
         raise ValueError("tree_attention: q, k and v must be tensors of one device")
-    if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError("tree_attention: q, k and v must share one floating dtype")
+    scales = None
+    if k.dtype == torch.float8_e4m3fn and v.dtype == torch.float8_e4m3fn and q.dtype in _DT:
+        if k_scale is None or v_scale is None:
+            raise ValueError("tree_attention: float8_e4m3fn k / v need k_scale and v_scale")
+        for x in (k_scale, v_scale):
+            if x.dtype != torch.float32 or x.shape != (Hkv,) or x.device != dev or not x.is_contiguous():
+                raise ValueError(f"tree_attention: k_scale and v_scale must be contiguous float32 [{Hkv}] on {dev}")
+        scales = (k_scale, v_scale)
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError("tree_attention: k_scale and v_scale go with float8_e4m3fn k and v")
+    elif q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("tree_attention: q, k and v must share one floating dtype (or k, v float8_e4m3fn with scales)")
     if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
         raise ValueError("tree_attention: the head dimension must have unit stride")
     ragged = torch.is_tensor(kv_len) or torch.is_tensor(win_base)
@@ -1377,8 +1399,10 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
         raise ValueError(f"tree_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
     if ragged:
         return _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles,
-                                      kv_len_add, win_base_add, status_or, workspace)
-    a = _lib.sd_tree_attention_args()
+                                      kv_len_add, win_base_add, status_or, workspace, scales)
+    a = _lib.sd_tree_attention_args() if scales is None else _lib.sd_tree_attention_fp8_args()
+    if scales is not None:
+        a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
     a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
     a.kv_len, a.kv_alloc, a.splits = kv_len, L, int(splits)
     a.scale = float(D) ** -0.5 if scale is None else float(scale)
@@ -1386,8 +1410,60 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     a.win_base = int(win_base)
     need = lib.sd_tree_attention_workspace_size(B, Hq, Hkv, R, D, kv_len, int(splits))
     workspace = _ta_workspace(a, workspace, need if tree_attention_splits(B, Hkv, kv_len, splits) > 1 else 0, dev)
-    _lib.check(lib.sd_tree_attention(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention")
+    if scales is None:
+        _lib.check(lib.sd_tree_attention(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention")
+    else:
+        _lib.check(lib.sd_tree_attention_fp8(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention_fp8")
     return out
+
+
+def kv_store_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                 k_scale: torch.Tensor, v_scale: torch.Tensor, pos: int, *, pos_dev: Optional[torch.Tensor] = None,
+                 status_or: Optional[torch.Tensor] = None) -> None:
+    """Quantise a layer's new K and V rows into its FP8 caches, one launch for both (sd_kv_store_fp8).
+
+    k_new, v_new: [B, H, R, D] bf16 or fp16, any strides with unit stride along D (a transposed view is taken as
+    it stands).  k_cache, v_cache: ``torch.float8_e4m3fn`` [B, H, L, D].  k_scale, v_scale: contiguous fp32 [H] on
+    the device, read when the kernel runs.  Row r of sequence b is written to position
+    ``pos + pos_dev[b or 0] + r`` (pos_dev: int64, one or B elements, on the device); a row that would land
+    outside [0, L) is not written and ORs SD_ROW_INVALID_DIST into ``status_or``.  The bytes are those of
+    ``(x.float() / scale[h]).clamp(-448, 448).to(torch.float8_e4m3fn)``."""
+    if k_new.dim() != 4 or k_new.shape != v_new.shape or k_new.dtype != v_new.dtype:
+        raise ValueError("kv_store_fp8: k_new and v_new must be [B, H, R, D] tensors of one shape and dtype")
+    B, H, R, D = k_new.shape
+    dev = k_new.device
+    if not k_new.is_cuda or k_new.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("kv_store_fp8: k_new and v_new must be bf16 or fp16 device tensors")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[:2] != (B, H) or k_cache.shape[3] != D:
+        raise ValueError(f"kv_store_fp8: the caches must be [{B}, {H}, L, {D}], got {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    for c in (k_cache, v_cache):
+        if c.dtype != torch.float8_e4m3fn or c.device != dev:
+            raise ValueError(f"kv_store_fp8: the caches must be float8_e4m3fn on {dev}")
+    for t in (k_new, v_new, k_cache, v_cache):
+        if t.stride(3) != 1:
+            raise ValueError("kv_store_fp8: the head dimension must have unit stride")
+    for x in (k_scale, v_scale):
+        if x.dtype != torch.float32 or x.shape != (H,) or x.device != dev or not x.is_contiguous():
+            raise ValueError(f"kv_store_fp8: k_scale and v_scale must be contiguous float32 [{H}] on {dev}")
+    if pos_dev is not None and (pos_dev.dtype != torch.int64 or pos_dev.numel() not in (1, B) or pos_dev.device != dev
+                                or not pos_dev.is_contiguous()):
+        raise ValueError("kv_store_fp8: pos_dev must be a contiguous int64 tensor of one or B elements on the device")
+    a = _lib.sd_kv_store_fp8_args()
+    a.batch, a.heads, a.rows, a.head_dim, a.dtype = B, H, R, D, _DT[k_new.dtype]
+    a.k_new, a.v_new, a.k_cache, a.v_cache = k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+    # a dimension of size 1 may carry any stride: it is never stepped along
+    a.kn_stride_b, a.kn_stride_h, a.kn_stride_r = (k_new.stride(i) if k_new.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.vn_stride_b, a.vn_stride_h, a.vn_stride_r = (v_new.stride(i) if v_new.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.kn_stride_r, a.vn_stride_r = a.kn_stride_r or D, a.vn_stride_r or D
+    a.kc_stride_b, a.kc_stride_h, a.kc_stride_pos = (k_cache.stride(i) if k_cache.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.vc_stride_b, a.vc_stride_h, a.vc_stride_pos = (v_cache.stride(i) if v_cache.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.kc_stride_pos, a.vc_stride_pos = a.kc_stride_pos or D, a.vc_stride_pos or D
+    a.num_positions, a.pos = k_cache.shape[2], int(pos)
+    if pos_dev is not None:
+        a.pos_dev, a.pos_per_seq = pos_dev.data_ptr(), int(B > 1 and pos_dev.numel() == B)
+    a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_kv_store_fp8(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_kv_store_fp8")
 
 
 # --------------------------------------------------------------------------- n-gram verify (A11)

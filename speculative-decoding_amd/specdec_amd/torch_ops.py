@@ -88,6 +88,11 @@ GPU), and callable as ``torch.ops.specdec.*``.
         The attention of a cached tree forward without a mask tensor (sd_tree_attention): row r sees key j
         below kv_limit[b, r] or where bit j - win_base of win_bits[b, r] is set.
 
+    torch.ops.specdec.tree_attention_fp8(q, k, v float8_e4m3fn, kv_limit, win_bits, win_base, k_scale, v_scale fp32 [Hkv], ...)
+    torch.ops.specdec.tree_attention_ragged_fp8(q, k, v float8_e4m3fn, kv_limit, win_bits, win_base, kv_len, k_scale, v_scale, ...)
+        The two attentions below over an FP8 cache with per-head dequantisation scales (sd_tree_attention_fp8,
+        sd_tree_attention_ragged_fp8); torch.ops.specdec.kv_store_fp8(k_new, v_new, k_cache, v_cache, k_scale,
+        v_scale, pos, pos_dev?) quantises new rows into such a cache in place (sd_kv_store_fp8).
     torch.ops.specdec.tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base int64 [B], kv_len int64 [B], scale float?,
                                             kv_cap int?, chunk_tiles, kv_len_add, win_base_add) -> out [B, R, Hq, D]
         The same attention over a ragged batch (sd_tree_attention_ragged): sequence b's valid length
@@ -520,3 +525,48 @@ def _(q, k, v, kv_limit, win_bits, win_base, kv_len, scale=None, kv_cap=None, ch
       win_base_add=0):
     B, Hq, R, D = q.shape
     return q.new_empty(B, R, Hq, D)
+
+
+@torch.library.custom_op("specdec::tree_attention_fp8", mutates_args=())
+def tree_attention_fp8(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_bits: Tensor, win_base: int,
+                       k_scale: Tensor, v_scale: Tensor, scale: Optional[float] = None, kv_len: Optional[int] = None,
+                       splits: int = 0) -> Tensor:
+    """ops.tree_attention over a float8_e4m3fn cache with per-head fp32 scales [Hkv], out [B, R, Hq, D] in q's dtype."""
+    return ops.tree_attention(q, k, v, kv_limit, win_bits, win_base, scale=scale, kv_len=kv_len, splits=splits,
+                              k_scale=k_scale, v_scale=v_scale)
+
+
+@tree_attention_fp8.register_fake
+def _(q, k, v, kv_limit, win_bits, win_base, k_scale, v_scale, scale=None, kv_len=None, splits=0):
+    B, Hq, R, D = q.shape
+    return q.new_empty(B, R, Hq, D)
+
+
+@torch.library.custom_op("specdec::tree_attention_ragged_fp8", mutates_args=())
+def tree_attention_ragged_fp8(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_bits: Tensor, win_base: Tensor,
+                              kv_len: Tensor, k_scale: Tensor, v_scale: Tensor, scale: Optional[float] = None,
+                              kv_cap: Optional[int] = None, chunk_tiles: int = 0, kv_len_add: int = 0,
+                              win_base_add: int = 0) -> Tensor:
+    """tree_attention_ragged over a float8_e4m3fn cache with per-head fp32 scales [Hkv]."""
+    return ops.tree_attention(q, k, v, kv_limit, win_bits, win_base, scale=scale, kv_len=kv_len, kv_cap=kv_cap,
+                              chunk_tiles=chunk_tiles, kv_len_add=kv_len_add, win_base_add=win_base_add,
+                              k_scale=k_scale, v_scale=v_scale)
+
+
+@tree_attention_ragged_fp8.register_fake
+def _(q, k, v, kv_limit, win_bits, win_base, kv_len, k_scale, v_scale, scale=None, kv_cap=None, chunk_tiles=0,
+      kv_len_add=0, win_base_add=0):
+    B, Hq, R, D = q.shape
+    return q.new_empty(B, R, Hq, D)
+
+
+@torch.library.custom_op("specdec::kv_store_fp8", mutates_args=("k_cache", "v_cache"))
+def kv_store_fp8(k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, k_scale: Tensor, v_scale: Tensor,
+                 pos: int, pos_dev: Optional[Tensor] = None) -> None:
+    """ops.kv_store_fp8: the new K / V rows quantised into the float8_e4m3fn caches in place, from position pos."""
+    ops.kv_store_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos, pos_dev=pos_dev)
+
+
+@kv_store_fp8.register_fake
+def _(k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos, pos_dev=None):
+    return None

@@ -47,6 +47,8 @@ class _Active:
     win_base: object            # int; int64 [B] on the device under descriptors_ragged
     kv_len: object
     kv_cap: Optional[int] = None   # descriptors_ragged: the host's bound on every length
+    k_scale: Optional[torch.Tensor] = None   # fp32 [Hkv]: the dequantisation scales of an FP8 cache, used when
+    v_scale: Optional[torch.Tensor] = None   # the `key` an attention call receives is float8_e4m3fn
 
 
 _active: Optional[_Active] = None
@@ -79,16 +81,19 @@ def supported(model, rows: int) -> bool:
 
 
 @contextmanager
-def descriptors(model, dsc: RowDescriptors, kv_len: int, device):
+def descriptors(model, dsc: RowDescriptors, kv_len: int, device, k_scale=None, v_scale=None):
     """Run the forwards inside on the kernel: `model`'s attention implementation is "specdec_tree" for
-    the block and every attention call reads `dsc` (batch 1) over the first `kv_len` cache positions."""
+    the block and every attention call reads `dsc` (batch 1) over the first `kv_len` cache positions.
+    k_scale, v_scale (fp32 [Hkv] on the device): the scales of an FP8 cache; a call whose key is
+    float8_e4m3fn then runs sd_tree_attention_fp8."""
     global _active
     if not register():
         raise RuntimeError("specdec_amd.tree_attention needs a transformers with AttentionInterface")
     signed = [b - (1 << 64) if b >> 63 else b for b in dsc.win_bits]      # the words as int64
     cfg, before, outer = model.config, model.config._attn_implementation, _active
     _active = _Active(torch.tensor([dsc.kv_limit], dtype=torch.int32).to(device, non_blocking=True),
-                      torch.tensor([signed], dtype=torch.int64).to(device, non_blocking=True), int(dsc.win_base), int(kv_len))
+                      torch.tensor([signed], dtype=torch.int64).to(device, non_blocking=True), int(dsc.win_base), int(kv_len),
+                      k_scale=k_scale, v_scale=v_scale)
     cfg._attn_implementation = NAME
     try:
         yield
@@ -99,17 +104,17 @@ def descriptors(model, dsc: RowDescriptors, kv_len: int, device):
 
 @contextmanager
 def descriptors_ragged(model, kv_limit: torch.Tensor, win_bits: torch.Tensor, win_base: torch.Tensor, kv_len: torch.Tensor,
-                       kv_cap: int):
+                       kv_cap: int, k_scale=None, v_scale=None):
     """``descriptors`` for a ragged batch, with everything on the device: kv_limit int32 [B, R], win_bits
     int64 [B, R], win_base and kv_len int64 [B] (sequence b's window base and valid length, the R new rows
     counted), kv_cap the host's bound on every length.  Every attention call inside runs
     sd_tree_attention_ragged, which reads them when its kernels run: the tensors may be overwritten in
-    place between the replays of a captured forward."""
+    place between the replays of a captured forward.  k_scale, v_scale: as for ``descriptors``."""
     global _active
     if not register():
         raise RuntimeError("specdec_amd.tree_attention needs a transformers with AttentionInterface")
     cfg, before, outer = model.config, model.config._attn_implementation, _active
-    _active = _Active(kv_limit, win_bits, win_base, kv_len, int(kv_cap))
+    _active = _Active(kv_limit, win_bits, win_base, kv_len, int(kv_cap), k_scale, v_scale)
     cfg._attn_implementation = NAME
     try:
         yield
@@ -127,7 +132,17 @@ def _attention(module, query, key, value, attention_mask, scaling=None, dropout=
         counts["stock"] += 1
         return ALL_ATTENTION_FUNCTIONS["sdpa"](module, query, key, value, attention_mask, scaling=scaling,
                                                dropout=dropout, **kwargs)
-    if d.kv_cap is not None:
+    if key.dtype == torch.float8_e4m3fn:
+        if d.k_scale is None or d.v_scale is None:
+            raise RuntimeError("specdec_tree: an FP8 key needs descriptors with k_scale and v_scale")
+        if d.kv_cap is not None:
+            out = torch.ops.specdec.tree_attention_ragged_fp8(query, key, value, d.kv_limit, d.win_bits, d.win_base,
+                                                              d.kv_len, d.k_scale, d.v_scale, scaling,
+                                                              min(d.kv_cap, key.shape[2]))
+        else:
+            out = ops.tree_attention(query, key, value, d.kv_limit, d.win_bits, d.win_base, scale=scaling,
+                                     kv_len=d.kv_len, k_scale=d.k_scale, v_scale=d.v_scale)
+    elif d.kv_cap is not None:
         out = torch.ops.specdec.tree_attention_ragged(query, key, value, d.kv_limit, d.win_bits, d.win_base, d.kv_len,
                                                       scaling, min(d.kv_cap, key.shape[2]))
     else:
