@@ -1613,6 +1613,120 @@ typedef struct {
 
 int32_t sd_kv_store_fp8(const sd_kv_store_fp8_args* args, void* stream);
 
+/* ---- Paged KV caches: attention, store and compaction through a block table (additive, ABI 12) -----------
+ * K and V live in fixed-size pages of a shared pool, [num_pages, Hkv, S, D] addressed by three strides (page,
+ * head, slot; so a [P, S, Hkv, D] pool is served as well), and every sequence has a row of a device int32
+ * block table [B, max_pages]:
+ *
+ *     position j of sequence b  =  pool + block_table[b*block_table_stride_b + (j >> log2 S)] * stride_page
+ *                                       + head * stride_h + (j & (S - 1)) * stride_pos
+ *
+ * S = page_size is 16, 32, 64, 128 or 256.  The table is device data the host cannot check, so all three
+ * entries keep one rule: an entry is read only when a position that is in use needs it (attention: index
+ * below ceil(len_b / S); trailing entries may hold anything), and a page id outside [0, num_pages) is never
+ * turned into an address — what needed it is skipped and SD_ROW_INVALID_DIST is ORed into status_or.  Nothing
+ * outside pool[id] for a valid id is read or written.
+ *
+ * sd_tree_attention_paged (csrc/tree_attention.hip: k_tattn_paged_partial, k_tattn_fp8_paged_partial) is
+ * sd_tree_attention_ragged / _ragged_fp8 over such a pool: len_b, win_base_b, visibility, zeros for an empty
+ * row or sequence, the status bit for a clamped length, the chunk rule (chunk_tiles, sd_tree_attention_ragged_
+ * chunks), the workspace (sd_tree_attention_ragged_workspace_size), the combine kernel, determinism and
+ * capturability are the ragged entry's.  kv_cap <= min(max_pages * S, SD_TREE_ATTN_MAX_KV).  kv_fp8 nonzero:
+ * k / v are e4m3 bytes, k_scale / v_scale (device fp32 [Hkv]) are required and the k / v strides are multiples
+ * of 16; zero: k / v have `dtype`, strides multiples of 8 elements.  The keys of a page whose id is refused
+ * enter the products as zeros: that sequence's output is finite and meaningless, the others are untouched.
+ * The attention writes nothing to the pools.                                                             */
+typedef struct {
+    int32_t batch, heads_q, heads_kv, rows, head_dim;
+    int32_t dtype;               /* SD_BF16 or SD_F16, of q and out (and of k / v unless kv_fp8)      */
+    int32_t kv_cap;              /* upper bound of every len_b, 1..min(max_pages * S, MAX_KV)         */
+    int32_t chunk_tiles;         /* as sd_tree_attention_ragged_args                                 */
+    int32_t page_size;           /* S: 16, 32, 64, 128 or 256 positions                              */
+    int32_t num_pages;           /* pages of the pools: valid ids are 0..num_pages - 1               */
+    int32_t max_pages;           /* entries of a block-table row                                     */
+    int32_t kv_fp8;              /* nonzero: e4m3 pools with k_scale / v_scale                        */
+    float scale;
+    const void* q;
+    int64_t q_stride_b, q_stride_h, q_stride_r;
+    const void* k;               /* pool [num_pages, Hkv, S, D] by the three strides below            */
+    const void* v;
+    int64_t k_stride_page, k_stride_h, k_stride_pos;
+    int64_t v_stride_page, v_stride_h, v_stride_pos;
+    void* out;
+    int64_t out_stride_b, out_stride_r, out_stride_h;
+    const int32_t* kv_limit;
+    const uint64_t* win_bits;
+    const int64_t* kv_len_dev;
+    int64_t kv_len_add;
+    const int64_t* win_base_dev;
+    int64_t win_base_add;
+    const int32_t* block_table;  /* device int32 [B, max_pages]                                      */
+    int64_t block_table_stride_b;/* >= max_pages                                                     */
+    int32_t* status_or;
+    void* workspace;
+    size_t workspace_bytes;
+    const float* k_scale;        /* device fp32 [Hkv], kv_fp8 only                                    */
+    const float* v_scale;
+} sd_tree_attention_paged_args;
+
+int32_t sd_tree_attention_paged(const sd_tree_attention_paged_args* args, void* stream);
+
+/* sd_kv_store_paged (csrc/kv_store_fp8.hip): the new rows [B, H, R, D] (bf16 / fp16) of K and V into the two
+ * pools in one launch, row r of sequence b at logical position p = pos + pos_dev[b] + r.  cache_fp8 zero: the
+ * pools have `dtype` and the row is copied; nonzero: the pools are e4m3 bytes and the row is quantised as by
+ * sd_kv_store_fp8 (the same bytes; k_scale / v_scale required).  A row with p outside [0, max_pages * S) or
+ * with a page id outside [0, num_pages) is not written and raises SD_ROW_INVALID_DIST.  Source strides in
+ * elements and multiples of 8; pool strides in BYTES and multiples of 16; head_dim a multiple of 16.       */
+typedef struct {
+    int32_t batch, heads, rows, head_dim;
+    int32_t dtype;               /* SD_BF16 or SD_F16, of k_new / v_new                              */
+    int32_t cache_fp8;
+    int32_t page_size, num_pages, max_pages;
+    const void* k_new;
+    const void* v_new;
+    int64_t kn_stride_b, kn_stride_h, kn_stride_r;
+    int64_t vn_stride_b, vn_stride_h, vn_stride_r;
+    void* k_cache;
+    void* v_cache;
+    int64_t kc_stride_page, kc_stride_h, kc_stride_pos;     /* bytes                                 */
+    int64_t vc_stride_page, vc_stride_h, vc_stride_pos;
+    int64_t pos;
+    const int64_t* pos_dev;      /* device int64 [B], required                                       */
+    const int32_t* block_table;
+    int64_t block_table_stride_b;
+    const float* k_scale;        /* device fp32 [H], cache_fp8 only                                   */
+    const float* v_scale;
+    int32_t* status_or;
+} sd_kv_store_paged_args;
+
+int32_t sd_kv_store_paged(const sd_kv_store_paged_args* args, void* stream);
+
+/* sd_kv_compact_paged (csrc/kv_compact.hip): sd_kv_compact_ragged's rule, src = base_b + slot(path[b][d]) to
+ * dst = base_b + d in ascending d, with both positions translated through the block table; base_b = base +
+ * base_dev[b].  tensors are the pools of all layers (one shape and stride set, bytes: an FP8 pool is served as
+ * it stands).  One thread owns a fixed byte range of one (tensor, sequence, head) for all depths, and since a
+ * sequence's pages are distinct, two logical positions never share bytes: the in-place argument of
+ * sd_kv_compact holds as it stands.  A table that repeats a page inside the window is the caller's error:
+ * undefined result, no fault.  A window that leaves [0, max_pages * S) moves nothing; a page id outside
+ * [0, num_pages) ends its sequence's moves; both raise SD_ROW_INVALID_DIST, per sequence.                 */
+typedef struct {
+    int32_t n_tensors, batch, heads, max_depth, num_slots, row_bytes;
+    int32_t page_size, num_pages, max_pages;
+    void* const* tensors;        /* HOST array of n_tensors pool pointers                            */
+    int64_t stride_page, stride_h, stride_pos;              /* bytes                                 */
+    int64_t base;
+    const int64_t* base_dev;     /* device int64 [B], required                                       */
+    const int32_t* block_table;
+    int64_t block_table_stride_b;
+    const int32_t* path;
+    int64_t path_stride_b;
+    const int32_t* count;
+    const int32_t* node_slot;    /* nullable HOST int32 [SD_TREE_MAX_NODES]                          */
+    int32_t* status_or;
+} sd_kv_compact_paged_args;
+
+int32_t sd_kv_compact_paged(const sd_kv_compact_paged_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,7 +136,181 @@ __global__ void __launch_bounds__(kKvThreads) k_kv_compact_ragged(KvCompact P) {
     kv_compact_body<W, true>(P);
 }
 
+// ---- paged pools (sd_kv_compact_paged) ----------------------------------------------------------------
+// The same moves with every position translated through the sequence's block-table row: position p lives in
+// page table[p >> shift] at slot p & (S - 1).  A sequence's pages are distinct, so two logical positions never
+// share bytes, and a thread still owns one fixed byte range (now: the same offset in every page) of one
+// (tensor, sequence, head) for all depths: what it has written before depth d lies at logical positions below
+// base + d <= src, hence at other bytes than any source it has yet to load.  The in-place argument above holds
+// unchanged, the loads of kKvGroup depths may run ahead of their stores.  (A table that repeats a page inside
+// the window breaks the premise: the caller's error, undefined result, no fault.)
+// The window has at most 64 slots, so it touches at most kKvWinPages = 5 pages (S = 16, base mid-page): a
+// thread reads those ids once, before the first depth, and picks among them by constant-index selects.
+constexpr int kKvWinPages = 5;
+
+struct KvCompactPaged {
+    void* tensors[SD_KV_MAX_TENSORS];
+    uint32_t slot_words[SD_TREE_MAX_NODES / 4];
+    int32_t has_slots;
+    int32_t batch, heads, chunks, max_depth, num_slots, row_bytes, page_shift, num_pages, max_pages;
+    int64_t stride_page, stride_h, stride_pos, base, bt_sb;
+    const int64_t* base_dev;   // [B]
+    const int32_t* block_table;
+    const int32_t* path;
+    int64_t path_stride_b;
+    const int32_t* count;
+    int32_t* status_or;
+};
+
+template <int W>
+__global__ void __launch_bounds__(kKvThreads) k_kv_compact_paged(KvCompactPaged P) {
+    using V = typename KvVec<W>::type;
+    constexpr int NV = kKvChunk / W;
+    __shared__ uint32_t s_slot[SD_TREE_MAX_NODES / 4];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < SD_TREE_MAX_NODES / 4; ++i) s_slot[i] = P.slot_words[i];
+    }
+    __syncthreads();
+    const int64_t gid = (int64_t)blockIdx.x * kKvThreads + threadIdx.x;
+    const int chunk = (int)(gid % P.chunks);
+    const int64_t bh = gid / P.chunks;
+    const int h = (int)(bh % P.heads);
+    const int64_t b = bh / P.heads;
+    if (b >= P.batch) return;
+    const bool reporter = blockIdx.y == 0 && h == 0 && chunk == 0;
+    const int32_t cnt = P.count[b];
+    const int lim = cnt < P.max_depth ? (cnt > 0 ? cnt : 0) : P.max_depth;
+    if (lim == 0) return;
+    const int64_t base = P.base + P.base_dev[b];
+    if (base < 0 || base > ((int64_t)P.max_pages << P.page_shift) - P.num_slots) {   // the window leaves the table
+        if (reporter && P.status_or) atomicOr(P.status_or, SD_ROW_INVALID_DIST);
+        return;
+    }
+    // the window's pages, read once: table entries page0 .. page of base + num_slots - 1 (all inside the row)
+    const int32_t* trow = P.block_table + b * P.bt_sb;
+    const int32_t page0 = (int32_t)(base >> P.page_shift);
+    const int32_t n_win = (int32_t)((base + P.num_slots - 1) >> P.page_shift) - page0 + 1;
+    auto page_id = [&](int i) -> int32_t {       // refused (or behind the window): -1, never an address
+        const int32_t id = i < n_win ? trow[page0 + i] : -1;
+        return (uint32_t)id >= (uint32_t)P.num_pages ? -1 : id;
+    };
+    static_assert(kKvWinPages == 5, "five named registers below");
+    const int32_t pg0 = page_id(0), pg1 = page_id(1), pg2 = page_id(2), pg3 = page_id(3), pg4 = page_id(4);
+    const int32_t off0 = (int32_t)(base & (((int64_t)1 << P.page_shift) - 1));
+    const int32_t smask = (1 << P.page_shift) - 1;
+    char* tbase = static_cast<char*>(P.tensors[blockIdx.y]) + h * P.stride_h + (int64_t)chunk * kKvChunk;
+    // the bytes of window slot s (0 <= s < num_slots), null when its page id was refused
+    auto at = [&](int32_t s) -> char* {
+        const int32_t q = off0 + s, rel = q >> P.page_shift;
+        const int32_t id = rel == 0 ? pg0 : rel == 1 ? pg1 : rel == 2 ? pg2 : rel == 3 ? pg3 : pg4;
+        return id < 0 ? nullptr : tbase + id * P.stride_page + (int64_t)(q & smask) * P.stride_pos;
+    };
+    const int32_t* prow = P.path + b * P.path_stride_b;
+    const int left = P.row_bytes - chunk * kKvChunk;
+    const int nacc = (left < kKvChunk ? left : kKvChunk) / W;
+    bool stop = false, bad = false;
+#pragma unroll 1
+    for (int d0 = 0; d0 < lim && !stop; d0 += kKvGroup) {
+        int32_t pth[kKvGroup];
+#pragma unroll
+        for (int g = 0; g < kKvGroup; ++g) pth[g] = d0 + g < lim ? prow[d0 + g] : -1;
+        const char* from[kKvGroup];   // null: nothing to move
+        char* to[kKvGroup];
+        V v[kKvGroup][NV];
+#pragma unroll
+        for (int g = 0; g < kKvGroup; ++g) {
+            const int d = d0 + g;
+            from[g] = nullptr;
+            to[g] = nullptr;
+            if (d < lim && !stop) {
+                const int32_t p = pth[g];
+                int32_t s = -1;
+                if (p >= 0 && p < SD_TREE_MAX_NODES)
+                    s = P.has_slots ? (int32_t)((s_slot[p >> 2] >> ((p & 3) * 8)) & 0xffu) : p;
+                if (s < d || s >= P.num_slots) { stop = true; bad = true; }   // ends this sequence's moves
+                else if (s != d) {
+                    const char* f = at(s);
+                    char* t = at(d);
+                    if (!f || !t) { stop = true; bad = true; }                // a refused page id
+                    else { from[g] = f; to[g] = t; }
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < kKvGroup; ++g)
+            if (from[g]) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k)
+                    if (W == kKvChunk || k < nacc) v[g][k] = *reinterpret_cast<const V*>(from[g] + k * W);
+            }
+#pragma unroll
+        for (int g = 0; g < kKvGroup; ++g)
+            if (from[g]) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k)
+                    if (W == kKvChunk || k < nacc) *reinterpret_cast<V*>(to[g] + k * W) = v[g][k];
+            }
+    }
+    if (bad && reporter && P.status_or) atomicOr(P.status_or, SD_ROW_INVALID_DIST);
+}
+
 }  // namespace sd
+
+extern "C" int32_t sd_kv_compact_paged(const sd_kv_compact_paged_args* a, void* stream) {
+    using namespace sd_host;
+    if (!a || !a->tensors) return SD_ERR_INVALID;
+    if (a->n_tensors < 1) return SD_ERR_INVALID;
+    if (a->n_tensors > SD_KV_MAX_TENSORS) return SD_ERR_UNSUPPORTED;
+    if (a->batch < 1 || a->heads < 1 || a->num_pages < 1 || a->max_pages < 1) return SD_ERR_INVALID;
+    if (a->row_bytes <= 0 || (a->row_bytes & 1)) return SD_ERR_INVALID;
+    if (a->stride_page < 0 || a->stride_h < 0 || a->stride_pos < a->row_bytes) return SD_ERR_INVALID;
+    if (a->max_depth < 1 || a->num_slots < 1) return SD_ERR_INVALID;
+    if (a->max_depth > SD_MAX_GAMMA || a->num_slots > SD_TREE_MAX_NODES) return SD_ERR_UNSUPPORTED;
+    int shift = 0;
+    while (shift < 9 && (1 << shift) != a->page_size) ++shift;
+    if (shift < 4 || shift > 8) return SD_ERR_INVALID;               // 16, 32, 64, 128, 256
+    if ((int64_t)a->max_pages * a->page_size < a->num_slots) return SD_ERR_INVALID;
+    if (!a->base_dev || !a->block_table || a->block_table_stride_b < a->max_pages) return SD_ERR_INVALID;
+    if (!a->path || !a->count || a->path_stride_b < a->max_depth) return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a->path) | reinterpret_cast<uintptr_t>(a->count) | reinterpret_cast<uintptr_t>(a->status_or) |
+         reinterpret_cast<uintptr_t>(a->block_table)) & 3)
+        return SD_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(a->base_dev) & 7) return SD_ERR_INVALID;
+    uintptr_t bits = (uintptr_t)a->stride_pos | (uintptr_t)a->row_bytes | (uintptr_t)a->stride_page;
+    if (a->heads > 1) bits |= (uintptr_t)a->stride_h;
+    sd::KvCompactPaged P{};
+    for (int t = 0; t < a->n_tensors; ++t) {
+        if (!a->tensors[t]) return SD_ERR_INVALID;
+        bits |= reinterpret_cast<uintptr_t>(a->tensors[t]);
+        P.tensors[t] = a->tensors[t];
+    }
+    if (bits & 1) return SD_ERR_INVALID;
+    P.has_slots = a->node_slot != nullptr;
+    if (a->node_slot)
+        for (int i = 0; i < SD_TREE_MAX_NODES; ++i) {
+            const int32_t s = a->node_slot[i];
+            const uint32_t byte = s >= 0 && s < SD_TREE_MAX_NODES ? (uint32_t)s : 0xffu;
+            P.slot_words[i >> 2] |= byte << ((i & 3) * 8);
+        }
+    const int width = (bits & 15) == 0 ? 16 : (bits & 7) == 0 ? 8 : (bits & 3) == 0 ? 4 : 2;
+    P.chunks = (a->row_bytes + sd::kKvChunk - 1) / sd::kKvChunk;
+    const int64_t bh = (int64_t)a->batch * a->heads;
+    const int64_t max_threads = ((int64_t)1 << 32) - 1;
+    if (bh > max_threads / P.chunks) return SD_ERR_UNSUPPORTED;
+    const int64_t blocks = (bh * P.chunks + sd::kKvThreads - 1) / sd::kKvThreads;
+    if (blocks * a->n_tensors > max_threads / sd::kKvThreads) return SD_ERR_UNSUPPORTED;
+    P.batch = a->batch; P.heads = a->heads; P.max_depth = a->max_depth; P.num_slots = a->num_slots;
+    P.row_bytes = a->row_bytes; P.page_shift = shift; P.num_pages = a->num_pages; P.max_pages = a->max_pages;
+    P.stride_page = a->stride_page; P.stride_h = a->stride_h; P.stride_pos = a->stride_pos;
+    P.base = a->base; P.base_dev = a->base_dev; P.block_table = a->block_table; P.bt_sb = a->block_table_stride_b;
+    P.path = a->path; P.path_stride_b = a->path_stride_b; P.count = a->count; P.status_or = a->status_or;
+    clear_stale_error();
+    const dim3 grid((unsigned)blocks, (unsigned)a->n_tensors);
+    return dispatch_int<16, 8, 4, 2>(width, [&](auto w) {
+        return launch(sd::k_kv_compact_paged<decltype(w)::value>, grid, dim3(sd::kKvThreads), 0, stream, P);
+    });
+}
 
 // sd_kv_compact (per_seq false: base_dev nullable, one element) and sd_kv_compact_ragged (true: base_dev
 // given, one element per sequence)

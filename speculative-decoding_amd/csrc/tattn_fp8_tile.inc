@@ -17,6 +17,13 @@
 //               (keys 16s + 4half + e and 16s + 8 + 4half + e) are one A fragment of the second.
 // The dequantisation scales never enter a product: k_scale[hkv] is folded into the fp32 score factor and
 // v_scale[hkv] multiplies the fp32 accumulators where the result is written (out, or part_o).
+// The address of a K or V row is formed in one place each, through TA_K_ROW(kj) / TA_V_ROW(kj), which the
+// including kernel may define (the paged kernels do); the default is the contiguous cache's.
+#ifndef TA_K_ROW
+#define TA_K_ROW(kj) kb + kj * P.k_sp
+#define TA_V_ROW(kj) vb + kj * P.v_sp
+#define TA_ROW_DEFAULT
+#endif
     using T = TaType<DT>;
     using E = typename T::elem;
     using V8 = typename T::vec8;
@@ -88,7 +95,7 @@
             const int32_t kj = t * kTaTile + key;
             kreg[it] = zero4;
             if (ta_visible(kj, any_lim, any_bits, win_base))
-                kreg[it] = *reinterpret_cast<const ta_u32x4*>(kb + kj * P.k_sp + c * 16);
+                kreg[it] = *reinterpret_cast<const ta_u32x4*>(TA_K_ROW(kj) + c * 16);
         }
         if (v_loader) {
 #pragma unroll
@@ -96,7 +103,7 @@
                 const int32_t kj = t * kTaTile + 4 * vq + e;
                 vreg[e] = zero4;
                 if (ta_visible(kj, any_lim, any_bits, win_base))
-                    vreg[e] = *reinterpret_cast<const ta_u32x4*>(vb + kj * P.v_sp + vc * 16);
+                    vreg[e] = *reinterpret_cast<const ta_u32x4*>(TA_V_ROW(kj) + vc * 16);
             }
         }
     };
@@ -260,3 +267,8 @@
             }
         }
     }
+#ifdef TA_ROW_DEFAULT
+#undef TA_K_ROW
+#undef TA_V_ROW
+#undef TA_ROW_DEFAULT
+#endif

@@ -6,6 +6,13 @@
 //     TA_WIN_BASE   the position of bit 0 of its window words (int64)
 //     TA_T_BEGIN, TA_T_END   the workgroup's 64-key tiles, from `split` (= blockIdx.x) and `n_tiles`
 // The result goes to `out` (P.part_ml null) or to the workspace as partial `split` of P.splits.
+// The address of a K or V row is formed in one place each, through TA_K_ROW(kj) / TA_V_ROW(kj), which the
+// including kernel may define (the paged kernels do); the default is the contiguous cache's.
+#ifndef TA_K_ROW
+#define TA_K_ROW(kj) kb + kj * P.k_sp
+#define TA_V_ROW(kj) vb + kj * P.v_sp
+#define TA_ROW_DEFAULT
+#endif
     using T = TaType<DT>;
     using E = typename T::elem;
     using V8 = typename T::vec8;
@@ -73,7 +80,7 @@
             const int32_t kj = t * kTaTile + key;
             kreg[it] = zero4;
             if (ta_visible(kj, any_lim, any_bits, win_base))
-                kreg[it] = *reinterpret_cast<const ta_u32x4*>(kb + kj * P.k_sp + c * 8);
+                kreg[it] = *reinterpret_cast<const ta_u32x4*>(TA_K_ROW(kj) + c * 8);
         }
 #pragma unroll
         for (int it = 0; it < VL; ++it) {
@@ -83,7 +90,7 @@
                 const int32_t kj = t * kTaTile + 2 * pair + e;
                 vreg[it][e] = zero4;
                 if (ta_visible(kj, any_lim, any_bits, win_base))
-                    vreg[it][e] = *reinterpret_cast<const ta_u32x4*>(vb + kj * P.v_sp + c * 8);
+                    vreg[it][e] = *reinterpret_cast<const ta_u32x4*>(TA_V_ROW(kj) + c * 8);
             }
         }
     };
@@ -239,3 +246,8 @@
             }
         }
     }
+#ifdef TA_ROW_DEFAULT
+#undef TA_K_ROW
+#undef TA_V_ROW
+#undef TA_ROW_DEFAULT
+#endif

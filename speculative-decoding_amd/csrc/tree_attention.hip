@@ -270,6 +270,129 @@ __global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_ragged_partial(TaParam
     }
 }
 
+// ---- paged caches (sd_tree_attention_paged) ----------------------------------------------------------------
+// K and V in pages of S = 2^page_shift positions of a shared pool, reached through a device block table.  The
+// grid, the early exits, the partial records and the combine are k_tattn_ragged_partial's; the tile bodies are
+// the same two files, whose row address goes through TA_K_ROW / TA_V_ROW.
+//
+// The page walk.  A key's page id would be a dependent global load in front of the K/V load the body issues
+// one tile ahead.  A workgroup needs the ids of its own chunk only, and knows which as soon as it has len_b,
+// so all 256 threads fetch them ONCE, before the body's first barrier, into s_pg (kTaPgStage int32), checked
+// against [0, num_pages) as they are staged (a refused id is stored as -1 and reported).  A lookup in load_tile
+// is then one LDS read at ((kj >> shift) - first page of the chunk) and a 64-bit multiply-add: no global round
+// trip and no division on the load path.  A chunk longer than kTaPgStage pages (S = 16 with chunks beyond 256
+// tiles: only when B * Hkv alone fills the device at a cap of 256k keys or more) reads the entries behind the
+// staged ones from the table, with the same check.  A refused id yields the address of ta_zero_row, 256 zero
+// bytes of the library's own, so its keys arrive in LDS as zeros and no address is formed from the id.
+constexpr int kTaPgStage = 1024;       // page ids a workgroup stages (4 KiB of LDS)
+
+struct TaPaged {
+    const int32_t* block_table;
+    int64_t bt_sb, k_ps, v_ps;         // table row stride (entries); page strides in the pools' elements
+    int32_t num_pages, page_shift;
+};
+
+__device__ const ta_u32x4 ta_zero_row[16] = {};      // a K/V row of zeros: D <= 128 elements of <= 2 bytes
+
+// the chunk's page ids into s_pg: entries [p0, ceil(key_end / S)) of the sequence's row, key_end <= len_b, so
+// no entry at or beyond ceil(len_b / S) is read
+__device__ __forceinline__ void ta_stage_pages(int32_t* s_pg, const TaPaged& Pg, const int32_t* bt_row, int32_t p0,
+                                               int32_t key_end, int32_t* status_or) {
+    const int32_t n_all = ((key_end + (1 << Pg.page_shift) - 1) >> Pg.page_shift) - p0;
+    const int32_t n = n_all < kTaPgStage ? n_all : kTaPgStage;
+    bool bad = false;
+    for (int i = threadIdx.x; i < n; i += kTaThreads) {
+        int32_t id = bt_row[p0 + i];
+        if ((uint32_t)id >= (uint32_t)Pg.num_pages) { id = -1; bad = true; }
+        s_pg[i] = id;
+    }
+    if (bad && status_or && blockIdx.y == 0) atomicOr(status_or, SD_ROW_INVALID_DIST);
+}
+
+// the row of key kj (< len_b) in a pool: `head` is the pool's base moved to the K/V head, ps / sp its page and
+// slot strides
+template <typename E>
+__device__ __forceinline__ const E* ta_paged_row(const E* head, const int32_t* s_pg, const TaPaged& Pg, const int32_t* bt_row,
+                                                 int32_t p0, int32_t* status_or, int32_t kj, int64_t ps, int64_t sp) {
+    const int32_t pi = (kj >> Pg.page_shift) - p0;
+    // the LDS read is unconditional: as one arm of a branch it would be merged with the table read of the other
+    // arm into one FLAT load, which waits on the LDS counter and the memory counter alike
+    int32_t id = s_pg[pi < kTaPgStage ? pi : 0];
+    if (pi >= kTaPgStage) {                // behind the staged entries: a chunk of more than kTaPgStage pages
+        id = bt_row[p0 + pi];
+        if ((uint32_t)id >= (uint32_t)Pg.num_pages) {
+            id = -1;
+            if (status_or) atomicOr(status_or, SD_ROW_INVALID_DIST);
+        }
+    }
+    // one base, two byte offsets: a select between two POINTERS loses the pool's address space and turns the
+    // body's K/V loads into flat loads, which wait on the LDS counter as well as the memory counter
+    const int64_t in_pool = (id * ps + (kj & ((1 << Pg.page_shift) - 1)) * sp) * (int64_t)sizeof(E);
+    const int64_t to_zero = (int64_t)(reinterpret_cast<uintptr_t>(ta_zero_row) - reinterpret_cast<uintptr_t>(head));
+    return reinterpret_cast<const E*>(reinterpret_cast<const char*>(head) + (id < 0 ? to_zero : in_pool));
+}
+
+#define TA_K_ROW(kj) ta_paged_row(kb, s_pg, Pg, pg_row, pg_p0, Rg.status_or, kj, Pg.k_ps, P.k_sp)
+#define TA_V_ROW(kj) ta_paged_row(vb, s_pg, Pg, pg_row, pg_p0, Rg.status_or, kj, Pg.v_ps, P.v_sp)
+
+// k_tattn_ragged_partial over a paged pool (P.k_sb = P.v_sb = 0: kb / vb of the body are the pools at the head)
+template <int DT, int D>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_paged_partial(TaParams P, TaRagged Rg, TaPaged Pg) {
+    __shared__ int32_t s_pg[kTaPgStage];
+    const int c = blockIdx.x, b = blockIdx.z;
+    bool bad;
+    const int32_t len = ta_ragged_len(Rg, b, &bad);
+    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
+    const int32_t pg_key0 = c * Rg.chunk_tiles * kTaTile;          // < 2^20: ta_chunks
+    if (pg_key0 >= len && P.part_ml != nullptr) return;
+    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
+    const int32_t* pg_row = Pg.block_table + b * Pg.bt_sb;
+    const int32_t pg_p0 = pg_key0 >> Pg.page_shift;
+    const int32_t pg_end = pg_key0 + Rg.chunk_tiles * kTaTile;
+    ta_stage_pages(s_pg, Pg, pg_row, pg_p0, pg_end < len ? pg_end : len, Rg.status_or);   // visible after the body's first barrier
+    {
+#define TA_KV_LEN len
+#define TA_WIN_BASE rg_win_base
+#define TA_T_BEGIN split * Rg.chunk_tiles
+#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+#include "tattn_tile.inc"
+#undef TA_KV_LEN
+#undef TA_WIN_BASE
+#undef TA_T_BEGIN
+#undef TA_T_END
+    }
+}
+
+// k_tattn_fp8_ragged_partial over a paged e4m3 pool
+template <int DT, int D>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_paged_partial(TaParams P, TaRagged Rg, TaFp8 Fs, TaPaged Pg) {
+    __shared__ int32_t s_pg[kTaPgStage];
+    const int c = blockIdx.x, b = blockIdx.z;
+    bool bad;
+    const int32_t len = ta_ragged_len(Rg, b, &bad);
+    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
+    const int32_t pg_key0 = c * Rg.chunk_tiles * kTaTile;
+    if (pg_key0 >= len && P.part_ml != nullptr) return;
+    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
+    const int32_t* pg_row = Pg.block_table + b * Pg.bt_sb;
+    const int32_t pg_p0 = pg_key0 >> Pg.page_shift;
+    const int32_t pg_end = pg_key0 + Rg.chunk_tiles * kTaTile;
+    ta_stage_pages(s_pg, Pg, pg_row, pg_p0, pg_end < len ? pg_end : len, Rg.status_or);
+    {
+#define TA_KV_LEN len
+#define TA_WIN_BASE rg_win_base
+#define TA_T_BEGIN split * Rg.chunk_tiles
+#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+#include "tattn_fp8_tile.inc"
+#undef TA_KV_LEN
+#undef TA_WIN_BASE
+#undef TA_T_BEGIN
+#undef TA_T_END
+    }
+}
+#undef TA_K_ROW
+#undef TA_V_ROW
+
 // k_tattn_combine over the chunks a sequence's own length reaches: chunks 0 .. ceil(tiles_b / chunk_tiles) - 1
 // were written by this call's k_tattn_ragged_partial, the slots behind them were not and are not read.
 template <int DT>
@@ -599,6 +722,79 @@ static int32_t ta_ragged_call(const A* a, void* stream, const sd::TaFp8* fs) {
                               dim3(sd::kTaThreads), 0, stream, P, Rg, *fs);
             return launch(sd::k_tattn_ragged_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
                           0, stream, P, Rg);
+        });
+    });
+    if (st != SD_OK || chunks == 1) return st;
+    const int64_t total = (int64_t)a->batch * a->heads_q * a->rows * (a->head_dim / 4);
+    const dim3 cgrid((unsigned)((total + sd::kTaThreads - 1) / sd::kTaThreads));
+    return dispatch_dtype16(a->dtype, [&](auto dt) {
+        return launch(sd::k_tattn_ragged_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, Rg, total);
+    });
+}
+
+// ---- paged caches: the ragged call through a block table -------------------------------------------------
+extern "C" int32_t sd_tree_attention_paged(const sd_tree_attention_paged_args* a, void* stream) {
+    using namespace sd_host;
+    if (!a) return SD_ERR_INVALID;
+    if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
+    if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;
+    if (a->chunk_tiles < 0) return SD_ERR_INVALID;
+    int shift = 0;
+    while (shift < 9 && (1 << shift) != a->page_size) ++shift;
+    if (shift < 4 || shift > 8) return SD_ERR_INVALID;               // 16, 32, 64, 128, 256
+    if (a->num_pages < 1 || a->max_pages < 1) return SD_ERR_INVALID;
+    const int32_t shape = sd::ta_check_shape(a->batch, a->heads_q, a->heads_kv, a->rows, a->head_dim, a->kv_cap, 0);
+    if (shape != SD_OK) return shape;
+    if (a->kv_cap > (int64_t)a->max_pages * a->page_size) return SD_ERR_INVALID;
+    // the fields the ragged checks and ta_params read, with the page strides in the place of the batch strides
+    sd_tree_attention_ragged_fp8_args r{};
+    r.head_dim = a->head_dim; r.heads_q = a->heads_q; r.heads_kv = a->heads_kv; r.rows = a->rows; r.scale = a->scale;
+    r.q = a->q; r.q_stride_b = a->q_stride_b; r.q_stride_h = a->q_stride_h; r.q_stride_r = a->q_stride_r;
+    r.k = a->k; r.v = a->v;
+    r.k_stride_b = a->k_stride_page; r.k_stride_h = a->k_stride_h; r.k_stride_pos = a->k_stride_pos;
+    r.v_stride_b = a->v_stride_page; r.v_stride_h = a->v_stride_h; r.v_stride_pos = a->v_stride_pos;
+    r.out = a->out; r.out_stride_b = a->out_stride_b; r.out_stride_r = a->out_stride_r; r.out_stride_h = a->out_stride_h;
+    r.kv_limit = a->kv_limit; r.win_bits = a->win_bits; r.k_scale = a->k_scale; r.v_scale = a->v_scale;
+    const int32_t tensors = sd::ta_check_tensors(&r);
+    if (tensors != SD_OK) return tensors;
+    if (a->kv_fp8) {
+        const int32_t st = sd::ta_check_fp8(&r);
+        if (st != SD_OK) return st;
+    }
+    if (!a->kv_len_dev || !a->win_base_dev) return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a->kv_len_dev) | reinterpret_cast<uintptr_t>(a->win_base_dev)) & 7) return SD_ERR_INVALID;
+    if (!a->block_table || (reinterpret_cast<uintptr_t>(a->block_table) & 3)) return SD_ERR_INVALID;
+    if (a->block_table_stride_b < a->max_pages) return SD_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(a->status_or) & 3) return SD_ERR_INVALID;
+    const int chunks = sd::ta_chunks(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
+    if (chunks == 0) return SD_ERR_UNSUPPORTED;
+    sd::TaWorkspace w{nullptr, nullptr, 0};
+    if (chunks > 1) {
+        w = sd::ta_carve(a->workspace, a->batch, a->heads_q, a->rows, a->head_dim, chunks);
+        if (!a->workspace || a->workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(a->workspace) & 255) return SD_ERR_INVALID;
+    }
+    sd::TaParams P = sd::ta_params(&r, w, chunks);
+    P.k_sb = 0; P.v_sb = 0;                                          // the body's kb / vb: the pools at the head
+    sd::TaRagged Rg{};
+    Rg.kv_len_dev = a->kv_len_dev; Rg.win_base_dev = a->win_base_dev;
+    Rg.kv_len_add = a->kv_len_add; Rg.win_base_add = a->win_base_add;
+    Rg.status_or = a->status_or; Rg.kv_cap = a->kv_cap;
+    Rg.chunk_tiles = sd::ta_chunk_tiles(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
+    sd::TaPaged Pg{};
+    Pg.block_table = a->block_table; Pg.bt_sb = a->block_table_stride_b;
+    Pg.k_ps = a->k_stride_page; Pg.v_ps = a->v_stride_page;
+    Pg.num_pages = a->num_pages; Pg.page_shift = shift;
+    const sd::TaFp8 fs{a->k_scale, a->v_scale};
+    clear_stale_error();
+    const dim3 grid((unsigned)chunks, (unsigned)a->heads_kv, (unsigned)a->batch);
+    int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
+        return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
+            if (a->kv_fp8)
+                return launch(sd::k_tattn_fp8_paged_partial<decltype(dt)::value, decltype(d)::value>, grid,
+                              dim3(sd::kTaThreads), 0, stream, P, Rg, fs, Pg);
+            return launch(sd::k_tattn_paged_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
+                          0, stream, P, Rg, Pg);
         });
     });
     if (st != SD_OK || chunks == 1) return st;

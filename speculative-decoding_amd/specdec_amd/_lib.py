@@ -92,7 +92,8 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_verify_tree_swor_workspace_size", "sd_verify_tree_swor",
            "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention",
            "sd_tree_attention_ragged_chunks", "sd_tree_attention_ragged_workspace_size", "sd_tree_attention_ragged",
-           "sd_tree_attention_fp8", "sd_tree_attention_ragged_fp8", "sd_kv_store_fp8")
+           "sd_tree_attention_fp8", "sd_tree_attention_ragged_fp8", "sd_kv_store_fp8",
+           "sd_tree_attention_paged", "sd_kv_store_paged", "sd_kv_compact_paged")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -443,6 +444,59 @@ class sd_kv_store_fp8_args(C.Structure):
     ]
 
 
+# paged KV caches: pools [num_pages, Hkv, S, D] behind a device block table
+class sd_tree_attention_paged_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("heads_q", C.c_int32), ("heads_kv", C.c_int32), ("rows", C.c_int32),
+        ("head_dim", C.c_int32), ("dtype", C.c_int32), ("kv_cap", C.c_int32), ("chunk_tiles", C.c_int32),
+        ("page_size", C.c_int32), ("num_pages", C.c_int32), ("max_pages", C.c_int32), ("kv_fp8", C.c_int32),
+        ("scale", C.c_float),
+        ("q", C.c_void_p), ("q_stride_b", C.c_int64), ("q_stride_h", C.c_int64), ("q_stride_r", C.c_int64),
+        ("k", C.c_void_p), ("v", C.c_void_p),
+        ("k_stride_page", C.c_int64), ("k_stride_h", C.c_int64), ("k_stride_pos", C.c_int64),
+        ("v_stride_page", C.c_int64), ("v_stride_h", C.c_int64), ("v_stride_pos", C.c_int64),
+        ("out", C.c_void_p), ("out_stride_b", C.c_int64), ("out_stride_r", C.c_int64), ("out_stride_h", C.c_int64),
+        ("kv_limit", C.c_void_p), ("win_bits", C.c_void_p),
+        ("kv_len_dev", C.c_void_p), ("kv_len_add", C.c_int64),
+        ("win_base_dev", C.c_void_p), ("win_base_add", C.c_int64),
+        ("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64),
+        ("status_or", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+    ]
+
+
+class sd_kv_store_paged_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("heads", C.c_int32), ("rows", C.c_int32), ("head_dim", C.c_int32),
+        ("dtype", C.c_int32), ("cache_fp8", C.c_int32),
+        ("page_size", C.c_int32), ("num_pages", C.c_int32), ("max_pages", C.c_int32),
+        ("k_new", C.c_void_p), ("v_new", C.c_void_p),
+        ("kn_stride_b", C.c_int64), ("kn_stride_h", C.c_int64), ("kn_stride_r", C.c_int64),
+        ("vn_stride_b", C.c_int64), ("vn_stride_h", C.c_int64), ("vn_stride_r", C.c_int64),
+        ("k_cache", C.c_void_p), ("v_cache", C.c_void_p),
+        ("kc_stride_page", C.c_int64), ("kc_stride_h", C.c_int64), ("kc_stride_pos", C.c_int64),
+        ("vc_stride_page", C.c_int64), ("vc_stride_h", C.c_int64), ("vc_stride_pos", C.c_int64),
+        ("pos", C.c_int64), ("pos_dev", C.c_void_p),
+        ("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64),
+        ("k_scale", C.c_void_p), ("v_scale", C.c_void_p), ("status_or", C.c_void_p),
+    ]
+
+
+class sd_kv_compact_paged_args(C.Structure):
+    _fields_ = [
+        ("n_tensors", C.c_int32), ("batch", C.c_int32), ("heads", C.c_int32), ("max_depth", C.c_int32),
+        ("num_slots", C.c_int32), ("row_bytes", C.c_int32),
+        ("page_size", C.c_int32), ("num_pages", C.c_int32), ("max_pages", C.c_int32),
+        ("tensors", C.POINTER(C.c_void_p)),
+        ("stride_page", C.c_int64), ("stride_h", C.c_int64), ("stride_pos", C.c_int64),
+        ("base", C.c_int64), ("base_dev", C.c_void_p),
+        ("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64),
+        ("path", C.c_void_p), ("path_stride_b", C.c_int64), ("count", C.c_void_p),
+        ("node_slot", C.POINTER(C.c_int32)), ("status_or", C.c_void_p),
+    ]
+
+
 class sd_vp_header(C.Structure):
     _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
                 ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
@@ -576,6 +630,12 @@ def _load():
     lib.sd_tree_attention_ragged_fp8.argtypes = [C.POINTER(sd_tree_attention_ragged_fp8_args), C.c_void_p]
     lib.sd_kv_store_fp8.restype = C.c_int32
     lib.sd_kv_store_fp8.argtypes = [C.POINTER(sd_kv_store_fp8_args), C.c_void_p]
+    lib.sd_tree_attention_paged.restype = C.c_int32
+    lib.sd_tree_attention_paged.argtypes = [C.POINTER(sd_tree_attention_paged_args), C.c_void_p]
+    lib.sd_kv_store_paged.restype = C.c_int32
+    lib.sd_kv_store_paged.argtypes = [C.POINTER(sd_kv_store_paged_args), C.c_void_p]
+    lib.sd_kv_compact_paged.restype = C.c_int32
+    lib.sd_kv_compact_paged.argtypes = [C.POINTER(sd_kv_compact_paged_args), C.c_void_p]
     lib.sd_tree_grow_workspace_size.restype = C.c_size_t
     lib.sd_tree_grow_workspace_size.argtypes = [C.c_int32] * 5
     lib.sd_tree_grow.restype = C.c_int32

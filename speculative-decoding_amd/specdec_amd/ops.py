@@ -1176,7 +1176,8 @@ def sample_distinct(logits_rows: torch.Tensor, k: int, proc, noise, tokens_out: 
 
 # --------------------------------------------------------------------------- KV-cache compaction
 def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, num_slots: int, node_slot=None,
-               base_dev: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None) -> None:
+               base_dev: Optional[torch.Tensor] = None, status_or: Optional[torch.Tensor] = None,
+               block_table: Optional[torch.Tensor] = None) -> None:
     """Move the accepted path of a token tree to the front of its cache window, in place
     (sd_kv_compact): in every tensor of ``tensors`` (the K and V buffers [B, H, L, D] of all layers: one
     shape, dtype and stride set, unit stride along D), for every sequence b and depth
@@ -1190,10 +1191,17 @@ def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, n
     status per sequence).  Only positions
     [base, base + num_slots) are read or written; a path entry that leaves the window ends its
     sequence's moves and ORs SD_ROW_INVALID_DIST into ``status_or``.  More than SD_KV_MAX_TENSORS
-    tensors take one launch per 256, on the current stream."""
+    tensors take one launch per 256, on the current stream.
+
+    Paged caches: with ``block_table`` (int32 [B, max_pages] on the device) the tensors are the POOLS
+    [num_pages, H, S, D] of all layers and every position goes through the table (sd_kv_compact_paged);
+    ``base_dev`` must then hold one int64 base per sequence.  A window that leaves ``max_pages * S`` or a page
+    id outside [0, num_pages) moves nothing further for its sequence and raises the status bit."""
     tensors = list(tensors)
     if not tensors:
         raise ValueError("kv_compact: no tensors")
+    if block_table is not None:
+        return _kv_compact_paged(tensors, path, count, int(base), int(num_slots), node_slot, base_dev, status_or, block_table)
     t0 = tensors[0]
     if t0.dim() != 4:
         raise ValueError(f"kv_compact: expected [B, H, L, D] tensors, got {tuple(t0.shape)}")
@@ -1246,6 +1254,56 @@ def kv_compact(tensors, path: torch.Tensor, count: torch.Tensor, base: int, *, n
         table = (C.c_void_p * len(part))(*(t.data_ptr() for t in part))
         a.n_tensors, a.tensors = len(part), table
         _lib.check(call(C.byref(a), stream), name)
+
+
+def _kv_compact_paged(tensors, path, count, base, num_slots, node_slot, base_dev, status_or, block_table):
+    t0 = tensors[0]
+    if t0.dim() != 4 or not t0.is_cuda:
+        raise ValueError(f"kv_compact: expected [num_pages, H, S, D] device pools, got {tuple(t0.shape)}")
+    for t in tensors:
+        if t.shape != t0.shape or t.dtype != t0.dtype or t.stride() != t0.stride() or t.device != t0.device:
+            raise ValueError("kv_compact: the tensors must share one shape, dtype, stride set and device")
+    num_pages, H, S, D = t0.shape
+    es, dev = t0.element_size(), t0.device
+    if t0.stride(3) != 1 or (D * es) % 2:
+        raise ValueError("kv_compact: the last dimension must have unit stride and an even number of bytes")
+    if S not in _PAGE_SIZES:
+        raise ValueError(f"kv_compact: page size {S} is not one of {_PAGE_SIZES}")
+    B = path.shape[0] if path.dim() == 2 else -1
+    if path.dtype != torch.int32 or B < 1 or path.stride(1) != 1 or path.device != dev \
+            or not 1 <= path.shape[1] <= _lib.SD_MAX_GAMMA:
+        raise ValueError(f"kv_compact: path must be int32 [B, 1..{_lib.SD_MAX_GAMMA}] on {dev}")
+    if count.dtype != torch.int32 or count.shape != (B,) or count.device != dev or not count.is_contiguous():
+        raise ValueError(f"kv_compact: count must be a contiguous int32 [B] on {dev}")
+    max_pages, bt_stride = _block_table(block_table, B, dev, "kv_compact")
+    if not 1 <= num_slots <= min(_lib.SD_TREE_MAX_NODES, max_pages * S):
+        raise ValueError(f"kv_compact: num_slots must be in 1..{min(_lib.SD_TREE_MAX_NODES, max_pages * S)}, got {num_slots}")
+    if base_dev is None or base_dev.dtype != torch.int64 or base_dev.shape != (B,) or base_dev.device != dev \
+            or not base_dev.is_contiguous():
+        raise ValueError(f"kv_compact: with a block_table, base_dev must be a contiguous int64 [{B}] on {dev}")
+    slots = None
+    if node_slot is not None:
+        node_slot = [int(x) for x in node_slot]
+        if len(node_slot) > _lib.SD_TREE_MAX_NODES:
+            raise ValueError(f"kv_compact: node_slot has at most {_lib.SD_TREE_MAX_NODES} entries")
+        slots = (C.c_int32 * _lib.SD_TREE_MAX_NODES)(*(node_slot + [-1] * (_lib.SD_TREE_MAX_NODES - len(node_slot))))
+    a = _lib.sd_kv_compact_paged_args()
+    a.batch, a.heads, a.max_depth, a.num_slots, a.row_bytes = B, H, path.shape[1], num_slots, D * es
+    a.page_size, a.num_pages, a.max_pages = S, num_pages, max_pages
+    a.stride_page, a.stride_h, a.stride_pos = (x * es for x in _pool_strides(t0))
+    a.base, a.base_dev = base, base_dev.data_ptr()
+    a.block_table, a.block_table_stride_b = block_table.data_ptr(), bt_stride
+    a.path, a.path_stride_b = path.data_ptr(), (path.stride(0) if B > 1 else path.shape[1])
+    a.count = count.data_ptr()
+    if slots is not None:
+        a.node_slot = slots
+    a.status_or = _status_or_ptr(status_or, dev)
+    stream = C.c_void_p(_stream_ptr(dev))
+    for i in range(0, len(tensors), _lib.SD_KV_MAX_TENSORS):
+        part = tensors[i:i + _lib.SD_KV_MAX_TENSORS]
+        table = (C.c_void_p * len(part))(*(t.data_ptr() for t in part))
+        a.n_tensors, a.tensors = len(part), table
+        _lib.check(lib.sd_kv_compact_paged(C.byref(a), stream), "sd_kv_compact_paged")
 
 
 # --------------------------------------------------------------------------- tree attention
@@ -1323,13 +1381,76 @@ def _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, s
     return out
 
 
+_PAGE_SIZES = (16, 32, 64, 128, 256)
+
+
+def _block_table(bt, B: int, dev, who: str):
+    if not torch.is_tensor(bt) or bt.dtype != torch.int32 or bt.dim() != 2 or bt.shape[0] != B or bt.device != dev \
+            or bt.shape[1] < 1 or (bt.shape[1] > 1 and bt.stride(1) != 1):
+        raise ValueError(f"{who}: block_table must be an int32 [{B}, max_pages] tensor on {dev} with unit stride along pages")
+    return bt.shape[1], (bt.stride(0) if B > 1 else bt.shape[1])
+
+
+def _pool_strides(t):
+    """(page, head, slot) strides of a pool [num_pages, H, S, D]; a dimension of size 1 is never stepped along."""
+    sp, sh, ss = (t.stride(i) if t.shape[i] > 1 else 0 for i in (0, 1, 2))
+    return sp, sh, ss or t.shape[3]
+
+
+def _tree_attention_paged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles, kv_len_add,
+                          win_base_add, status_or, workspace, scales, block_table):
+    """tree_attention over paged pools k, v [num_pages, Hkv, S, D] (sd_tree_attention_paged)."""
+    B, Hq, R, D = q.shape
+    num_pages, Hkv, S = k.shape[0], k.shape[1], k.shape[2]
+    dev = q.device
+    if S not in _PAGE_SIZES:
+        raise ValueError(f"tree_attention: page size {S} is not one of {_PAGE_SIZES}")
+    max_pages, bt_stride = _block_table(block_table, B, dev, "tree_attention")
+    limit = min(max_pages * S, _lib.SD_TREE_ATTN_MAX_KV)
+    kv_cap = limit if kv_cap is None else int(kv_cap)
+    if not 1 <= kv_cap <= limit:
+        raise ValueError(f"tree_attention: kv_cap {kv_cap} outside 1..{limit}")
+    if not torch.is_tensor(kv_len) or kv_len.dtype != torch.int64 or kv_len.shape != (B,) or kv_len.device != dev \
+            or not kv_len.is_contiguous():
+        raise ValueError(f"tree_attention: with a block_table, kv_len must be a contiguous int64 [{B}] on {dev}")
+    if not torch.is_tensor(win_base):
+        win_base = torch.full((B,), int(win_base), dtype=torch.int64, device=dev)
+    elif win_base.dtype != torch.int64 or win_base.shape != (B,) or win_base.device != dev or not win_base.is_contiguous():
+        raise ValueError(f"tree_attention: a win_base tensor must be a contiguous int64 [{B}] on {dev}")
+    a = _lib.sd_tree_attention_paged_args()
+    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
+    a.kv_cap, a.chunk_tiles = kv_cap, int(chunk_tiles)
+    a.page_size, a.num_pages, a.max_pages, a.kv_fp8 = S, num_pages, max_pages, int(scales is not None)
+    a.scale = float(D) ** -0.5 if scale is None else float(scale)
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.q_stride_r = a.q_stride_r or D
+    a.k_stride_page, a.k_stride_h, a.k_stride_pos = _pool_strides(k)
+    a.v_stride_page, a.v_stride_h, a.v_stride_pos = _pool_strides(v)
+    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.out_stride_h = a.out_stride_h or D
+    a.kv_limit, a.win_bits = kv_limit.data_ptr(), win_bits.data_ptr()
+    a.kv_len_dev, a.kv_len_add = kv_len.data_ptr(), int(kv_len_add)
+    a.win_base_dev, a.win_base_add = win_base.data_ptr(), int(win_base_add)
+    a.block_table, a.block_table_stride_b = block_table.data_ptr(), bt_stride
+    if scales is not None:
+        a.k_scale, a.v_scale = scales[0].data_ptr(), scales[1].data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    need = lib.sd_tree_attention_ragged_workspace_size(B, Hq, Hkv, R, D, kv_cap, int(chunk_tiles))
+    one = tree_attention_chunks(B, Hkv, kv_cap, chunk_tiles) <= 1
+    keep = _ta_workspace(a, workspace, 0 if one else need, dev)
+    _lib.check(lib.sd_tree_attention_paged(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention_paged")
+    del keep, win_base
+    return out
+
+
 def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: torch.Tensor, win_bits: torch.Tensor,
                    win_base, scale: Optional[float] = None, kv_len=None,
                    out: Optional[torch.Tensor] = None, splits: int = 0, *,
                    workspace: Optional[torch.Tensor] = None, kv_cap: Optional[int] = None, chunk_tiles: int = 0,
                    kv_len_add: int = 0, win_base_add: int = 0,
                    status_or: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
-                   v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   v_scale: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The attention of a cached tree forward without a mask tensor (sd_tree_attention, MFMA kernels).
 
     q: [B, Hq, R, D]; k, v: [B, Hkv, L, D] (a cache layer's tensors; the first ``kv_len`` positions are
@@ -1356,11 +1477,21 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     fp32 [Hkv] device tensors: key j of K/V head h then stands for ``k_scale[h] * k[b, h, j].float()``, likewise V
     (sd_tree_attention_fp8 / sd_tree_attention_ragged_fp8).  The scales are read when the kernels run; the bytes
     are converted exactly and the scales applied in fp32, so the result is that of the 16-bit path on the
-    dequantised values.  k / v strides must then be multiples of 16.  ``kv_store_fp8`` writes such a cache."""
+    dequantised values.  k / v strides must then be multiples of 16.  ``kv_store_fp8`` writes such a cache.
+
+    Paged caches: with ``block_table`` (int32 [B, max_pages] on the device, unit stride along pages) k and v are
+    POOLS [num_pages, Hkv, S, D] (or a permuted view of a [P, S, Hkv, D] pool; unit stride along D), S one of
+    16, 32, 64, 128, 256, and position j of sequence b is slot ``j % S`` of page ``block_table[b, j // S]``
+    (sd_tree_attention_paged).  The call is the ragged one: ``kv_len`` must be an int64 device tensor [B],
+    ``win_base`` a tensor or an int, ``kv_cap`` defaults to ``max_pages * S`` capped at the kernels' limit;
+    float8_e4m3fn pools take ``k_scale`` / ``v_scale`` as above.  Table entries at or beyond
+    ``ceil(len_b / S)`` are never read.  A page id outside [0, num_pages) is never used as an address: its
+    keys count as zeros, SD_ROW_INVALID_DIST is ORed into ``status_or``, that sequence's output is finite and
+    meaningless and the other sequences are untouched.  ``kv_store_paged`` writes such pools."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("tree_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D]")
     B, Hq, R, D = q.shape
-    if k.shape != v.shape or k.shape[0] != B or k.shape[3] != D:
+    if k.shape != v.shape or (block_table is None and k.shape[0] != B) or k.shape[3] != D:
         raise ValueError(f"tree_attention: k / v shapes {tuple(k.shape)}, {tuple(v.shape)} do not match q {tuple(q.shape)}")
     Hkv, L = k.shape[1], k.shape[2]
     dev = q.device
@@ -1380,7 +1511,7 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
         raise ValueError("tree_attention: q, k and v must share one floating dtype (or k, v float8_e4m3fn with scales)")
     if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
         raise ValueError("tree_attention: the head dimension must have unit stride")
-    ragged = torch.is_tensor(kv_len) or torch.is_tensor(win_base)
+    ragged = torch.is_tensor(kv_len) or torch.is_tensor(win_base) or block_table is not None
     if not ragged:
         if kv_cap is not None or chunk_tiles or kv_len_add or win_base_add or status_or is not None:
             raise ValueError("tree_attention: kv_cap, chunk_tiles, the addends and status_or go with a kv_len or "
@@ -1397,6 +1528,9 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
         out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
     elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
         raise ValueError(f"tree_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
+    if block_table is not None:
+        return _tree_attention_paged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles,
+                                     kv_len_add, win_base_add, status_or, workspace, scales, block_table)
     if ragged:
         return _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles,
                                       kv_len_add, win_base_add, status_or, workspace, scales)
@@ -1464,6 +1598,65 @@ def kv_store_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor
     a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
     a.status_or = _status_or_ptr(status_or, dev)
     _lib.check(lib.sd_kv_store_fp8(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_kv_store_fp8")
+
+
+def kv_store_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                   block_table: torch.Tensor, pos_dev: torch.Tensor, *, pos: int = 0,
+                   k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
+                   status_or: Optional[torch.Tensor] = None) -> None:
+    """Write a layer's new K and V rows into its paged pools, one launch for both (sd_kv_store_paged).
+
+    k_new, v_new: [B, H, R, D] bf16 or fp16 (unit stride along D).  k_cache, v_cache: pools [num_pages, H, S, D]
+    (or a permuted view of [P, S, H, D]), of k_new's dtype (the rows are copied) or ``torch.float8_e4m3fn`` with
+    ``k_scale`` / ``v_scale``, contiguous fp32 [H] (the rows are quantised to the bytes of ``kv_store_fp8``).
+    Row r of sequence b goes to logical position ``pos + pos_dev[b] + r`` (pos_dev: int64 [B] on the device),
+    slot ``p % S`` of page ``block_table[b, p // S]``.  A row whose position lies outside
+    ``[0, max_pages * S)`` or whose page id lies outside ``[0, num_pages)`` is not written and ORs
+    SD_ROW_INVALID_DIST into ``status_or``."""
+    if k_new.dim() != 4 or k_new.shape != v_new.shape or k_new.dtype != v_new.dtype:
+        raise ValueError("kv_store_paged: k_new and v_new must be [B, H, R, D] tensors of one shape and dtype")
+    B, H, R, D = k_new.shape
+    dev = k_new.device
+    if not k_new.is_cuda or k_new.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("kv_store_paged: k_new and v_new must be bf16 or fp16 device tensors")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[1] != H or k_cache.shape[3] != D:
+        raise ValueError(f"kv_store_paged: the pools must be [num_pages, {H}, S, {D}], got {tuple(k_cache.shape)}, "
+                         f"{tuple(v_cache.shape)}")
+    num_pages, S = k_cache.shape[0], k_cache.shape[2]
+    if S not in _PAGE_SIZES:
+        raise ValueError(f"kv_store_paged: page size {S} is not one of {_PAGE_SIZES}")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    for c in (k_cache, v_cache):
+        if c.dtype != k_cache.dtype or c.device != dev or (not fp8 and c.dtype != k_new.dtype):
+            raise ValueError(f"kv_store_paged: the pools must both be float8_e4m3fn or {k_new.dtype}, on {dev}")
+    for t in (k_new, v_new, k_cache, v_cache):
+        if t.stride(3) != 1:
+            raise ValueError("kv_store_paged: the head dimension must have unit stride")
+    if fp8:
+        for x in (k_scale, v_scale):
+            if x is None or x.dtype != torch.float32 or x.shape != (H,) or x.device != dev or not x.is_contiguous():
+                raise ValueError(f"kv_store_paged: float8_e4m3fn pools need contiguous float32 [{H}] k_scale and v_scale on {dev}")
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError("kv_store_paged: k_scale and v_scale go with float8_e4m3fn pools")
+    if pos_dev.dtype != torch.int64 or pos_dev.shape != (B,) or pos_dev.device != dev or not pos_dev.is_contiguous():
+        raise ValueError(f"kv_store_paged: pos_dev must be a contiguous int64 [{B}] on {dev}")
+    max_pages, bt_stride = _block_table(block_table, B, dev, "kv_store_paged")
+    es = k_cache.element_size()
+    a = _lib.sd_kv_store_paged_args()
+    a.batch, a.heads, a.rows, a.head_dim, a.dtype, a.cache_fp8 = B, H, R, D, _DT[k_new.dtype], int(fp8)
+    a.page_size, a.num_pages, a.max_pages = S, num_pages, max_pages
+    a.k_new, a.v_new, a.k_cache, a.v_cache = k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+    a.kn_stride_b, a.kn_stride_h, a.kn_stride_r = (k_new.stride(i) if k_new.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.vn_stride_b, a.vn_stride_h, a.vn_stride_r = (v_new.stride(i) if v_new.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.kn_stride_r, a.vn_stride_r = a.kn_stride_r or D, a.vn_stride_r or D
+    a.kc_stride_page, a.kc_stride_h, a.kc_stride_pos = (x * es for x in _pool_strides(k_cache))
+    a.vc_stride_page, a.vc_stride_h, a.vc_stride_pos = (x * es for x in _pool_strides(v_cache))
+    a.pos, a.pos_dev = int(pos), pos_dev.data_ptr()
+    a.block_table, a.block_table_stride_b = block_table.data_ptr(), bt_stride
+    if fp8:
+        a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_kv_store_paged(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_kv_store_paged")
 
 
 # --------------------------------------------------------------------------- n-gram verify (A11)

@@ -93,6 +93,12 @@ GPU), and callable as ``torch.ops.specdec.*``.
         The two attentions below over an FP8 cache with per-head dequantisation scales (sd_tree_attention_fp8,
         sd_tree_attention_ragged_fp8); torch.ops.specdec.kv_store_fp8(k_new, v_new, k_cache, v_cache, k_scale,
         v_scale, pos, pos_dev?) quantises new rows into such a cache in place (sd_kv_store_fp8).
+    torch.ops.specdec.tree_attention_paged(q, k, v pools [num_pages, Hkv, S, D], kv_limit, win_bits, win_base int64 [B],
+        kv_len int64 [B], block_table int32 [B, max_pages], k_scale?, v_scale?, ...), .kv_store_paged(k_new, v_new, k_cache,
+        v_cache, block_table, pos_dev, pos, k_scale?, v_scale?), .kv_compact_paged(tensors, path, count, base, num_slots,
+        block_table, base_dev, node_slot?)
+        The ragged attention, the store and the compaction over paged pools behind a device block table
+        (sd_tree_attention_paged, sd_kv_store_paged, sd_kv_compact_paged).
     torch.ops.specdec.tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base int64 [B], kv_len int64 [B], scale float?,
                                             kv_cap int?, chunk_tiles, kv_len_add, win_base_add) -> out [B, R, Hq, D]
         The same attention over a ragged batch (sd_tree_attention_ragged): sequence b's valid length
@@ -569,4 +575,47 @@ def kv_store_fp8(k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor,
 
 @kv_store_fp8.register_fake
 def _(k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos, pos_dev=None):
+    return None
+
+
+@torch.library.custom_op("specdec::tree_attention_paged", mutates_args=())
+def tree_attention_paged(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_bits: Tensor, win_base: Tensor,
+                         kv_len: Tensor, block_table: Tensor, k_scale: Optional[Tensor] = None,
+                         v_scale: Optional[Tensor] = None, scale: Optional[float] = None, kv_cap: Optional[int] = None,
+                         chunk_tiles: int = 0, kv_len_add: int = 0, win_base_add: int = 0) -> Tensor:
+    """ops.tree_attention over paged pools k, v [num_pages, Hkv, S, D] behind block_table int32 [B, max_pages]."""
+    return ops.tree_attention(q, k, v, kv_limit, win_bits, win_base, scale=scale, kv_len=kv_len, kv_cap=kv_cap,
+                              chunk_tiles=chunk_tiles, kv_len_add=kv_len_add, win_base_add=win_base_add,
+                              k_scale=k_scale, v_scale=v_scale, block_table=block_table)
+
+
+@tree_attention_paged.register_fake
+def _(q, k, v, kv_limit, win_bits, win_base, kv_len, block_table, k_scale=None, v_scale=None, scale=None, kv_cap=None,
+      chunk_tiles=0, kv_len_add=0, win_base_add=0):
+    B, Hq, R, D = q.shape
+    return q.new_empty(B, R, Hq, D)
+
+
+@torch.library.custom_op("specdec::kv_store_paged", mutates_args=("k_cache", "v_cache"))
+def kv_store_paged(k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor, pos_dev: Tensor,
+                   pos: int = 0, k_scale: Optional[Tensor] = None, v_scale: Optional[Tensor] = None) -> None:
+    """ops.kv_store_paged: the new K / V rows written (or quantised) into the paged pools in place."""
+    ops.kv_store_paged(k_new, v_new, k_cache, v_cache, block_table, pos_dev, pos=pos, k_scale=k_scale, v_scale=v_scale)
+
+
+@kv_store_paged.register_fake
+def _(k_new, v_new, k_cache, v_cache, block_table, pos_dev, pos=0, k_scale=None, v_scale=None):
+    return None
+
+
+@torch.library.custom_op("specdec::kv_compact_paged", mutates_args=("tensors",))
+def kv_compact_paged(tensors: List[Tensor], path: Tensor, count: Tensor, base: int, num_slots: int, block_table: Tensor,
+                     base_dev: Tensor, node_slot: Optional[List[int]] = None) -> None:
+    """ops.kv_compact over the paged pools of all layers, positions translated through block_table."""
+    ops.kv_compact(tensors, path, count, base, num_slots=num_slots, node_slot=node_slot, base_dev=base_dev,
+                   block_table=block_table)
+
+
+@kv_compact_paged.register_fake
+def _(tensors, path, count, base, num_slots, block_table, base_dev, node_slot=None):
     return None
