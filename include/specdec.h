@@ -1727,6 +1727,67 @@ typedef struct {
 
 int32_t sd_kv_compact_paged(const sd_kv_compact_paged_args* args, void* stream);
 
+/* ---- Prefill: causal "extend" attention over the same four cache forms (additive, ABI 12) ---------------
+ * sd_prefill_attention (csrc/prefill_attention.hip: k_pattn) is the attention of the forward that FILLS a
+ * cache — a prompt, or a chunk of one behind a cached prefix — for any number of new rows, whose K/V are
+ * already in the cache (written by sd_kv_store_fp8 / sd_kv_store_paged or by the model).  Per sequence b:
+ *
+ *     len_b = clamp((kv_len_dev ? kv_len_dev[b] : 0) + kv_len_add, 0, kv_cap)      valid keys, new rows counted
+ *     n_b   = clamp((rows_dev ? rows_dev[b] : 0) + rows_add, 0, min(rows, len_b))  new rows of the sequence
+ *
+ * A sum outside its range is clamped and ORs SD_ROW_INVALID_DIST into status_or.  Row r < n_b sits at position
+ * p = len_b - n_b + r and sees exactly the keys j <= p; row r >= n_b (padding on the right) gets zeros.  No key
+ * at or beyond len_b is loaded, and a sequence with n_b = 0 loads nothing.  Arithmetic as sd_tree_attention:
+ * fp32 accumulation, scale * log2(e) on the fp32 score, P rounded to `dtype` for the second product; kv_fp8
+ * nonzero: k / v are e4m3 bytes converted exactly at the MFMA operand, k_scale / v_scale (device fp32 [Hkv],
+ * required) applied in fp32 outside the products.  A sequence's result depends on its own inputs only.
+ *
+ * block_table null: k / v are [B, Hkv, kv_alloc, D] by k_stride_b / _h / _pos.  Non-null: k / v are pools
+ * [num_pages, Hkv, S, D] by k_stride_page / _h / _pos (k_stride_b unused) and position j is slot j & (S - 1) of
+ * page block_table[b * block_table_stride_b + (j >> log2 S)], S = page_size in {16, 32, 64, 128, 256}; entries
+ * at or beyond ceil(len_b / S) are not read, an id outside [0, num_pages) is never turned into an address (its
+ * keys read as zeros, SD_ROW_INVALID_DIST is ORed) and the pools are never written.
+ *
+ * One launch, grid (row blocks, Hkv, B); no workspace, no second kernel; capturable (lengths, row counts, table
+ * and scales are read when the kernel runs).  Limits: dtype bf16 / fp16, head_dim 64 or 128, heads_q a multiple
+ * of heads_kv with at most SD_TREE_ATTN_MAX_GROUP per K/V head, rows 1..SD_PREFILL_ATTN_MAX_ROWS, kv_cap
+ * 1..SD_TREE_ATTN_MAX_KV and <= kv_alloc (paged: <= max_pages * S); beyond them SD_ERR_UNSUPPORTED.  Pointers
+ * 16-byte aligned, strides non-negative multiples of 8 elements (k / v of e4m3: of 16), else SD_ERR_INVALID.
+ * Both are returned before anything is launched.                                                          */
+#define SD_PREFILL_ATTN_MAX_ROWS 65536
+
+typedef struct {
+    int32_t batch, heads_q, heads_kv, rows, head_dim;
+    int32_t dtype;               /* SD_BF16 or SD_F16, of q and out (and of k / v unless kv_fp8)      */
+    int32_t kv_cap;              /* upper bound of every len_b                                       */
+    int32_t kv_alloc;            /* allocated positions of a contiguous k / v (unused when paged)    */
+    int32_t kv_fp8;              /* nonzero: e4m3 k / v with k_scale / v_scale                        */
+    int32_t page_size;           /* S (paged only)                                                   */
+    int32_t num_pages;           /* pages of the pools: valid ids are 0..num_pages - 1               */
+    int32_t max_pages;           /* entries of a block-table row                                     */
+    float scale;
+    const void* q;               /* [B, Hq, R, D] by the three strides below                         */
+    int64_t q_stride_b, q_stride_h, q_stride_r;
+    const void* k;
+    const void* v;
+    int64_t k_stride_b, k_stride_h, k_stride_pos;           /* _h and _pos also inside a page        */
+    int64_t v_stride_b, v_stride_h, v_stride_pos;
+    int64_t k_stride_page, v_stride_page;                   /* paged only                            */
+    void* out;                   /* [B, R, Hq, D] by the three strides below                         */
+    int64_t out_stride_b, out_stride_r, out_stride_h;
+    const float* k_scale;        /* device fp32 [Hkv], kv_fp8 only                                    */
+    const float* v_scale;
+    const int32_t* block_table;  /* nullable (contiguous); device int32 [B, max_pages]               */
+    int64_t block_table_stride_b;/* >= max_pages                                                     */
+    const int64_t* kv_len_dev;   /* nullable, device int64 [B]                                       */
+    int64_t kv_len_add;
+    const int64_t* rows_dev;     /* nullable, device int64 [B]                                       */
+    int64_t rows_add;
+    int32_t* status_or;          /* nullable                                                         */
+} sd_prefill_attention_args;
+
+int32_t sd_prefill_attention(const sd_prefill_attention_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

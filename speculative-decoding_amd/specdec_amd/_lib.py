@@ -93,7 +93,7 @@ EXPORTS = ("sd_abi_version", "sd_status_string", "sd_last_hip_error", "sd_verify
            "sd_tree_attention_splits", "sd_tree_attention_workspace_size", "sd_tree_attention",
            "sd_tree_attention_ragged_chunks", "sd_tree_attention_ragged_workspace_size", "sd_tree_attention_ragged",
            "sd_tree_attention_fp8", "sd_tree_attention_ragged_fp8", "sd_kv_store_fp8",
-           "sd_tree_attention_paged", "sd_kv_store_paged", "sd_kv_compact_paged")
+           "sd_tree_attention_paged", "sd_kv_store_paged", "sd_kv_compact_paged", "sd_prefill_attention")
 
 # vocabulary-parallel verify
 SD_VP_MAX_SHARDS, SD_VP_MAX_BATCH, SD_VP_MAX_VOCAB_LOCAL = 64, 1024, 2097152
@@ -118,6 +118,7 @@ SD_KV_MAX_TENSORS = 256
 
 # tree attention (sd_tree_attention)
 SD_TREE_ATTN_MAX_ROWS, SD_TREE_ATTN_MAX_GROUP, SD_TREE_ATTN_MAX_SPLITS, SD_TREE_ATTN_MAX_KV = 128, 8, 64, 1 << 20
+SD_PREFILL_ATTN_MAX_ROWS = 65536       # rows of one sd_prefill_attention call
 
 # beam step (ABI 12)
 SD_BEAM_MAX_BEAMS, SD_BEAM_MAX_TOPK, SD_BEAM_MAX_CANDIDATES, SD_BEAM_MAX_VOCAB = 64, 64, 1024, 524288
@@ -497,6 +498,27 @@ class sd_kv_compact_paged_args(C.Structure):
     ]
 
 
+# causal prefill / extend attention over a contiguous or paged cache (block_table null: contiguous)
+class sd_prefill_attention_args(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("heads_q", C.c_int32), ("heads_kv", C.c_int32), ("rows", C.c_int32),
+        ("head_dim", C.c_int32), ("dtype", C.c_int32), ("kv_cap", C.c_int32), ("kv_alloc", C.c_int32),
+        ("kv_fp8", C.c_int32), ("page_size", C.c_int32), ("num_pages", C.c_int32), ("max_pages", C.c_int32),
+        ("scale", C.c_float),
+        ("q", C.c_void_p), ("q_stride_b", C.c_int64), ("q_stride_h", C.c_int64), ("q_stride_r", C.c_int64),
+        ("k", C.c_void_p), ("v", C.c_void_p),
+        ("k_stride_b", C.c_int64), ("k_stride_h", C.c_int64), ("k_stride_pos", C.c_int64),
+        ("v_stride_b", C.c_int64), ("v_stride_h", C.c_int64), ("v_stride_pos", C.c_int64),
+        ("k_stride_page", C.c_int64), ("v_stride_page", C.c_int64),
+        ("out", C.c_void_p), ("out_stride_b", C.c_int64), ("out_stride_r", C.c_int64), ("out_stride_h", C.c_int64),
+        ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+        ("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64),
+        ("kv_len_dev", C.c_void_p), ("kv_len_add", C.c_int64),
+        ("rows_dev", C.c_void_p), ("rows_add", C.c_int64),
+        ("status_or", C.c_void_p),
+    ]
+
+
 class sd_vp_header(C.Structure):
     _fields_ = [("magic", C.c_int32), ("shard", C.c_int32), ("num_shards", C.c_int32), ("vocab_offset", C.c_int32),
                 ("vocab_local", C.c_int32), ("vocab", C.c_int32), ("batch", C.c_int32), ("gamma", C.c_int32)]
@@ -636,6 +658,8 @@ def _load():
     lib.sd_kv_store_paged.argtypes = [C.POINTER(sd_kv_store_paged_args), C.c_void_p]
     lib.sd_kv_compact_paged.restype = C.c_int32
     lib.sd_kv_compact_paged.argtypes = [C.POINTER(sd_kv_compact_paged_args), C.c_void_p]
+    lib.sd_prefill_attention.restype = C.c_int32
+    lib.sd_prefill_attention.argtypes = [C.POINTER(sd_prefill_attention_args), C.c_void_p]
     lib.sd_tree_grow_workspace_size.restype = C.c_size_t
     lib.sd_tree_grow_workspace_size.argtypes = [C.c_int32] * 5
     lib.sd_tree_grow.restype = C.c_int32

@@ -1551,6 +1551,95 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     return out
 
 
+def _per_sequence(x, B: int, dev, who: str):
+    """(device pointer or None, host addend, tensor kept alive) of an int or an int64 device tensor [B]."""
+    if not torch.is_tensor(x):
+        return None, int(x), None
+    if x.dtype != torch.int64 or x.shape != (B,) or x.device != dev or not x.is_contiguous():
+        raise ValueError(f"prefill_attention: a {who} tensor must be a contiguous int64 [{B}] on {dev}")
+    return x.data_ptr(), 0, x
+
+
+def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_len, *, rows=None,
+                      kv_cap: Optional[int] = None, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                      status_or: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None,
+                      k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
+                      kv_len_add: int = 0, rows_add: int = 0) -> torch.Tensor:
+    """Causal attention of the forward that fills a cache (sd_prefill_attention, one MFMA kernel): a prompt, or a
+    chunk of one behind a cached prefix, of any number of rows.
+
+    q: [B, Hq, R, D], bf16 or fp16.  k, v: the cache WITH the new rows' K/V already in it — [B, Hkv, L, D] of q's
+    dtype or ``float8_e4m3fn`` (then with ``k_scale`` / ``v_scale``, fp32 [Hkv] on the device), or, with
+    ``block_table`` (int32 [B, max_pages]), pools [num_pages, Hkv, S, D] read as ``tree_attention(...,
+    block_table=)`` reads them.  ``kv_len``: sequence b's valid keys, the new rows counted; ``rows`` (default R):
+    how many of the R rows are its own, the rest being padding on the right.  Each is an int (for the whole
+    batch) or an int64 device tensor [B] read when the kernel runs, plus the host addend ``kv_len_add`` /
+    ``rows_add``; both are clamped (kv_len to ``kv_cap``, default L or ``max_pages * S``; rows to
+    ``min(R, kv_len)``) and a clamped value ORs SD_ROW_INVALID_DIST into ``status_or`` (int32 [1]).
+
+    Row r < rows_b sits at position ``kv_len_b - rows_b + r`` and sees the keys at or below it.  Returns ``out``
+    [B, R, Hq, D]; padding rows are zeros.  No key at or beyond kv_len_b is read, no workspace is used and the
+    call is capturable.  A page id outside [0, num_pages) is never used as an address: its keys count as zeros
+    and SD_ROW_INVALID_DIST is ORed."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("prefill_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D] (or pools [P, Hkv, S, D])")
+    B, Hq, R, D = q.shape
+    if k.shape != v.shape or (block_table is None and k.shape[0] != B) or k.shape[3] != D:
+        raise ValueError(f"prefill_attention: k / v shapes {tuple(k.shape)}, {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    Hkv, L, dev = k.shape[1], k.shape[2], q.device
+    if not q.is_cuda or k.device != dev or v.device != dev:
+        raise ValueError("prefill_attention: q, k and v must be tensors of one device")
+    fp8 = k.dtype == torch.float8_e4m3fn and v.dtype == torch.float8_e4m3fn
+    if q.dtype not in _DT or q.dtype == torch.float32:
+        raise ValueError("prefill_attention: q must be bfloat16 or float16")
+    if fp8:
+        for x in (k_scale, v_scale):
+            if x is None or x.dtype != torch.float32 or x.shape != (Hkv,) or x.device != dev or not x.is_contiguous():
+                raise ValueError(f"prefill_attention: float8_e4m3fn k / v need contiguous float32 [{Hkv}] k_scale and v_scale on {dev}")
+    elif k_scale is not None or v_scale is not None or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("prefill_attention: k and v must have q's dtype, or be float8_e4m3fn with k_scale and v_scale")
+    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
+        raise ValueError("prefill_attention: the head dimension must have unit stride")
+    if out is None:
+        out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
+    elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
+        raise ValueError(f"prefill_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
+    a = _lib.sd_prefill_attention_args()
+    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype, a.kv_fp8 = B, Hq, Hkv, R, D, _DT[q.dtype], int(fp8)
+    if block_table is not None:
+        if L not in _PAGE_SIZES:
+            raise ValueError(f"prefill_attention: page size {L} is not one of {_PAGE_SIZES}")
+        a.max_pages, a.block_table_stride_b = _block_table(block_table, B, dev, "prefill_attention")
+        a.page_size, a.num_pages, a.block_table = L, k.shape[0], block_table.data_ptr()
+        limit = min(a.max_pages * L, _lib.SD_TREE_ATTN_MAX_KV)
+        a.k_stride_page, a.k_stride_h, a.k_stride_pos = _pool_strides(k)
+        a.v_stride_page, a.v_stride_h, a.v_stride_pos = _pool_strides(v)
+    else:
+        limit = a.kv_alloc = L
+        a.k_stride_b, a.k_stride_h, a.k_stride_pos = (k.stride(i) if k.shape[i] > 1 else 0 for i in (0, 1, 2))
+        a.v_stride_b, a.v_stride_h, a.v_stride_pos = (v.stride(i) if v.shape[i] > 1 else 0 for i in (0, 1, 2))
+        a.k_stride_pos, a.v_stride_pos = a.k_stride_pos or D, a.v_stride_pos or D
+    a.kv_cap = limit if kv_cap is None else int(kv_cap)
+    if not 1 <= a.kv_cap <= limit:
+        raise ValueError(f"prefill_attention: kv_cap {a.kv_cap} outside 1..{limit}")
+    a.scale = float(D) ** -0.5 if scale is None else float(scale)
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    # a dimension of size 1 may carry any stride: it is never stepped along
+    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.q_stride_r = a.q_stride_r or D
+    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
+    a.out_stride_h = a.out_stride_h or D
+    if fp8:
+        a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
+    a.kv_len_dev, len_add, keep_len = _per_sequence(kv_len, B, dev, "kv_len")
+    a.rows_dev, n_add, keep_rows = _per_sequence(R if rows is None else rows, B, dev, "rows")
+    a.kv_len_add, a.rows_add = len_add + int(kv_len_add), n_add + int(rows_add)
+    a.status_or = _status_or_ptr(status_or, dev)
+    _lib.check(lib.sd_prefill_attention(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_prefill_attention")
+    del keep_len, keep_rows
+    return out
+
+
 def kv_store_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  k_scale: torch.Tensor, v_scale: torch.Tensor, pos: int, *, pos_dev: Optional[torch.Tensor] = None,
                  status_or: Optional[torch.Tensor] = None) -> None:

@@ -99,6 +99,10 @@ GPU), and callable as ``torch.ops.specdec.*``.
         block_table, base_dev, node_slot?)
         The ragged attention, the store and the compaction over paged pools behind a device block table
         (sd_tree_attention_paged, sd_kv_store_paged, sd_kv_compact_paged).
+    torch.ops.specdec.prefill_attention(q [B, Hq, R, D], k, v (cache or pools), kv_len int64 [B]?, rows int64 [B]?, kv_len_add,
+                                        rows_add, scale float?, kv_cap int?, block_table?, k_scale?, v_scale?) -> out [B, R, Hq, D]
+        Causal attention of the rows that fill a cache (sd_prefill_attention): row r of sequence b sits at position
+        kv_len_b - rows_b + r and sees the keys at or below it; contiguous or paged, 16-bit or float8_e4m3fn.
     torch.ops.specdec.tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base int64 [B], kv_len int64 [B], scale float?,
                                             kv_cap int?, chunk_tiles, kv_len_add, win_base_add) -> out [B, R, Hq, D]
         The same attention over a ragged batch (sd_tree_attention_ragged): sequence b's valid length
@@ -592,6 +596,25 @@ def tree_attention_paged(q: Tensor, k: Tensor, v: Tensor, kv_limit: Tensor, win_
 @tree_attention_paged.register_fake
 def _(q, k, v, kv_limit, win_bits, win_base, kv_len, block_table, k_scale=None, v_scale=None, scale=None, kv_cap=None,
       chunk_tiles=0, kv_len_add=0, win_base_add=0):
+    B, Hq, R, D = q.shape
+    return q.new_empty(B, R, Hq, D)
+
+
+@torch.library.custom_op("specdec::prefill_attention", mutates_args=())
+def prefill_attention(q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                      kv_len_add: int = 0, rows_add: int = 0, scale: Optional[float] = None, kv_cap: Optional[int] = None,
+                      block_table: Optional[Tensor] = None, k_scale: Optional[Tensor] = None,
+                      v_scale: Optional[Tensor] = None) -> Tensor:
+    """ops.prefill_attention: causal attention of the rows that fill a cache, out [B, R, Hq, D].  Sequence b has
+    kv_len[b] + kv_len_add keys and rows[b] + rows_add new rows; a tensor left out counts as zeros."""
+    return ops.prefill_attention(q, k, v, 0 if kv_len is None else kv_len, rows=0 if rows is None else rows, kv_cap=kv_cap,
+                                 scale=scale, block_table=block_table, k_scale=k_scale, v_scale=v_scale,
+                                 kv_len_add=kv_len_add, rows_add=rows_add)
+
+
+@prefill_attention.register_fake
+def _(q, k, v, kv_len=None, rows=None, kv_len_add=0, rows_add=0, scale=None, kv_cap=None, block_table=None, k_scale=None,
+      v_scale=None):
     B, Hq, R, D = q.shape
     return q.new_empty(B, R, Hq, D)
 

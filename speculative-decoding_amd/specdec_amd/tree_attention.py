@@ -8,6 +8,8 @@ GQA group read one K/V stream, and transformers builds no mask at all.  Outside 
 behaves as the stock ``"sdpa"`` attention with the stock mask, so switching a model to it is harmless.
 ``descriptors_ragged`` is the same for a batch of sequences of different lengths: per-sequence device
 tensors for the window base and the valid length, read by sd_tree_attention_ragged when it runs.
+``causal(model, kv_len, ...)`` takes the plain causal forwards (a prompt, or a chunk of one behind a cached
+prefix; any number of rows) through ``ops.prefill_attention`` (sd_prefill_attention) instead.
 
     dsc = row_descriptors(tree, cur, start, nodes, col_of)          # host lists, no [R, width] tensor
     if supported(model, len(dsc.kv_limit)):
@@ -49,6 +51,7 @@ class _Active:
     kv_cap: Optional[int] = None   # descriptors_ragged: the host's bound on every length
     k_scale: Optional[torch.Tensor] = None   # fp32 [Hkv]: the dequantisation scales of an FP8 cache, used when
     v_scale: Optional[torch.Tensor] = None   # the `key` an attention call receives is float8_e4m3fn
+    causal: bool = False           # under `causal`: no descriptors, the rows are the last ones of kv_len
 
 
 _active: Optional[_Active] = None
@@ -65,10 +68,11 @@ def row_descriptors(tr, cur: int, start: int, nodes, col_of) -> RowDescriptors:
     return RowDescriptors(limit, bits, cur)
 
 
-def supported(model, rows: int) -> bool:
+def supported(model, rows: int, max_rows: int = _lib.SD_TREE_ATTN_MAX_ROWS) -> bool:
     """Whether a forward of `rows` new tokens through `model` can take the kernel: a transformers model
     (its attention goes through the interface) of a 16-bit dtype with head_dim 64 or 128, at most
-    SD_TREE_ATTN_MAX_GROUP query heads per K/V head and at most SD_TREE_ATTN_MAX_ROWS rows."""
+    SD_TREE_ATTN_MAX_GROUP query heads per K/V head and at most SD_TREE_ATTN_MAX_ROWS rows (max_rows:
+    SD_PREFILL_ATTN_MAX_ROWS asks the same of a forward under ``causal``)."""
     cfg = getattr(model, "config", None)
     heads = getattr(cfg, "num_attention_heads", None)
     if cfg is None or not heads or not hasattr(cfg, "_attn_implementation"):
@@ -77,7 +81,7 @@ def supported(model, rows: int) -> bool:
     head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // heads
     return (getattr(model, "dtype", None) in (torch.bfloat16, torch.float16) and head_dim in (64, 128)
             and heads % kv_heads == 0 and heads // kv_heads <= _lib.SD_TREE_ATTN_MAX_GROUP
-            and 1 <= rows <= _lib.SD_TREE_ATTN_MAX_ROWS and register())
+            and 1 <= rows <= max_rows and register())
 
 
 @contextmanager
@@ -123,6 +127,25 @@ def descriptors_ragged(model, kv_limit: torch.Tensor, win_bits: torch.Tensor, wi
         _active = outer
 
 
+@contextmanager
+def causal(model, kv_len: int, device, k_scale=None, v_scale=None):
+    """Run the plain causal forwards inside on sd_prefill_attention (batch 1): `model`'s attention implementation
+    is "specdec_tree" for the block, no mask is built, and the R rows of every attention call are the last R of
+    the first `kv_len` cache positions — a prompt (kv_len = R) or a chunk behind a cached prefix.  Any R up to
+    SD_PREFILL_ATTN_MAX_ROWS.  k_scale, v_scale: as for ``descriptors``."""
+    global _active
+    if not register():
+        raise RuntimeError("specdec_amd.tree_attention needs a transformers with AttentionInterface")
+    cfg, before, outer = model.config, model.config._attn_implementation, _active
+    _active = _Active(None, None, 0, int(kv_len), k_scale=k_scale, v_scale=v_scale, causal=True)
+    cfg._attn_implementation = NAME
+    try:
+        yield
+    finally:
+        cfg._attn_implementation = before
+        _active = outer
+
+
 def _attention(module, query, key, value, attention_mask, scaling=None, dropout=0.0, **kwargs):
     """The ``AttentionInterface`` entry.  With descriptors: the kernel, out [B, R, Hq, D].  Without: the
     stock sdpa attention with the mask it was given."""
@@ -132,7 +155,12 @@ def _attention(module, query, key, value, attention_mask, scaling=None, dropout=
         counts["stock"] += 1
         return ALL_ATTENTION_FUNCTIONS["sdpa"](module, query, key, value, attention_mask, scaling=scaling,
                                                dropout=dropout, **kwargs)
-    if key.dtype == torch.float8_e4m3fn:
+    if d.causal:
+        if key.dtype == torch.float8_e4m3fn and (d.k_scale is None or d.v_scale is None):
+            raise RuntimeError("specdec_tree: an FP8 key needs k_scale and v_scale")
+        scales = dict(k_scale=d.k_scale, v_scale=d.v_scale) if key.dtype == torch.float8_e4m3fn else {}
+        out = ops.prefill_attention(query, key, value, d.kv_len, scale=scaling, **scales)
+    elif key.dtype == torch.float8_e4m3fn:
         if d.k_scale is None or d.v_scale is None:
             raise RuntimeError("specdec_tree: an FP8 key needs descriptors with k_scale and v_scale")
         if d.kv_cap is not None:
