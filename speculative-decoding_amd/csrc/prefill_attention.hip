@@ -29,7 +29,7 @@
 //       publishes the current tile: no thread still reads the old ids there (their last reader was the prefetch
 //       of the tile now in LDS), so it costs one extra barrier and one exposed table read per 1024 pages.  A
 //       lookup is an unconditional LDS read and a select between two BYTE OFFSETS from one base (a refused id:
-//       the offset of pa_zero_row), never between pointers.  The pools are read only.
+//       the offset of ta_zero_row; ta_page_row, csrc/tattn_common.h), never between pointers.  The pools are read only.
 // status_or is the one word several workgroups may write; it is ORed with atomicOr like every entry's.  The launch
 // boundary is the only synchronisation.
 #include "sd_device.h"
@@ -57,8 +57,6 @@ struct PaParams {
     int32_t rows, group, rb_shift, kv_cap, num_pages, page_shift;
     float scale_log2;                  // scale * log2(e): the softmax runs in base 2
 };
-
-__device__ const ta_u32x4 pa_zero_row[16] = {};      // a K/V row of zeros: D <= 128 elements of <= 2 bytes
 
 template <int DT, int D, bool FP8, bool PAGED>
 __global__ void __launch_bounds__(kTaThreads) k_pattn(PaParams P) {
@@ -163,9 +161,7 @@ __global__ void __launch_bounds__(kTaThreads) k_pattn(PaParams P) {
     auto kv_row = [&](const KV* head, int32_t kj, int64_t ps, int64_t sp) -> const KV* {
         if constexpr (PAGED) {
             const int32_t id = s_pg[(kj >> P.page_shift) & (kPaPgWindow - 1)];     // unconditional: see the header
-            const int64_t in_pool = (id * ps + (kj & ((1 << P.page_shift) - 1)) * sp) * (int64_t)sizeof(KV);
-            const int64_t to_zero = (int64_t)(reinterpret_cast<uintptr_t>(pa_zero_row) - reinterpret_cast<uintptr_t>(head));
-            return reinterpret_cast<const KV*>(reinterpret_cast<const char*>(head) + (id < 0 ? to_zero : in_pool));
+            return ta_page_row(head, id, kj, P.page_shift, ps, sp);
         } else {
             return head + kj * sp;
         }
@@ -386,44 +382,24 @@ extern "C" int32_t sd_prefill_attention(const sd_prefill_attention_args* a, void
     if (!a) return SD_ERR_INVALID;
     if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
     if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;
-    if (a->batch < 1 || a->heads_q < 1 || a->heads_kv < 1 || a->rows < 1 || a->head_dim < 1 || a->kv_cap < 1)
-        return SD_ERR_INVALID;
-    if (a->heads_q % a->heads_kv) return SD_ERR_INVALID;
-    if (a->head_dim != 64 && a->head_dim != 128) return SD_ERR_UNSUPPORTED;
-    if (a->heads_q / a->heads_kv > SD_TREE_ATTN_MAX_GROUP || a->rows > SD_PREFILL_ATTN_MAX_ROWS) return SD_ERR_UNSUPPORTED;
-    if (a->kv_cap > SD_TREE_ATTN_MAX_KV) return SD_ERR_UNSUPPORTED;
-    if (a->batch > 65535 || a->heads_kv > 65535) return SD_ERR_UNSUPPORTED;       // grid.z, grid.y
+    int32_t st = sd::ta_check_dims(a->batch, a->heads_q, a->heads_kv, a->rows, SD_PREFILL_ATTN_MAX_ROWS, a->head_dim, a->kv_cap);
+    if (st != SD_OK) return st;
     const bool paged = a->block_table != nullptr;
     int shift = 0;
     if (paged) {
-        while (shift < 9 && (1 << shift) != a->page_size) ++shift;
-        if (shift < 4 || shift > 8) return SD_ERR_INVALID;               // 16, 32, 64, 128, 256
-        if (a->num_pages < 1 || a->max_pages < 1 || a->block_table_stride_b < a->max_pages) return SD_ERR_INVALID;
-        if (a->kv_cap > (int64_t)a->max_pages * a->page_size) return SD_ERR_INVALID;
-        if (reinterpret_cast<uintptr_t>(a->block_table) & 3) return SD_ERR_INVALID;
+        if ((st = sd::ta_check_pool(a->page_size, a->num_pages, a->max_pages, &shift)) != SD_OK) return st;
+        st = sd::ta_check_table(a->block_table, a->block_table_stride_b, a->max_pages, a->page_size, a->kv_cap);
+        if (st != SD_OK) return st;
     } else if (a->kv_alloc < a->kv_cap) {
         return SD_ERR_INVALID;
     }
-    if (!a->q || !a->k || !a->v || !a->out) return SD_ERR_INVALID;
-    if (!(a->scale == a->scale)) return SD_ERR_INVALID;
-    // 16-byte accesses: every address the kernel forms is a multiple of 16 bytes (8 elements, 16 e4m3 bytes)
-    const int64_t k_sb = paged ? a->k_stride_page : a->k_stride_b, v_sb = paged ? a->v_stride_page : a->v_stride_b;
-    const int64_t qo[] = {a->q_stride_b, a->q_stride_h, a->q_stride_r, a->out_stride_b, a->out_stride_r, a->out_stride_h};
-    for (int64_t s : qo)
-        if (s < 0 || (s & 7)) return SD_ERR_INVALID;
-    const int64_t kv[] = {k_sb, a->k_stride_h, a->k_stride_pos, v_sb, a->v_stride_h, a->v_stride_pos};
-    for (int64_t s : kv)
-        if (s < 0 || (s & (a->kv_fp8 ? 15 : 7))) return SD_ERR_INVALID;
-    if (a->q_stride_r < a->head_dim || a->k_stride_pos < a->head_dim || a->v_stride_pos < a->head_dim ||
-        a->out_stride_h < a->head_dim)
-        return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
-         reinterpret_cast<uintptr_t>(a->out)) & 15)
-        return SD_ERR_INVALID;
-    if (a->kv_fp8) {
-        if (!a->k_scale || !a->v_scale) return SD_ERR_INVALID;
-        if ((reinterpret_cast<uintptr_t>(a->k_scale) | reinterpret_cast<uintptr_t>(a->v_scale)) & 3) return SD_ERR_INVALID;
-    }
+    // the page strides in the place of the batch strides
+    const sd::TaTensors t{a->q, a->k, a->v, a->out, a->q_stride_b, a->q_stride_h, a->q_stride_r,
+                          paged ? a->k_stride_page : a->k_stride_b, a->k_stride_h, a->k_stride_pos,
+                          paged ? a->v_stride_page : a->v_stride_b, a->v_stride_h, a->v_stride_pos,
+                          a->out_stride_b, a->out_stride_r, a->out_stride_h};
+    if ((st = sd::ta_check_tensors(t, a->head_dim, a->scale)) != SD_OK) return st;
+    if (a->kv_fp8 && (st = sd::ta_check_fp8(t, a->k_scale, a->v_scale)) != SD_OK) return st;
     if ((reinterpret_cast<uintptr_t>(a->kv_len_dev) | reinterpret_cast<uintptr_t>(a->rows_dev)) & 7) return SD_ERR_INVALID;
     if (reinterpret_cast<uintptr_t>(a->status_or) & 3) return SD_ERR_INVALID;
 

@@ -1,9 +1,9 @@
 // tattn_fp8_tile.inc — the body of a tree-attention partial kernel over a KV cache stored as OCP e4m3 bytes,
-// included once by k_tattn_fp8_partial and once by k_tattn_fp8_ragged_partial (csrc/tree_attention.hip), as
-// tattn_tile.inc is by the 16-bit kernels.  The including kernel has `TaParams P` and `TaFp8 Fs` in scope,
-// blockIdx = (partial slot, K/V head, sequence), and defines TA_KV_LEN, TA_WIN_BASE, TA_T_BEGIN and TA_T_END
-// as for tattn_tile.inc.  Wave ownership, the two products and the one-tile-ahead prefetch are those of the
-// 16-bit body; what differs is the way of K and V from memory to the MFMA operands:
+// included once by each of k_tattn_fp8_partial, k_tattn_fp8_ragged_partial and k_tattn_fp8_paged_partial
+// (csrc/tree_attention.hip), as tattn_tile.inc is by the 16-bit kernels.  The including kernel has in scope what
+// tattn_tile.inc asks for (`rows` addressing bytes) and `TaFp8 Fs`.  Wave ownership, the two products and the
+// one-tile-ahead prefetch are those of the 16-bit body; what differs is the way of K and V from memory to the
+// MFMA operands:
 //   registers   a thread prefetches KL = D / 64 16-byte chunks of K (16 values each) and, the first D
 //               threads only, the same 16-byte chunk of the FOUR keys of a key quad of V.
 //   LDS         K [64][D] as bytes, rows padded by 8 bytes: a row is D / 8 + 1 (odd) 8-byte units, so the 32
@@ -17,13 +17,6 @@
 //               (keys 16s + 4half + e and 16s + 8 + 4half + e) are one A fragment of the second.
 // The dequantisation scales never enter a product: k_scale[hkv] is folded into the fp32 score factor and
 // v_scale[hkv] multiplies the fp32 accumulators where the result is written (out, or part_o).
-// The address of a K or V row is formed in one place each, through TA_K_ROW(kj) / TA_V_ROW(kj), which the
-// including kernel may define (the paged kernels do); the default is the contiguous cache's.
-#ifndef TA_K_ROW
-#define TA_K_ROW(kj) kb + kj * P.k_sp
-#define TA_V_ROW(kj) vb + kj * P.v_sp
-#define TA_ROW_DEFAULT
-#endif
     using T = TaType<DT>;
     using E = typename T::elem;
     using V8 = typename T::vec8;
@@ -42,7 +35,6 @@
     const int half = lane >> 5, col = lane & 31;
     const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
     const int R = P.rows, G = P.group, M = R * G;
-    const int64_t win_base = TA_WIN_BASE;
     const float score_scale = P.scale_log2 * Fs.k_scale[hkv];     // read when the kernel runs
     const float v_scale = Fs.v_scale[hkv];
 
@@ -52,8 +44,8 @@
         uint64_t bits = 0;
         if (tid < R) {
             lim = P.kv_limit[(int64_t)b * R + tid];
-            lim = lim < 0 ? 0 : (lim > TA_KV_LEN ? TA_KV_LEN : lim);
-            bits = P.win_bits[(int64_t)b * R + tid] & ta_range_mask(-win_base, (int64_t)TA_KV_LEN - win_base);
+            lim = lim < 0 ? 0 : (lim > kv_len ? kv_len : lim);
+            bits = P.win_bits[(int64_t)b * R + tid] & ta_range_mask(-win_base, (int64_t)kv_len - win_base);
         }
         s_lim[tid] = lim;
         s_bits[tid] = bits;
@@ -68,9 +60,8 @@
     const int32_t any_lim = s_any_lim[0] > s_any_lim[1] ? s_any_lim[0] : s_any_lim[1];
     const uint64_t any_bits = s_any_bits[0] | s_any_bits[1];
 
-    const int n_tiles = (TA_KV_LEN + kTaTile - 1) / kTaTile;
-    const int t_begin = TA_T_BEGIN;
-    const int t_end = TA_T_END;
+    const int n_tiles = (kv_len + kTaTile - 1) / kTaTile;
+    const int t_begin = span.begin(n_tiles), t_end = span.end(n_tiles);
     // the first tile at or after t that some row of the sequence can see (t_end: none)
     auto next_tile = [&](int t) {
         for (; t < t_end; ++t) {
@@ -95,7 +86,7 @@
             const int32_t kj = t * kTaTile + key;
             kreg[it] = zero4;
             if (ta_visible(kj, any_lim, any_bits, win_base))
-                kreg[it] = *reinterpret_cast<const ta_u32x4*>(TA_K_ROW(kj) + c * 16);
+                kreg[it] = *reinterpret_cast<const ta_u32x4*>(rows.k(kb, kj) + c * 16);
         }
         if (v_loader) {
 #pragma unroll
@@ -103,7 +94,7 @@
                 const int32_t kj = t * kTaTile + 4 * vq + e;
                 vreg[e] = zero4;
                 if (ta_visible(kj, any_lim, any_bits, win_base))
-                    vreg[e] = *reinterpret_cast<const ta_u32x4*>(TA_V_ROW(kj) + vc * 16);
+                    vreg[e] = *reinterpret_cast<const ta_u32x4*>(rows.v(vb, kj) + vc * 16);
             }
         }
     };
@@ -267,8 +258,3 @@
             }
         }
     }
-#ifdef TA_ROW_DEFAULT
-#undef TA_K_ROW
-#undef TA_V_ROW
-#undef TA_ROW_DEFAULT
-#endif

@@ -1,18 +1,17 @@
-// tattn_tile.inc — the body of a tree-attention partial kernel, included once by k_tattn_partial and once by
-// k_tattn_ragged_partial (csrc/tree_attention.hip), so that each kernel is compiled from its own copy and
-// the first one's code does not depend on the second's existence.  The including kernel has `TaParams P`
-// in scope, blockIdx = (partial slot, K/V head, sequence), and defines
-//     TA_KV_LEN     the sequence's valid length (int32)
-//     TA_WIN_BASE   the position of bit 0 of its window words (int64)
-//     TA_T_BEGIN, TA_T_END   the workgroup's 64-key tiles, from `split` (= blockIdx.x) and `n_tiles`
-// The result goes to `out` (P.part_ml null) or to the workspace as partial `split` of P.splits.
-// The address of a K or V row is formed in one place each, through TA_K_ROW(kj) / TA_V_ROW(kj), which the
-// including kernel may define (the paged kernels do); the default is the contiguous cache's.
-#ifndef TA_K_ROW
-#define TA_K_ROW(kj) kb + kj * P.k_sp
-#define TA_V_ROW(kj) vb + kj * P.v_sp
-#define TA_ROW_DEFAULT
-#endif
+// tattn_tile.inc — the body of a tree-attention partial kernel over a 16-bit cache, included once by each of
+// k_tattn_partial, k_tattn_ragged_partial and k_tattn_paged_partial (csrc/tree_attention.hip), so that each kernel
+// is compiled from its own copy and one kernel's code does not depend on another's existence.  (As a force-inlined
+// function the same text costs the D = 64 kernels four VGPRs: DESIGN.md §4i.)  It has no parameters of its own
+// and no macros: it reads ordinary names of the including kernel, which has blockIdx = (partial slot, K/V head,
+// sequence), the template arguments DT and D, and in scope
+//     TaParams P
+//     int32_t kv_len     the sequence's valid length
+//     int64_t win_base   the position of bit 0 of its window words
+//     span               the workgroup's 64-key tiles [span.begin(n_tiles), span.end(n_tiles)), asked for behind
+//                        the first barrier: TaSplitSpan or TaChunkSpan
+//     rows               the address of a K or V row, rows.k(kb, kj) / rows.v(vb, kj), kb / vb being P.k / P.v moved
+//                        to the sequence and the K/V head: TaFlatRows for a contiguous cache, TaPagedRows for a pool
+// The result goes to `out` (P.part_ml null) or to the workspace as partial blockIdx.x of P.splits.
     using T = TaType<DT>;
     using E = typename T::elem;
     using V8 = typename T::vec8;
@@ -32,7 +31,6 @@
     const int half = lane >> 5, col = lane & 31;
     const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
     const int R = P.rows, G = P.group, M = R * G;
-    const int64_t win_base = TA_WIN_BASE;
 
     // the rows' descriptors, clamped to the valid keys, and their union over the sequence
     if (tid < SD_TREE_ATTN_MAX_ROWS) {
@@ -40,8 +38,8 @@
         uint64_t bits = 0;
         if (tid < R) {
             lim = P.kv_limit[(int64_t)b * R + tid];
-            lim = lim < 0 ? 0 : (lim > TA_KV_LEN ? TA_KV_LEN : lim);
-            bits = P.win_bits[(int64_t)b * R + tid] & ta_range_mask(-win_base, (int64_t)TA_KV_LEN - win_base);
+            lim = lim < 0 ? 0 : (lim > kv_len ? kv_len : lim);
+            bits = P.win_bits[(int64_t)b * R + tid] & ta_range_mask(-win_base, (int64_t)kv_len - win_base);
         }
         s_lim[tid] = lim;
         s_bits[tid] = bits;
@@ -56,9 +54,8 @@
     const int32_t any_lim = s_any_lim[0] > s_any_lim[1] ? s_any_lim[0] : s_any_lim[1];
     const uint64_t any_bits = s_any_bits[0] | s_any_bits[1];
 
-    const int n_tiles = (TA_KV_LEN + kTaTile - 1) / kTaTile;
-    const int t_begin = TA_T_BEGIN;
-    const int t_end = TA_T_END;
+    const int n_tiles = (kv_len + kTaTile - 1) / kTaTile;
+    const int t_begin = span.begin(n_tiles), t_end = span.end(n_tiles);
     // the first tile at or after t that some row of the sequence can see (t_end: none)
     auto next_tile = [&](int t) {
         for (; t < t_end; ++t) {
@@ -80,7 +77,7 @@
             const int32_t kj = t * kTaTile + key;
             kreg[it] = zero4;
             if (ta_visible(kj, any_lim, any_bits, win_base))
-                kreg[it] = *reinterpret_cast<const ta_u32x4*>(TA_K_ROW(kj) + c * 8);
+                kreg[it] = *reinterpret_cast<const ta_u32x4*>(rows.k(kb, kj) + c * 8);
         }
 #pragma unroll
         for (int it = 0; it < VL; ++it) {
@@ -90,7 +87,7 @@
                 const int32_t kj = t * kTaTile + 2 * pair + e;
                 vreg[it][e] = zero4;
                 if (ta_visible(kj, any_lim, any_bits, win_base))
-                    vreg[it][e] = *reinterpret_cast<const ta_u32x4*>(TA_V_ROW(kj) + c * 8);
+                    vreg[it][e] = *reinterpret_cast<const ta_u32x4*>(rows.v(vb, kj) + c * 8);
             }
         }
     };
@@ -246,8 +243,3 @@
             }
         }
     }
-#ifdef TA_ROW_DEFAULT
-#undef TA_K_ROW
-#undef TA_V_ROW
-#undef TA_ROW_DEFAULT
-#endif

@@ -52,7 +52,7 @@
 // Launch boundaries are the only synchronisation.  The workspace's common counter block is skipped.
 #include "sd_device.h"
 #include "sd_host.h"
-#include "tattn_common.h"   // constants, TaType, ta_exp2, ta_perm, TaFp8Cvt: shared with prefill_attention.hip
+#include "tattn_common.h"   // constants, TaType, ta_exp2, ta_perm, TaFp8Cvt, the paged row, the host checks: shared with prefill_attention.hip
 
 namespace sd {
 
@@ -88,17 +88,52 @@ struct TaParams {
     float scale_log2;   // scale * log2(e): the softmax runs in base 2
 };
 
+// The 64-key tiles [begin(n), end(n)) of a workgroup whose sequence has n tiles.  The body asks behind its first
+// barrier, where these few scalar instructions have always stood.  Split `split` of `splits` ...
+struct TaSplitSpan {
+    int split, splits;
+    __device__ __forceinline__ int begin(int n) const { return (int)((int64_t)split * n / splits); }
+    __device__ __forceinline__ int end(int n) const { return (int)((int64_t)(split + 1) * n / splits); }
+};
+// ... or the chunk of `tiles` tiles from tile `first` on, cut off at n
+struct TaChunkSpan {
+    int first, tiles;
+    __device__ __forceinline__ int begin(int) const { return first; }
+    __device__ __forceinline__ int end(int n) const { return first + tiles < n ? first + tiles : n; }
+};
+
+// the rows of a contiguous cache, sp elements apart
+struct TaFlatRows {
+    int64_t k_sp, v_sp;
+    template <typename E> __device__ __forceinline__ const E* k(const E* kb, int32_t kj) const { return kb + kj * k_sp; }
+    template <typename E> __device__ __forceinline__ const E* v(const E* vb, int32_t kj) const { return vb + kj * v_sp; }
+};
+
+// What the FP8 entries add to TaParams (whose k / v then point at e4m3 bytes, strides in bytes): one fp32
+// dequantisation scale per K/V head for K and for V, read when the kernels run.
+struct TaFp8 {
+    const float* k_scale;   // [Hkv]
+    const float* v_scale;   // [Hkv]
+};
+
+// grid (splits, Hkv, B): split s of a sequence owns the tiles [s * T / splits, (s + 1) * T / splits)
 template <int DT, int D>
 __global__ void __launch_bounds__(kTaThreads) k_tattn_partial(TaParams P) {
-#define TA_KV_LEN P.kv_len
-#define TA_WIN_BASE P.win_base
-#define TA_T_BEGIN (int)((int64_t)split * n_tiles / P.splits)
-#define TA_T_END (int)((int64_t)(split + 1) * n_tiles / P.splits)
+    const int32_t kv_len = P.kv_len;
+    const int64_t win_base = P.win_base;
+    const TaSplitSpan span{(int)blockIdx.x, P.splits};
+    const TaFlatRows rows{P.k_sp, P.v_sp};
 #include "tattn_tile.inc"
-#undef TA_KV_LEN
-#undef TA_WIN_BASE
-#undef TA_T_BEGIN
-#undef TA_T_END
+}
+
+// k_tattn_partial over an e4m3 cache
+template <int DT, int D>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_partial(TaParams P, TaFp8 Fs) {
+    const int32_t kv_len = P.kv_len;
+    const int64_t win_base = P.win_base;
+    const TaSplitSpan span{(int)blockIdx.x, P.splits};
+    const TaFlatRows rows{P.k_sp, P.v_sp};
+#include "tattn_fp8_tile.inc"
 }
 
 // What sd_tree_attention_ragged adds to TaParams (whose kv_len and win_base it leaves unused; P.splits
@@ -118,79 +153,48 @@ __device__ __forceinline__ int32_t ta_ragged_len(const TaRagged& Rg, int64_t b, 
     return (int32_t)(len < 0 ? 0 : (len > Rg.kv_cap ? Rg.kv_cap : len));
 }
 
-// grid (C, Hkv, B).  Chunk c of a sequence is the tiles [c * chunk_tiles, (c + 1) * chunk_tiles) cut off
-// at the sequence's own tile count: a chunk that starts at or beyond len_b leaves before any barrier or
-// K/V load and writes nothing (k_tattn_ragged_combine does not read it).  With C = 1 the one chunk always
-// runs, so that a sequence of length 0 gets its zeros here.
-template <int DT, int D>
-__global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_partial(TaParams P, TaRagged Rg) {
+// The prologue of the ragged and paged kernels, grid (C, Hkv, B).  Chunk c of a sequence is the tiles
+// [c * chunk_tiles, (c + 1) * chunk_tiles) cut off at the sequence's own tile count: a chunk that starts at or
+// beyond len_b leaves before any barrier or K/V load and writes nothing (k_tattn_ragged_combine does not read
+// it).  With C = 1 the one chunk always runs, so that a sequence of length 0 gets its zeros here.  Gives the
+// body's kv_len (len_b), win_base and span; false: the workgroup leaves.
+__device__ __forceinline__ bool ta_ragged_chunk(const TaParams& P, const TaRagged& Rg, int32_t* kv_len, int64_t* win_base,
+                                                TaChunkSpan* span) {
     const int c = blockIdx.x, b = blockIdx.z;
     bool bad;
-    const int32_t len = ta_ragged_len(Rg, b, &bad);
+    *kv_len = ta_ragged_len(Rg, b, &bad);
     if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
-    // chunk c starts at tile c * chunk_tiles (< 2^14 tiles: no overflow)
-    if ((int64_t)c * Rg.chunk_tiles * kTaTile >= len && P.part_ml != nullptr) return;
-    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
-    {
-#define TA_KV_LEN len
-#define TA_WIN_BASE rg_win_base
-#define TA_T_BEGIN split * Rg.chunk_tiles
-#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
-#include "tattn_tile.inc"
-#undef TA_KV_LEN
-#undef TA_WIN_BASE
-#undef TA_T_BEGIN
-#undef TA_T_END
-    }
+    *span = TaChunkSpan{c * Rg.chunk_tiles, Rg.chunk_tiles};       // < 2^14 tiles (ta_chunks): its first key is below 2^20
+    if (span->first * kTaTile >= *kv_len && P.part_ml != nullptr) return false;
+    *win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
+    return true;
 }
 
-// What the FP8 entries add to TaParams (whose k / v then point at e4m3 bytes, strides in bytes): one fp32
-// dequantisation scale per K/V head for K and for V, read when the kernels run.
-struct TaFp8 {
-    const float* k_scale;   // [Hkv]
-    const float* v_scale;   // [Hkv]
-};
-
-// k_tattn_partial over an e4m3 cache
 template <int DT, int D>
-__global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_partial(TaParams P, TaFp8 Fs) {
-#define TA_KV_LEN P.kv_len
-#define TA_WIN_BASE P.win_base
-#define TA_T_BEGIN (int)((int64_t)split * n_tiles / P.splits)
-#define TA_T_END (int)((int64_t)(split + 1) * n_tiles / P.splits)
-#include "tattn_fp8_tile.inc"
-#undef TA_KV_LEN
-#undef TA_WIN_BASE
-#undef TA_T_BEGIN
-#undef TA_T_END
+__global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_partial(TaParams P, TaRagged Rg) {
+    int32_t kv_len;
+    int64_t win_base;
+    TaChunkSpan span;
+    if (!ta_ragged_chunk(P, Rg, &kv_len, &win_base, &span)) return;
+    const TaFlatRows rows{P.k_sp, P.v_sp};
+#include "tattn_tile.inc"
 }
 
 // k_tattn_ragged_partial over an e4m3 cache: the same early exits, so k_tattn_ragged_combine reads what it reads
 template <int DT, int D>
 __global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_ragged_partial(TaParams P, TaRagged Rg, TaFp8 Fs) {
-    const int c = blockIdx.x, b = blockIdx.z;
-    bool bad;
-    const int32_t len = ta_ragged_len(Rg, b, &bad);
-    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
-    if ((int64_t)c * Rg.chunk_tiles * kTaTile >= len && P.part_ml != nullptr) return;
-    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
-    {
-#define TA_KV_LEN len
-#define TA_WIN_BASE rg_win_base
-#define TA_T_BEGIN split * Rg.chunk_tiles
-#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+    int32_t kv_len;
+    int64_t win_base;
+    TaChunkSpan span;
+    if (!ta_ragged_chunk(P, Rg, &kv_len, &win_base, &span)) return;
+    const TaFlatRows rows{P.k_sp, P.v_sp};
 #include "tattn_fp8_tile.inc"
-#undef TA_KV_LEN
-#undef TA_WIN_BASE
-#undef TA_T_BEGIN
-#undef TA_T_END
-    }
 }
 
 // ---- paged caches (sd_tree_attention_paged) ----------------------------------------------------------------
 // K and V in pages of S = 2^page_shift positions of a shared pool, reached through a device block table.  The
 // grid, the early exits, the partial records and the combine are k_tattn_ragged_partial's; the tile bodies are
-// the same two files, whose row address goes through TA_K_ROW / TA_V_ROW.
+// the same two files, given TaPagedRows for their row addresses.
 //
 // The page walk.  A key's page id would be a dependent global load in front of the K/V load the body issues
 // one tile ahead.  A workgroup needs the ids of its own chunk only, and knows which as soon as it has len_b,
@@ -209,12 +213,42 @@ struct TaPaged {
     int32_t num_pages, page_shift;
 };
 
-__device__ const ta_u32x4 ta_zero_row[16] = {};      // a K/V row of zeros: D <= 128 elements of <= 2 bytes
+// The rows of a paged pool (P.k_sb = P.v_sb = 0: kb / vb of the body are the pools at the K/V head), for keys
+// kj < len_b of the workgroup's chunk, whose first page is p0.
+struct TaPagedRows {
+    const int32_t* s_pg;               // the chunk's first kTaPgStage page ids
+    const int32_t* bt_row;             // the sequence's row of the block table
+    int32_t* status_or;
+    int64_t k_ps, k_sp, v_ps, v_sp;    // page and slot strides
+    int32_t p0, num_pages, page_shift;
 
-// the chunk's page ids into s_pg: entries [p0, ceil(key_end / S)) of the sequence's row, key_end <= len_b, so
-// no entry at or beyond ceil(len_b / S) is read
-__device__ __forceinline__ void ta_stage_pages(int32_t* s_pg, const TaPaged& Pg, const int32_t* bt_row, int32_t p0,
-                                               int32_t key_end, int32_t* status_or) {
+    template <typename E>
+    __device__ __forceinline__ const E* row(const E* head, int32_t kj, int64_t ps, int64_t sp) const {
+        const int32_t pi = (kj >> page_shift) - p0;
+        // the LDS read is unconditional: as one arm of a branch it would be merged with the table read of the other
+        // arm into one FLAT load, which waits on the LDS counter and the memory counter alike
+        int32_t id = s_pg[pi < kTaPgStage ? pi : 0];
+        if (pi >= kTaPgStage) {                // behind the staged entries: a chunk of more than kTaPgStage pages
+            id = bt_row[p0 + pi];
+            if ((uint32_t)id >= (uint32_t)num_pages) {
+                id = -1;
+                if (status_or) atomicOr(status_or, SD_ROW_INVALID_DIST);
+            }
+        }
+        return ta_page_row(head, id, kj, page_shift, ps, sp);
+    }
+    template <typename E> __device__ __forceinline__ const E* k(const E* kb, int32_t kj) const { return row(kb, kj, k_ps, k_sp); }
+    template <typename E> __device__ __forceinline__ const E* v(const E* vb, int32_t kj) const { return row(vb, kj, v_ps, v_sp); }
+};
+
+// The prologue of the paged kernels behind ta_ragged_chunk: the chunk's page ids into s_pg (visible after the
+// body's first barrier) — entries [p0, ceil(key_end / S)) of the sequence's row, key_end <= len_b, so no entry at
+// or beyond ceil(len_b / S) is read.
+__device__ __forceinline__ TaPagedRows ta_stage_pages(int32_t* s_pg, const TaParams& P, const TaRagged& Rg, const TaPaged& Pg,
+                                                      int32_t len, const TaChunkSpan& span) {
+    const int32_t* bt_row = Pg.block_table + blockIdx.z * Pg.bt_sb;
+    const int32_t key0 = span.first * kTaTile, chunk_end = key0 + span.tiles * kTaTile;
+    const int32_t p0 = key0 >> Pg.page_shift, key_end = chunk_end < len ? chunk_end : len;
     const int32_t n_all = ((key_end + (1 << Pg.page_shift) - 1) >> Pg.page_shift) - p0;
     const int32_t n = n_all < kTaPgStage ? n_all : kTaPgStage;
     bool bad = false;
@@ -223,101 +257,40 @@ __device__ __forceinline__ void ta_stage_pages(int32_t* s_pg, const TaPaged& Pg,
         if ((uint32_t)id >= (uint32_t)Pg.num_pages) { id = -1; bad = true; }
         s_pg[i] = id;
     }
-    if (bad && status_or && blockIdx.y == 0) atomicOr(status_or, SD_ROW_INVALID_DIST);
+    if (bad && Rg.status_or && blockIdx.y == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
+    return TaPagedRows{s_pg, bt_row, Rg.status_or, Pg.k_ps, P.k_sp, Pg.v_ps, P.v_sp, p0, Pg.num_pages, Pg.page_shift};
 }
 
-// the row of key kj (< len_b) in a pool: `head` is the pool's base moved to the K/V head, ps / sp its page and
-// slot strides
-template <typename E>
-__device__ __forceinline__ const E* ta_paged_row(const E* head, const int32_t* s_pg, const TaPaged& Pg, const int32_t* bt_row,
-                                                 int32_t p0, int32_t* status_or, int32_t kj, int64_t ps, int64_t sp) {
-    const int32_t pi = (kj >> Pg.page_shift) - p0;
-    // the LDS read is unconditional: as one arm of a branch it would be merged with the table read of the other
-    // arm into one FLAT load, which waits on the LDS counter and the memory counter alike
-    int32_t id = s_pg[pi < kTaPgStage ? pi : 0];
-    if (pi >= kTaPgStage) {                // behind the staged entries: a chunk of more than kTaPgStage pages
-        id = bt_row[p0 + pi];
-        if ((uint32_t)id >= (uint32_t)Pg.num_pages) {
-            id = -1;
-            if (status_or) atomicOr(status_or, SD_ROW_INVALID_DIST);
-        }
-    }
-    // one base, two byte offsets: a select between two POINTERS loses the pool's address space and turns the
-    // body's K/V loads into flat loads, which wait on the LDS counter as well as the memory counter
-    const int64_t in_pool = (id * ps + (kj & ((1 << Pg.page_shift) - 1)) * sp) * (int64_t)sizeof(E);
-    const int64_t to_zero = (int64_t)(reinterpret_cast<uintptr_t>(ta_zero_row) - reinterpret_cast<uintptr_t>(head));
-    return reinterpret_cast<const E*>(reinterpret_cast<const char*>(head) + (id < 0 ? to_zero : in_pool));
-}
-
-#define TA_K_ROW(kj) ta_paged_row(kb, s_pg, Pg, pg_row, pg_p0, Rg.status_or, kj, Pg.k_ps, P.k_sp)
-#define TA_V_ROW(kj) ta_paged_row(vb, s_pg, Pg, pg_row, pg_p0, Rg.status_or, kj, Pg.v_ps, P.v_sp)
-
-// k_tattn_ragged_partial over a paged pool (P.k_sb = P.v_sb = 0: kb / vb of the body are the pools at the head)
+// k_tattn_ragged_partial over a paged pool
 template <int DT, int D>
 __global__ void __launch_bounds__(kTaThreads) k_tattn_paged_partial(TaParams P, TaRagged Rg, TaPaged Pg) {
     __shared__ int32_t s_pg[kTaPgStage];
-    const int c = blockIdx.x, b = blockIdx.z;
-    bool bad;
-    const int32_t len = ta_ragged_len(Rg, b, &bad);
-    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
-    const int32_t pg_key0 = c * Rg.chunk_tiles * kTaTile;          // < 2^20: ta_chunks
-    if (pg_key0 >= len && P.part_ml != nullptr) return;
-    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
-    const int32_t* pg_row = Pg.block_table + b * Pg.bt_sb;
-    const int32_t pg_p0 = pg_key0 >> Pg.page_shift;
-    const int32_t pg_end = pg_key0 + Rg.chunk_tiles * kTaTile;
-    ta_stage_pages(s_pg, Pg, pg_row, pg_p0, pg_end < len ? pg_end : len, Rg.status_or);   // visible after the body's first barrier
-    {
-#define TA_KV_LEN len
-#define TA_WIN_BASE rg_win_base
-#define TA_T_BEGIN split * Rg.chunk_tiles
-#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+    int32_t kv_len;
+    int64_t win_base;
+    TaChunkSpan span;
+    if (!ta_ragged_chunk(P, Rg, &kv_len, &win_base, &span)) return;
+    const TaPagedRows rows = ta_stage_pages(s_pg, P, Rg, Pg, kv_len, span);
 #include "tattn_tile.inc"
-#undef TA_KV_LEN
-#undef TA_WIN_BASE
-#undef TA_T_BEGIN
-#undef TA_T_END
-    }
 }
 
 // k_tattn_fp8_ragged_partial over a paged e4m3 pool
 template <int DT, int D>
 __global__ void __launch_bounds__(kTaThreads) k_tattn_fp8_paged_partial(TaParams P, TaRagged Rg, TaFp8 Fs, TaPaged Pg) {
     __shared__ int32_t s_pg[kTaPgStage];
-    const int c = blockIdx.x, b = blockIdx.z;
-    bool bad;
-    const int32_t len = ta_ragged_len(Rg, b, &bad);
-    if (bad && Rg.status_or && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicOr(Rg.status_or, SD_ROW_INVALID_DIST);
-    const int32_t pg_key0 = c * Rg.chunk_tiles * kTaTile;
-    if (pg_key0 >= len && P.part_ml != nullptr) return;
-    const int64_t rg_win_base = (int64_t)((uint64_t)Rg.win_base_dev[b] + (uint64_t)Rg.win_base_add);
-    const int32_t* pg_row = Pg.block_table + b * Pg.bt_sb;
-    const int32_t pg_p0 = pg_key0 >> Pg.page_shift;
-    const int32_t pg_end = pg_key0 + Rg.chunk_tiles * kTaTile;
-    ta_stage_pages(s_pg, Pg, pg_row, pg_p0, pg_end < len ? pg_end : len, Rg.status_or);
-    {
-#define TA_KV_LEN len
-#define TA_WIN_BASE rg_win_base
-#define TA_T_BEGIN split * Rg.chunk_tiles
-#define TA_T_END (t_begin + Rg.chunk_tiles < n_tiles ? t_begin + Rg.chunk_tiles : n_tiles)
+    int32_t kv_len;
+    int64_t win_base;
+    TaChunkSpan span;
+    if (!ta_ragged_chunk(P, Rg, &kv_len, &win_base, &span)) return;
+    const TaPagedRows rows = ta_stage_pages(s_pg, P, Rg, Pg, kv_len, span);
 #include "tattn_fp8_tile.inc"
-#undef TA_KV_LEN
-#undef TA_WIN_BASE
-#undef TA_T_BEGIN
-#undef TA_T_END
-    }
 }
-#undef TA_K_ROW
-#undef TA_V_ROW
 
-// k_tattn_combine over the chunks a sequence's own length reaches: chunks 0 .. ceil(tiles_b / chunk_tiles) - 1
-// were written by this call's k_tattn_ragged_partial, the slots behind them were not and are not read.
+// One thread of a combine kernel, idx = (((b * Hq + hq) * R + r) * D / 4 + d / 4): the first n partials of its
+// row merged in ascending order.
 template <int DT>
-__global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_combine(TaParams P, TaRagged Rg, int64_t total) {
+__device__ __forceinline__ void ta_combine(const TaParams& P, int64_t idx, int n) {
     using E = typename TaType<DT>::elem;
     constexpr float kNegInf = -__builtin_inff();
-    const int64_t idx = (int64_t)blockIdx.x * kTaThreads + threadIdx.x;
-    if (idx >= total) return;
     const int D = P.head_dim, R = P.rows, G = P.group, M = R * G;
     const int q4 = D / 4;
     const int d = (int)(idx % q4) * 4;
@@ -328,17 +301,13 @@ __global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_combine(TaParams P,
     const int hq = (int)(bh % heads_q);
     const int64_t b = bh / heads_q;
     const int hkv = hq / G, m = (hq - hkv * G) * R + r;
-    bool bad;
-    const int32_t len = ta_ragged_len(Rg, b, &bad);
-    const int n_tiles = (len + kTaTile - 1) / kTaTile;
-    const int chunks = (n_tiles + Rg.chunk_tiles - 1) / Rg.chunk_tiles;     // <= P.splits, 0 for an empty sequence
-    const int64_t prow0 = ((b * P.heads_kv + hkv) * P.splits) * M + m;     // chunk c: + c * M
+    const int64_t prow0 = ((b * P.heads_kv + hkv) * P.splits) * M + m;     // partial s: + s * M
     float mx = kNegInf;
-    for (int c = 0; c < chunks; ++c) mx = fmaxf(mx, P.part_ml[2 * (prow0 + (int64_t)c * M)]);
+    for (int s = 0; s < n; ++s) mx = fmaxf(mx, P.part_ml[2 * (prow0 + (int64_t)s * M)]);
     ta_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float l = 0.f;
-    for (int c = 0; c < chunks; ++c) {            // ascending: the sum's order never depends on timing
-        const int64_t prow = prow0 + (int64_t)c * M;
+    for (int s = 0; s < n; ++s) {                 // ascending: the sum's order never depends on timing
+        const int64_t prow = prow0 + (int64_t)s * M;
         const float ms = P.part_ml[2 * prow];
         if (ms == kNegInf) continue;              // an empty partial: its O was never written
         const float w = ta_exp2(ms - mx);
@@ -357,41 +326,20 @@ __global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_combine(TaParams P,
 
 template <int DT>
 __global__ void __launch_bounds__(kTaThreads) k_tattn_combine(TaParams P, int64_t total) {
-    using E = typename TaType<DT>::elem;
-    constexpr float kNegInf = -__builtin_inff();
+    const int64_t idx = (int64_t)blockIdx.x * kTaThreads + threadIdx.x;
+    if (idx < total) ta_combine<DT>(P, idx, P.splits);
+}
+
+// k_tattn_combine over the chunks a sequence's own length reaches: chunks 0 .. ceil(tiles_b / chunk_tiles) - 1
+// were written by this call's k_tattn_ragged_partial, the slots behind them were not and are not read.
+template <int DT>
+__global__ void __launch_bounds__(kTaThreads) k_tattn_ragged_combine(TaParams P, TaRagged Rg, int64_t total) {
     const int64_t idx = (int64_t)blockIdx.x * kTaThreads + threadIdx.x;
     if (idx >= total) return;
-    const int D = P.head_dim, R = P.rows, G = P.group, M = R * G;
-    const int q4 = D / 4;
-    const int d = (int)(idx % q4) * 4;
-    const int64_t row = idx / q4;
-    const int r = (int)(row % R);
-    const int64_t bh = row / R;
-    const int heads_q = P.heads_kv * G;
-    const int hq = (int)(bh % heads_q);
-    const int64_t b = bh / heads_q;
-    const int hkv = hq / G, m = (hq - hkv * G) * R + r;
-    const int64_t prow0 = ((b * P.heads_kv + hkv) * P.splits) * M + m;     // split s: + s * M
-    float mx = kNegInf;
-    for (int s = 0; s < P.splits; ++s) mx = fmaxf(mx, P.part_ml[2 * (prow0 + (int64_t)s * M)]);
-    ta_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    float l = 0.f;
-    for (int s = 0; s < P.splits; ++s) {          // ascending: the sum's order never depends on timing
-        const int64_t prow = prow0 + (int64_t)s * M;
-        const float ms = P.part_ml[2 * prow];
-        if (ms == kNegInf) continue;              // an empty partial: its O was never written
-        const float w = ta_exp2(ms - mx);
-        l += w * P.part_ml[2 * prow + 1];
-        const ta_f32x4 y = *reinterpret_cast<const ta_f32x4*>(P.part_o + prow * D + d);
-        acc += w * y;
-    }
-    typedef E vec4 __attribute__((ext_vector_type(4)));
-    vec4 y;
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = l > 0.f ? (E)(acc[e] * inv) : (E)0.f;
-    E* o = static_cast<E*>(P.out) + b * P.o_sb + r * P.o_sr + hq * P.o_sh + d;
-    *reinterpret_cast<ta_u32x2*>(o) = __builtin_bit_cast(ta_u32x2, y);
+    bool bad;
+    const int32_t len = ta_ragged_len(Rg, idx / (P.head_dim / 4) / P.rows / (P.heads_kv * P.group), &bad);
+    const int n_tiles = (len + kTaTile - 1) / kTaTile;
+    ta_combine<DT>(P, idx, (n_tiles + Rg.chunk_tiles - 1) / Rg.chunk_tiles);     // <= P.splits, 0 for an empty sequence
 }
 
 // The splits a call runs.  Auto: as many workgroups as fill the device (kTaFill over B * Hkv), but no
@@ -437,13 +385,10 @@ static int ta_chunks(int64_t batch, int64_t heads_kv, int32_t kv_cap, int32_t ch
 // SD_OK when sd_tree_attention takes the shape
 static int32_t ta_check_shape(int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t rows, int32_t head_dim,
                               int32_t kv_len, int32_t splits) {
-    if (batch < 1 || heads_q < 1 || heads_kv < 1 || rows < 1 || head_dim < 1 || kv_len < 1 || splits < 0)
-        return SD_ERR_INVALID;
-    if (heads_q % heads_kv) return SD_ERR_INVALID;
-    if (head_dim != 64 && head_dim != 128) return SD_ERR_UNSUPPORTED;
-    if (heads_q / heads_kv > SD_TREE_ATTN_MAX_GROUP || rows > SD_TREE_ATTN_MAX_ROWS) return SD_ERR_UNSUPPORTED;
-    if (kv_len > SD_TREE_ATTN_MAX_KV || splits > SD_TREE_ATTN_MAX_SPLITS) return SD_ERR_UNSUPPORTED;
-    if (batch > 65535 || heads_kv > 65535) return SD_ERR_UNSUPPORTED;       // grid.z, grid.y
+    if (splits < 0) return SD_ERR_INVALID;
+    const int32_t dims = ta_check_dims(batch, heads_q, heads_kv, rows, SD_TREE_ATTN_MAX_ROWS, head_dim, kv_len);
+    if (dims != SD_OK) return dims;
+    if (splits > SD_TREE_ATTN_MAX_SPLITS) return SD_ERR_UNSUPPORTED;
     // the combine's grid: one thread per four output elements
     const int64_t quads = (int64_t)batch * heads_q * rows * (head_dim / 4);
     if ((quads + kTaThreads - 1) / kTaThreads > INT32_MAX) return SD_ERR_UNSUPPORTED;
@@ -469,54 +414,134 @@ static TaWorkspace ta_carve(void* base, int64_t batch, int64_t heads_q, int64_t 
     return w;
 }
 
-// the tensor fields sd_tree_attention_args and sd_tree_attention_ragged_args share: SD_OK when the
-// pointers are given and every address the kernels form from them keeps its alignment
-template <typename A>
-static int32_t ta_check_tensors(const A* a) {
-    if (!a->q || !a->k || !a->v || !a->out || !a->kv_limit || !a->win_bits) return SD_ERR_INVALID;
-    if (!(a->scale == a->scale)) return SD_ERR_INVALID;
-    // 16-byte accesses: every address the kernels form is a multiple of 16 bytes (8 elements)
-    const int64_t strides[] = {a->q_stride_b, a->q_stride_h, a->q_stride_r, a->k_stride_b, a->k_stride_h, a->k_stride_pos,
-                               a->v_stride_b, a->v_stride_h, a->v_stride_pos, a->out_stride_b, a->out_stride_r,
-                               a->out_stride_h};
-    for (int64_t s : strides)
-        if (s < 0 || (s & 7)) return SD_ERR_INVALID;
-    if (a->q_stride_r < a->head_dim || a->k_stride_pos < a->head_dim || a->v_stride_pos < a->head_dim ||
-        a->out_stride_h < a->head_dim)
-        return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
-         reinterpret_cast<uintptr_t>(a->out)) & 15)
-        return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->kv_limit) & 3) || (reinterpret_cast<uintptr_t>(a->win_bits) & 7)) return SD_ERR_INVALID;
-    return SD_OK;
-}
+// One tree-attention call as every entry describes it; ta_run does the rest.
+struct TaCall {
+    int32_t dtype, batch, heads_q, heads_kv, rows, head_dim;
+    float scale;
+    TaTensors t;
+    const int32_t* kv_limit;
+    const uint64_t* win_bits;
+    const TaFp8* fp8;                  // the scales of an e4m3 cache, null for a 16-bit one
+    int32_t kv_len, splits;            // the valid keys and the split count asked for; unused with `ragged`
+    int64_t win_base;
+    int32_t kv_alloc;                  // positions k / v hold; unused with `paged`
+    const TaRagged* ragged;            // per-sequence lengths (chunk_tiles as the caller gave it), or null
+    const TaPaged* paged;              // with `ragged`: the pools' table (page_shift unset), or null
+    int32_t page_size, max_pages;
+    void* workspace;
+    size_t workspace_bytes;
+};
 
-// what the FP8 argument structs add to ta_check_tensors: k / v are bytes, so their strides (in elements) must
-// themselves be multiples of 16, and the scales must be given
-template <typename A>
-static int32_t ta_check_fp8(const A* a) {
-    if (!a->k_scale || !a->v_scale) return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->k_scale) | reinterpret_cast<uintptr_t>(a->v_scale)) & 3) return SD_ERR_INVALID;
-    const int64_t strides[] = {a->k_stride_b, a->k_stride_h, a->k_stride_pos, a->v_stride_b, a->v_stride_h, a->v_stride_pos};
-    for (int64_t s : strides)
-        if (s & 15) return SD_ERR_INVALID;
-    return SD_OK;
-}
-
-// the fields both argument structs share, into the kernels' parameters
-template <typename A>
-static TaParams ta_params(const A* a, const TaWorkspace& w, int splits) {
+// Checks (in the order the entries have always made them, where two statuses can meet), the split or chunk
+// count, the workspace, the partial launch and the combine launch of every sd_tree_attention* entry.
+static int32_t ta_run(const TaCall& c, void* stream) {
+    using namespace sd_host;
+    const bool ragged = c.ragged != nullptr, paged = c.paged != nullptr;
+    int32_t st;
+    // the contiguous FP8 entries check their scales first, the paged entry behind its tensors
+    if (c.fp8 && !paged && (st = ta_check_fp8(c.t, c.fp8->k_scale, c.fp8->v_scale)) != SD_OK) return st;
+    if (!valid_dtype(c.dtype)) return SD_ERR_INVALID;
+    if (c.dtype == SD_F32) return SD_ERR_UNSUPPORTED;
+    TaRagged Rg{};
+    TaPaged Pg{};
+    if (ragged) Rg = *c.ragged;
+    if (Rg.chunk_tiles < 0) return SD_ERR_INVALID;
+    if (paged) {
+        Pg = *c.paged;
+        if ((st = ta_check_pool(c.page_size, Pg.num_pages, c.max_pages, &Pg.page_shift)) != SD_OK) return st;
+    }
+    const int32_t kv = ragged ? Rg.kv_cap : c.kv_len;                // the host's bound on the valid keys
+    if ((st = ta_check_shape(c.batch, c.heads_q, c.heads_kv, c.rows, c.head_dim, kv, ragged ? 0 : c.splits)) != SD_OK) return st;
+    if (paged) {
+        if ((st = ta_check_table(Pg.block_table, Pg.bt_sb, c.max_pages, c.page_size, kv)) != SD_OK) return st;
+    } else if (c.kv_alloc < kv) {
+        return SD_ERR_INVALID;
+    }
+    if ((st = ta_check_tensors(c.t, c.head_dim, c.scale)) != SD_OK) return st;
+    if (!c.kv_limit || !c.win_bits) return SD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(c.kv_limit) & 3) || (reinterpret_cast<uintptr_t>(c.win_bits) & 7)) return SD_ERR_INVALID;
+    if (c.fp8 && paged && (st = ta_check_fp8(c.t, c.fp8->k_scale, c.fp8->v_scale)) != SD_OK) return st;
+    if (ragged) {
+        if (!Rg.kv_len_dev || !Rg.win_base_dev) return SD_ERR_INVALID;
+        if ((reinterpret_cast<uintptr_t>(Rg.kv_len_dev) | reinterpret_cast<uintptr_t>(Rg.win_base_dev)) & 7) return SD_ERR_INVALID;
+        if (reinterpret_cast<uintptr_t>(Rg.status_or) & 3) return SD_ERR_INVALID;
+    }
+    // the partials of a row: splits of a known length, or the chunk slots of kv_cap
+    const int parts = ragged ? ta_chunks(c.batch, c.heads_kv, kv, Rg.chunk_tiles) : ta_splits(c.batch, c.heads_kv, kv, c.splits);
+    if (parts == 0) return SD_ERR_UNSUPPORTED;              // a pinned chunk length that needs too many slots
+    TaWorkspace w{nullptr, nullptr, 0};
+    if (parts > 1) {
+        w = ta_carve(c.workspace, c.batch, c.heads_q, c.rows, c.head_dim, parts);
+        if (!c.workspace || c.workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(c.workspace) & 255) return SD_ERR_INVALID;
+    }
     TaParams P{};
-    P.q = a->q; P.k = a->k; P.v = a->v; P.out = a->out; P.kv_limit = a->kv_limit; P.win_bits = a->win_bits;
+    P.q = c.t.q; P.k = c.t.k; P.v = c.t.v; P.out = c.t.out; P.kv_limit = c.kv_limit; P.win_bits = c.win_bits;
     P.part_ml = w.ml; P.part_o = w.o;
-    P.q_sb = a->q_stride_b; P.q_sh = a->q_stride_h; P.q_sr = a->q_stride_r;
-    P.k_sb = a->k_stride_b; P.k_sh = a->k_stride_h; P.k_sp = a->k_stride_pos;
-    P.v_sb = a->v_stride_b; P.v_sh = a->v_stride_h; P.v_sp = a->v_stride_pos;
-    P.o_sb = a->out_stride_b; P.o_sr = a->out_stride_r; P.o_sh = a->out_stride_h;
-    P.rows = a->rows; P.group = a->heads_q / a->heads_kv; P.heads_kv = a->heads_kv;
-    P.splits = splits; P.head_dim = a->head_dim;
-    P.scale_log2 = a->scale * 1.4426950408889634f;
-    return P;
+    P.q_sb = c.t.q_sb; P.q_sh = c.t.q_sh; P.q_sr = c.t.q_sr;
+    P.k_sb = c.t.k_sb; P.k_sh = c.t.k_sh; P.k_sp = c.t.k_sp;
+    P.v_sb = c.t.v_sb; P.v_sh = c.t.v_sh; P.v_sp = c.t.v_sp;
+    P.o_sb = c.t.o_sb; P.o_sr = c.t.o_sr; P.o_sh = c.t.o_sh;
+    P.rows = c.rows; P.group = c.heads_q / c.heads_kv; P.heads_kv = c.heads_kv;
+    P.splits = parts; P.head_dim = c.head_dim;
+    P.scale_log2 = c.scale * 1.4426950408889634f;
+    if (paged) P.k_sb = P.v_sb = 0;                                  // the body's kb / vb: the pools at the head
+    if (ragged) Rg.chunk_tiles = ta_chunk_tiles(c.batch, c.heads_kv, kv, Rg.chunk_tiles);
+    else { P.win_base = c.win_base; P.kv_len = kv; }
+    clear_stale_error();
+    const dim3 grid((unsigned)parts, (unsigned)c.heads_kv, (unsigned)c.batch), block(kTaThreads);
+    st = dispatch_dtype16(c.dtype, [&](auto dt) {
+        return dispatch_int<64, 128>(c.head_dim, [&](auto d) {
+            constexpr int DT = decltype(dt)::value, D = decltype(d)::value;
+            if (paged)
+                return c.fp8 ? launch(k_tattn_fp8_paged_partial<DT, D>, grid, block, 0, stream, P, Rg, *c.fp8, Pg)
+                             : launch(k_tattn_paged_partial<DT, D>, grid, block, 0, stream, P, Rg, Pg);
+            if (ragged)
+                return c.fp8 ? launch(k_tattn_fp8_ragged_partial<DT, D>, grid, block, 0, stream, P, Rg, *c.fp8)
+                             : launch(k_tattn_ragged_partial<DT, D>, grid, block, 0, stream, P, Rg);
+            return c.fp8 ? launch(k_tattn_fp8_partial<DT, D>, grid, block, 0, stream, P, *c.fp8)
+                         : launch(k_tattn_partial<DT, D>, grid, block, 0, stream, P);
+        });
+    });
+    if (st != SD_OK || parts == 1) return st;
+    const int64_t total = (int64_t)c.batch * c.heads_q * c.rows * (c.head_dim / 4);
+    const dim3 cgrid((unsigned)((total + kTaThreads - 1) / kTaThreads));
+    return dispatch_dtype16(c.dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return ragged ? launch(k_tattn_ragged_combine<DT>, cgrid, block, 0, stream, P, Rg, total)
+                      : launch(k_tattn_combine<DT>, cgrid, block, 0, stream, P, total);
+    });
+}
+
+// the fields the four contiguous argument structs share
+template <typename A>
+static TaCall ta_describe(const A* a, const TaFp8* fp8) {
+    TaCall c{};
+    c.dtype = a->dtype; c.batch = a->batch; c.heads_q = a->heads_q; c.heads_kv = a->heads_kv; c.rows = a->rows;
+    c.head_dim = a->head_dim; c.scale = a->scale; c.kv_alloc = a->kv_alloc;
+    c.t = TaTensors{a->q, a->k, a->v, a->out, a->q_stride_b, a->q_stride_h, a->q_stride_r, a->k_stride_b, a->k_stride_h,
+                    a->k_stride_pos, a->v_stride_b, a->v_stride_h, a->v_stride_pos, a->out_stride_b, a->out_stride_r,
+                    a->out_stride_h};
+    c.kv_limit = a->kv_limit; c.win_bits = a->win_bits; c.fp8 = fp8;
+    c.workspace = a->workspace; c.workspace_bytes = a->workspace_bytes;
+    return c;
+}
+
+// sd_tree_attention (fp8 null) and sd_tree_attention_fp8
+template <typename A>
+static int32_t ta_split_entry(const A* a, void* stream, const TaFp8* fp8) {
+    TaCall c = ta_describe(a, fp8);
+    c.kv_len = a->kv_len; c.splits = a->splits; c.win_base = a->win_base;
+    return ta_run(c, stream);
+}
+
+// sd_tree_attention_ragged (fp8 null) and sd_tree_attention_ragged_fp8
+template <typename A>
+static int32_t ta_ragged_entry(const A* a, void* stream, const TaFp8* fp8) {
+    TaCall c = ta_describe(a, fp8);
+    const TaRagged rg{a->kv_len_dev, a->win_base_dev, a->kv_len_add, a->win_base_add, a->status_or, a->kv_cap, a->chunk_tiles};
+    c.ragged = &rg;
+    return ta_run(c, stream);
 }
 
 }  // namespace sd
@@ -534,57 +559,14 @@ extern "C" size_t sd_tree_attention_workspace_size(int32_t batch, int32_t heads_
     return sd::ta_carve(nullptr, batch, heads_q, rows, head_dim, sd::ta_splits(batch, heads_kv, kv_len, splits)).bytes;
 }
 
-// sd_tree_attention (fs null) and sd_tree_attention_fp8 (fs: the scales), whose argument structs share every
-// other field
-template <typename A>
-static int32_t ta_call(const A* a, void* stream, const sd::TaFp8* fs) {
-    using namespace sd_host;
-    if (!a) return SD_ERR_INVALID;
-    if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
-    if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;
-    const int32_t shape = sd::ta_check_shape(a->batch, a->heads_q, a->heads_kv, a->rows, a->head_dim, a->kv_len, a->splits);
-    if (shape != SD_OK) return shape;
-    if (a->kv_alloc < a->kv_len) return SD_ERR_INVALID;
-    const int32_t tensors = sd::ta_check_tensors(a);
-    if (tensors != SD_OK) return tensors;
-    const int splits = sd::ta_splits(a->batch, a->heads_kv, a->kv_len, a->splits);
-    sd::TaWorkspace w{nullptr, nullptr, 0};
-    if (splits > 1) {
-        w = sd::ta_carve(a->workspace, a->batch, a->heads_q, a->rows, a->head_dim, splits);
-        if (!a->workspace || a->workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
-        if (reinterpret_cast<uintptr_t>(a->workspace) & 255) return SD_ERR_INVALID;
-    }
-    sd::TaParams P = sd::ta_params(a, w, splits);
-    P.win_base = a->win_base; P.kv_len = a->kv_len;
-    clear_stale_error();
-    const dim3 grid((unsigned)splits, (unsigned)a->heads_kv, (unsigned)a->batch);
-    int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
-        return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
-            if (fs)
-                return launch(sd::k_tattn_fp8_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
-                              0, stream, P, *fs);
-            return launch(sd::k_tattn_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads), 0,
-                          stream, P);
-        });
-    });
-    if (st != SD_OK || splits == 1) return st;
-    const int64_t total = (int64_t)a->batch * a->heads_q * a->rows * (a->head_dim / 4);
-    const dim3 cgrid((unsigned)((total + sd::kTaThreads - 1) / sd::kTaThreads));
-    return dispatch_dtype16(a->dtype, [&](auto dt) {
-        return launch(sd::k_tattn_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, total);
-    });
-}
-
 extern "C" int32_t sd_tree_attention(const sd_tree_attention_args* a, void* stream) {
-    return ta_call(a, stream, nullptr);
+    return a ? sd::ta_split_entry(a, stream, nullptr) : SD_ERR_INVALID;
 }
 
 extern "C" int32_t sd_tree_attention_fp8(const sd_tree_attention_fp8_args* a, void* stream) {
     if (!a) return SD_ERR_INVALID;
-    const int32_t st = sd::ta_check_fp8(a);
-    if (st != SD_OK) return st;
     const sd::TaFp8 fs{a->k_scale, a->v_scale};
-    return ta_call(a, stream, &fs);
+    return sd::ta_split_entry(a, stream, &fs);
 }
 
 // ---- ragged batches: per-sequence lengths and window bases read on the device ---------------------------
@@ -600,136 +582,32 @@ extern "C" size_t sd_tree_attention_ragged_workspace_size(int32_t batch, int32_t
     return chunks ? sd::ta_carve(nullptr, batch, heads_q, rows, head_dim, chunks).bytes : 0;
 }
 
-// sd_tree_attention_ragged (fs null) and sd_tree_attention_ragged_fp8 (fs: the scales)
-template <typename A>
-static int32_t ta_ragged_call(const A* a, void* stream, const sd::TaFp8* fs) {
-    using namespace sd_host;
-    if (!a) return SD_ERR_INVALID;
-    if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
-    if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;
-    if (a->chunk_tiles < 0) return SD_ERR_INVALID;
-    const int32_t shape = sd::ta_check_shape(a->batch, a->heads_q, a->heads_kv, a->rows, a->head_dim, a->kv_cap, 0);
-    if (shape != SD_OK) return shape;
-    if (a->kv_alloc < a->kv_cap) return SD_ERR_INVALID;
-    const int32_t tensors = sd::ta_check_tensors(a);
-    if (tensors != SD_OK) return tensors;
-    if (!a->kv_len_dev || !a->win_base_dev) return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->kv_len_dev) | reinterpret_cast<uintptr_t>(a->win_base_dev)) & 7) return SD_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(a->status_or) & 3) return SD_ERR_INVALID;
-    const int chunks = sd::ta_chunks(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
-    if (chunks == 0) return SD_ERR_UNSUPPORTED;             // a pinned chunk length that needs too many slots
-    sd::TaWorkspace w{nullptr, nullptr, 0};
-    if (chunks > 1) {
-        w = sd::ta_carve(a->workspace, a->batch, a->heads_q, a->rows, a->head_dim, chunks);
-        if (!a->workspace || a->workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
-        if (reinterpret_cast<uintptr_t>(a->workspace) & 255) return SD_ERR_INVALID;
-    }
-    const sd::TaParams P = sd::ta_params(a, w, chunks);
-    sd::TaRagged Rg{};
-    Rg.kv_len_dev = a->kv_len_dev; Rg.win_base_dev = a->win_base_dev;
-    Rg.kv_len_add = a->kv_len_add; Rg.win_base_add = a->win_base_add;
-    Rg.status_or = a->status_or; Rg.kv_cap = a->kv_cap;
-    Rg.chunk_tiles = sd::ta_chunk_tiles(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
-    clear_stale_error();
-    const dim3 grid((unsigned)chunks, (unsigned)a->heads_kv, (unsigned)a->batch);
-    int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
-        return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
-            if (fs)
-                return launch(sd::k_tattn_fp8_ragged_partial<decltype(dt)::value, decltype(d)::value>, grid,
-                              dim3(sd::kTaThreads), 0, stream, P, Rg, *fs);
-            return launch(sd::k_tattn_ragged_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
-                          0, stream, P, Rg);
-        });
-    });
-    if (st != SD_OK || chunks == 1) return st;
-    const int64_t total = (int64_t)a->batch * a->heads_q * a->rows * (a->head_dim / 4);
-    const dim3 cgrid((unsigned)((total + sd::kTaThreads - 1) / sd::kTaThreads));
-    return dispatch_dtype16(a->dtype, [&](auto dt) {
-        return launch(sd::k_tattn_ragged_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, Rg, total);
-    });
-}
-
-// ---- paged caches: the ragged call through a block table -------------------------------------------------
-extern "C" int32_t sd_tree_attention_paged(const sd_tree_attention_paged_args* a, void* stream) {
-    using namespace sd_host;
-    if (!a) return SD_ERR_INVALID;
-    if (!valid_dtype(a->dtype)) return SD_ERR_INVALID;
-    if (a->dtype == SD_F32) return SD_ERR_UNSUPPORTED;
-    if (a->chunk_tiles < 0) return SD_ERR_INVALID;
-    int shift = 0;
-    while (shift < 9 && (1 << shift) != a->page_size) ++shift;
-    if (shift < 4 || shift > 8) return SD_ERR_INVALID;               // 16, 32, 64, 128, 256
-    if (a->num_pages < 1 || a->max_pages < 1) return SD_ERR_INVALID;
-    const int32_t shape = sd::ta_check_shape(a->batch, a->heads_q, a->heads_kv, a->rows, a->head_dim, a->kv_cap, 0);
-    if (shape != SD_OK) return shape;
-    if (a->kv_cap > (int64_t)a->max_pages * a->page_size) return SD_ERR_INVALID;
-    // the fields the ragged checks and ta_params read, with the page strides in the place of the batch strides
-    sd_tree_attention_ragged_fp8_args r{};
-    r.head_dim = a->head_dim; r.heads_q = a->heads_q; r.heads_kv = a->heads_kv; r.rows = a->rows; r.scale = a->scale;
-    r.q = a->q; r.q_stride_b = a->q_stride_b; r.q_stride_h = a->q_stride_h; r.q_stride_r = a->q_stride_r;
-    r.k = a->k; r.v = a->v;
-    r.k_stride_b = a->k_stride_page; r.k_stride_h = a->k_stride_h; r.k_stride_pos = a->k_stride_pos;
-    r.v_stride_b = a->v_stride_page; r.v_stride_h = a->v_stride_h; r.v_stride_pos = a->v_stride_pos;
-    r.out = a->out; r.out_stride_b = a->out_stride_b; r.out_stride_r = a->out_stride_r; r.out_stride_h = a->out_stride_h;
-    r.kv_limit = a->kv_limit; r.win_bits = a->win_bits; r.k_scale = a->k_scale; r.v_scale = a->v_scale;
-    const int32_t tensors = sd::ta_check_tensors(&r);
-    if (tensors != SD_OK) return tensors;
-    if (a->kv_fp8) {
-        const int32_t st = sd::ta_check_fp8(&r);
-        if (st != SD_OK) return st;
-    }
-    if (!a->kv_len_dev || !a->win_base_dev) return SD_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(a->kv_len_dev) | reinterpret_cast<uintptr_t>(a->win_base_dev)) & 7) return SD_ERR_INVALID;
-    if (!a->block_table || (reinterpret_cast<uintptr_t>(a->block_table) & 3)) return SD_ERR_INVALID;
-    if (a->block_table_stride_b < a->max_pages) return SD_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(a->status_or) & 3) return SD_ERR_INVALID;
-    const int chunks = sd::ta_chunks(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
-    if (chunks == 0) return SD_ERR_UNSUPPORTED;
-    sd::TaWorkspace w{nullptr, nullptr, 0};
-    if (chunks > 1) {
-        w = sd::ta_carve(a->workspace, a->batch, a->heads_q, a->rows, a->head_dim, chunks);
-        if (!a->workspace || a->workspace_bytes < w.bytes) return SD_ERR_WORKSPACE;
-        if (reinterpret_cast<uintptr_t>(a->workspace) & 255) return SD_ERR_INVALID;
-    }
-    sd::TaParams P = sd::ta_params(&r, w, chunks);
-    P.k_sb = 0; P.v_sb = 0;                                          // the body's kb / vb: the pools at the head
-    sd::TaRagged Rg{};
-    Rg.kv_len_dev = a->kv_len_dev; Rg.win_base_dev = a->win_base_dev;
-    Rg.kv_len_add = a->kv_len_add; Rg.win_base_add = a->win_base_add;
-    Rg.status_or = a->status_or; Rg.kv_cap = a->kv_cap;
-    Rg.chunk_tiles = sd::ta_chunk_tiles(a->batch, a->heads_kv, a->kv_cap, a->chunk_tiles);
-    sd::TaPaged Pg{};
-    Pg.block_table = a->block_table; Pg.bt_sb = a->block_table_stride_b;
-    Pg.k_ps = a->k_stride_page; Pg.v_ps = a->v_stride_page;
-    Pg.num_pages = a->num_pages; Pg.page_shift = shift;
-    const sd::TaFp8 fs{a->k_scale, a->v_scale};
-    clear_stale_error();
-    const dim3 grid((unsigned)chunks, (unsigned)a->heads_kv, (unsigned)a->batch);
-    int32_t st = dispatch_dtype16(a->dtype, [&](auto dt) {
-        return dispatch_int<64, 128>(a->head_dim, [&](auto d) {
-            if (a->kv_fp8)
-                return launch(sd::k_tattn_fp8_paged_partial<decltype(dt)::value, decltype(d)::value>, grid,
-                              dim3(sd::kTaThreads), 0, stream, P, Rg, fs, Pg);
-            return launch(sd::k_tattn_paged_partial<decltype(dt)::value, decltype(d)::value>, grid, dim3(sd::kTaThreads),
-                          0, stream, P, Rg, Pg);
-        });
-    });
-    if (st != SD_OK || chunks == 1) return st;
-    const int64_t total = (int64_t)a->batch * a->heads_q * a->rows * (a->head_dim / 4);
-    const dim3 cgrid((unsigned)((total + sd::kTaThreads - 1) / sd::kTaThreads));
-    return dispatch_dtype16(a->dtype, [&](auto dt) {
-        return launch(sd::k_tattn_ragged_combine<decltype(dt)::value>, cgrid, dim3(sd::kTaThreads), 0, stream, P, Rg, total);
-    });
-}
-
 extern "C" int32_t sd_tree_attention_ragged(const sd_tree_attention_ragged_args* a, void* stream) {
-    return ta_ragged_call(a, stream, nullptr);
+    return a ? sd::ta_ragged_entry(a, stream, nullptr) : SD_ERR_INVALID;
 }
 
 extern "C" int32_t sd_tree_attention_ragged_fp8(const sd_tree_attention_ragged_fp8_args* a, void* stream) {
     if (!a) return SD_ERR_INVALID;
-    const int32_t st = sd::ta_check_fp8(a);
-    if (st != SD_OK) return st;
     const sd::TaFp8 fs{a->k_scale, a->v_scale};
-    return ta_ragged_call(a, stream, &fs);
+    return sd::ta_ragged_entry(a, stream, &fs);
+}
+
+// ---- paged caches: the ragged call through a block table -------------------------------------------------
+extern "C" int32_t sd_tree_attention_paged(const sd_tree_attention_paged_args* a, void* stream) {
+    if (!a) return SD_ERR_INVALID;
+    sd::TaCall c{};
+    c.dtype = a->dtype; c.batch = a->batch; c.heads_q = a->heads_q; c.heads_kv = a->heads_kv; c.rows = a->rows;
+    c.head_dim = a->head_dim; c.scale = a->scale;
+    // the page strides in the place of the batch strides
+    c.t = sd::TaTensors{a->q, a->k, a->v, a->out, a->q_stride_b, a->q_stride_h, a->q_stride_r, a->k_stride_page, a->k_stride_h,
+                        a->k_stride_pos, a->v_stride_page, a->v_stride_h, a->v_stride_pos, a->out_stride_b, a->out_stride_r,
+                        a->out_stride_h};
+    c.kv_limit = a->kv_limit; c.win_bits = a->win_bits;
+    const sd::TaFp8 fs{a->k_scale, a->v_scale};
+    c.fp8 = a->kv_fp8 ? &fs : nullptr;
+    const sd::TaRagged rg{a->kv_len_dev, a->win_base_dev, a->kv_len_add, a->win_base_add, a->status_or, a->kv_cap, a->chunk_tiles};
+    const sd::TaPaged pg{a->block_table, a->block_table_stride_b, a->k_stride_page, a->v_stride_page, a->num_pages, 0};
+    c.ragged = &rg; c.paged = &pg; c.page_size = a->page_size; c.max_pages = a->max_pages;
+    c.workspace = a->workspace; c.workspace_bytes = a->workspace_bytes;
+    return sd::ta_run(c, stream);
 }

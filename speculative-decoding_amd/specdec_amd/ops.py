@@ -1320,65 +1320,68 @@ def tree_attention_chunks(batch: int, heads_kv: int, kv_cap: int, chunk_tiles: i
     return int(lib.sd_tree_attention_ragged_chunks(int(batch), int(heads_kv), int(kv_cap), int(chunk_tiles)))
 
 
-def _ta_tensors(a, q, k, v, out, kv_limit, win_bits, D):
-    """The tensor fields sd_tree_attention_args and sd_tree_attention_ragged_args share."""
+def _strides3(t, D):
+    """The strides of the first three dimensions of a [.., .., .., D] tensor.  A dimension of size 1 may carry any
+    stride: it is never stepped along, so it counts as 0 — but the innermost of the three (rows, positions or
+    heads of D elements) defaults to D, which the library's row-stride checks ask for."""
+    s0, s1, s2 = (t.stride(i) if t.shape[i] > 1 else 0 for i in (0, 1, 2))
+    return s0, s1, s2 or D
+
+
+def _seq_tensor(x, B: int, dev, who: str, what: str):
+    """x, an int64 device tensor [B] with one value per sequence."""
+    if not torch.is_tensor(x) or x.dtype != torch.int64 or x.shape != (B,) or x.device != dev or not x.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous int64 [{B}] on {dev}")
+    return x
+
+
+def _attn_tensors(who: str, q, k, v, out, block_table, kv_layout: str):
+    """The q / k / v / out checks tree_attention and prefill_attention share; returns ``out`` (made if None)."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f"{who}: q must be [B, Hq, R, D], k and v {kv_layout}")
+    B, Hq, R, D = q.shape
+    if k.shape != v.shape or (block_table is None and k.shape[0] != B) or k.shape[3] != D:
+        raise ValueError(f"{who}: k / v shapes {tuple(k.shape)}, {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    dev = q.device
+    if not q.is_cuda or k.device != dev or v.device != dev:
+        raise ValueError(f"{who}: q, k and v must be tensors of one device")
+    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
+        raise ValueError(f"{who}: the head dimension must have unit stride")
+    if out is None:
+        out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
+    elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
+        raise ValueError(f"{who}: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
+    return out
+
+
+def _attn_fill(a, q, k, v, out, scale, scales, paged: bool):
+    """The head of an attention argument struct: shape, dtype, scale, q / k / v / out with their strides (a pool's
+    page stride in the place of a cache's batch stride) and the scales of an FP8 cache."""
+    B, Hq, R, D = q.shape
+    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, k.shape[1], R, D, _DT[q.dtype]
+    a.scale = float(D) ** -0.5 if scale is None else float(scale)
     a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    # a dimension of size 1 may carry any stride: it is never stepped along
-    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.q_stride_r = a.q_stride_r or D
-    a.k_stride_b, a.k_stride_h, a.k_stride_pos = (k.stride(i) if k.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.k_stride_pos = a.k_stride_pos or D
-    a.v_stride_b, a.v_stride_h, a.v_stride_pos = (v.stride(i) if v.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.v_stride_pos = a.v_stride_pos or D
-    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.out_stride_h = a.out_stride_h or D
-    a.kv_limit, a.win_bits = kv_limit.data_ptr(), win_bits.data_ptr()
+    a.q_stride_b, a.q_stride_h, a.q_stride_r = _strides3(q, D)
+    a.out_stride_b, a.out_stride_r, a.out_stride_h = _strides3(out, D)
+    if paged:
+        a.k_stride_page, a.k_stride_h, a.k_stride_pos = _strides3(k, D)
+        a.v_stride_page, a.v_stride_h, a.v_stride_pos = _strides3(v, D)
+    else:
+        a.k_stride_b, a.k_stride_h, a.k_stride_pos = _strides3(k, D)
+        a.v_stride_b, a.v_stride_h, a.v_stride_pos = _strides3(v, D)
+    if scales is not None:
+        a.k_scale, a.v_scale = scales[0].data_ptr(), scales[1].data_ptr()
 
 
-def _ta_workspace(a, workspace, need, dev):
+def _ta_run(a, entry: str, workspace, need: int, dev):
+    """The workspace step and the call of every tree-attention branch; `need`: 0 when one partial is written directly."""
     if workspace is None and need:
         workspace = _workspace(need, dev)
     if workspace is not None:
         if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
             raise ValueError("tree_attention: workspace must be a contiguous uint8 tensor on the call's device")
         a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
-    return workspace
-
-
-def _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles, kv_len_add,
-                           win_base_add, status_or, workspace, scales=None):
-    """tree_attention with a device tensor for kv_len and / or win_base (sd_tree_attention_ragged; with
-    `scales`, the (k_scale, v_scale) of an FP8 cache, sd_tree_attention_ragged_fp8)."""
-    B, Hq, R, D = q.shape
-    Hkv, L, dev = k.shape[1], k.shape[2], q.device
-    kv_cap = L if kv_cap is None else int(kv_cap)
-    if not 1 <= kv_cap <= L:
-        raise ValueError(f"tree_attention: kv_cap {kv_cap} outside 1..{L}")
-    per_seq = []
-    for name, x, default in (("kv_len", kv_len, kv_cap), ("win_base", win_base, 0)):
-        if not torch.is_tensor(x):                     # a host value, expanded on the device: nothing is read back
-            x = torch.full((B,), default if x is None else int(x), dtype=torch.int64, device=dev)
-        elif x.dtype != torch.int64 or x.shape != (B,) or x.device != dev or not x.is_contiguous():
-            raise ValueError(f"tree_attention: a {name} tensor must be a contiguous int64 [{B}] on {dev}")
-        per_seq.append(x)
-    a = _lib.sd_tree_attention_ragged_args() if scales is None else _lib.sd_tree_attention_ragged_fp8_args()
-    call, name = (lib.sd_tree_attention_ragged, "sd_tree_attention_ragged") if scales is None else \
-        (lib.sd_tree_attention_ragged_fp8, "sd_tree_attention_ragged_fp8")
-    if scales is not None:
-        a.k_scale, a.v_scale = scales[0].data_ptr(), scales[1].data_ptr()
-    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
-    a.kv_cap, a.kv_alloc, a.chunk_tiles = kv_cap, L, int(chunk_tiles)
-    a.scale = float(D) ** -0.5 if scale is None else float(scale)
-    _ta_tensors(a, q, k, v, out, kv_limit, win_bits, D)
-    a.kv_len_dev, a.kv_len_add = per_seq[0].data_ptr(), int(kv_len_add)
-    a.win_base_dev, a.win_base_add = per_seq[1].data_ptr(), int(win_base_add)
-    a.status_or = _status_or_ptr(status_or, dev)
-    need = lib.sd_tree_attention_ragged_workspace_size(B, Hq, Hkv, R, D, kv_cap, int(chunk_tiles))
-    one = tree_attention_chunks(B, Hkv, kv_cap, chunk_tiles) <= 1
-    keep = _ta_workspace(a, workspace, 0 if one else need, dev)
-    _lib.check(call(C.byref(a), C.c_void_p(_stream_ptr(dev))), name)
-    del keep, per_seq
-    return out
+    _lib.check(getattr(lib, entry)(C.byref(a), C.c_void_p(_stream_ptr(dev))), entry)
 
 
 _PAGE_SIZES = (16, 32, 64, 128, 256)
@@ -1393,55 +1396,42 @@ def _block_table(bt, B: int, dev, who: str):
 
 def _pool_strides(t):
     """(page, head, slot) strides of a pool [num_pages, H, S, D]; a dimension of size 1 is never stepped along."""
-    sp, sh, ss = (t.stride(i) if t.shape[i] > 1 else 0 for i in (0, 1, 2))
-    return sp, sh, ss or t.shape[3]
+    return _strides3(t, t.shape[3])
 
 
-def _tree_attention_paged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles, kv_len_add,
-                          win_base_add, status_or, workspace, scales, block_table):
-    """tree_attention over paged pools k, v [num_pages, Hkv, S, D] (sd_tree_attention_paged)."""
+def _tree_attention_ragged(a, q, k, kv_cap, chunk_tiles, kv_len, win_base, kv_len_add, win_base_add, status_or, block_table):
+    """What the ragged entries add to the struct's head (sd_tree_attention_ragged, sd_tree_attention_ragged_fp8 and, with
+    a block_table over pools k, v [num_pages, Hkv, S, D], sd_tree_attention_paged); returns the workspace bytes and
+    the per-sequence tensors to keep alive."""
     B, Hq, R, D = q.shape
-    num_pages, Hkv, S = k.shape[0], k.shape[1], k.shape[2]
-    dev = q.device
-    if S not in _PAGE_SIZES:
-        raise ValueError(f"tree_attention: page size {S} is not one of {_PAGE_SIZES}")
-    max_pages, bt_stride = _block_table(block_table, B, dev, "tree_attention")
-    limit = min(max_pages * S, _lib.SD_TREE_ATTN_MAX_KV)
-    kv_cap = limit if kv_cap is None else int(kv_cap)
-    if not 1 <= kv_cap <= limit:
-        raise ValueError(f"tree_attention: kv_cap {kv_cap} outside 1..{limit}")
-    if not torch.is_tensor(kv_len) or kv_len.dtype != torch.int64 or kv_len.shape != (B,) or kv_len.device != dev \
-            or not kv_len.is_contiguous():
-        raise ValueError(f"tree_attention: with a block_table, kv_len must be a contiguous int64 [{B}] on {dev}")
-    if not torch.is_tensor(win_base):
-        win_base = torch.full((B,), int(win_base), dtype=torch.int64, device=dev)
-    elif win_base.dtype != torch.int64 or win_base.shape != (B,) or win_base.device != dev or not win_base.is_contiguous():
-        raise ValueError(f"tree_attention: a win_base tensor must be a contiguous int64 [{B}] on {dev}")
-    a = _lib.sd_tree_attention_paged_args()
-    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
-    a.kv_cap, a.chunk_tiles = kv_cap, int(chunk_tiles)
-    a.page_size, a.num_pages, a.max_pages, a.kv_fp8 = S, num_pages, max_pages, int(scales is not None)
-    a.scale = float(D) ** -0.5 if scale is None else float(scale)
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.q_stride_r = a.q_stride_r or D
-    a.k_stride_page, a.k_stride_h, a.k_stride_pos = _pool_strides(k)
-    a.v_stride_page, a.v_stride_h, a.v_stride_pos = _pool_strides(v)
-    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.out_stride_h = a.out_stride_h or D
-    a.kv_limit, a.win_bits = kv_limit.data_ptr(), win_bits.data_ptr()
-    a.kv_len_dev, a.kv_len_add = kv_len.data_ptr(), int(kv_len_add)
-    a.win_base_dev, a.win_base_add = win_base.data_ptr(), int(win_base_add)
-    a.block_table, a.block_table_stride_b = block_table.data_ptr(), bt_stride
-    if scales is not None:
-        a.k_scale, a.v_scale = scales[0].data_ptr(), scales[1].data_ptr()
+    Hkv, L, dev = k.shape[1], k.shape[2], q.device
+    if block_table is not None:
+        if L not in _PAGE_SIZES:
+            raise ValueError(f"tree_attention: page size {L} is not one of {_PAGE_SIZES}")
+        a.max_pages, a.block_table_stride_b = _block_table(block_table, B, dev, "tree_attention")
+        a.page_size, a.num_pages, a.block_table = L, k.shape[0], block_table.data_ptr()
+        limit = min(a.max_pages * L, _lib.SD_TREE_ATTN_MAX_KV)
+    else:
+        limit = a.kv_alloc = L
+    a.kv_cap = limit if kv_cap is None else int(kv_cap)
+    if not 1 <= a.kv_cap <= limit:
+        raise ValueError(f"tree_attention: kv_cap {a.kv_cap} outside 1..{limit}")
+    if block_table is not None:                        # the lengths of a paged batch have no host default
+        _seq_tensor(kv_len, B, dev, "tree_attention", "with a block_table, kv_len")
+    per_seq = []
+    for name, x, default in (("kv_len", kv_len, a.kv_cap), ("win_base", win_base, 0)):
+        if torch.is_tensor(x):
+            _seq_tensor(x, B, dev, "tree_attention", f"a {name} tensor")
+        else:                                          # a host value, expanded on the device: nothing is read back
+            x = torch.full((B,), default if x is None else int(x), dtype=torch.int64, device=dev)
+        per_seq.append(x)
+    a.chunk_tiles = int(chunk_tiles)
+    a.kv_len_dev, a.kv_len_add = per_seq[0].data_ptr(), int(kv_len_add)
+    a.win_base_dev, a.win_base_add = per_seq[1].data_ptr(), int(win_base_add)
     a.status_or = _status_or_ptr(status_or, dev)
-    need = lib.sd_tree_attention_ragged_workspace_size(B, Hq, Hkv, R, D, kv_cap, int(chunk_tiles))
-    one = tree_attention_chunks(B, Hkv, kv_cap, chunk_tiles) <= 1
-    keep = _ta_workspace(a, workspace, 0 if one else need, dev)
-    _lib.check(lib.sd_tree_attention_paged(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention_paged")
-    del keep, win_base
-    return out
+    if tree_attention_chunks(B, Hkv, a.kv_cap, chunk_tiles) <= 1:
+        return 0, per_seq
+    return lib.sd_tree_attention_ragged_workspace_size(B, Hq, Hkv, R, D, a.kv_cap, int(chunk_tiles)), per_seq
 
 
 def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: torch.Tensor, win_bits: torch.Tensor,
@@ -1488,15 +1478,9 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     ``ceil(len_b / S)`` are never read.  A page id outside [0, num_pages) is never used as an address: its
     keys count as zeros, SD_ROW_INVALID_DIST is ORed into ``status_or``, that sequence's output is finite and
     meaningless and the other sequences are untouched.  ``kv_store_paged`` writes such pools."""
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("tree_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D]")
+    out = _attn_tensors("tree_attention", q, k, v, out, block_table, "[B, Hkv, L, D]")
     B, Hq, R, D = q.shape
-    if k.shape != v.shape or (block_table is None and k.shape[0] != B) or k.shape[3] != D:
-        raise ValueError(f"tree_attention: k / v shapes {tuple(k.shape)}, {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    Hkv, L = k.shape[1], k.shape[2]
-    dev = q.device
-    if not q.is_cuda or k.device != dev or v.device != dev:
-        raise ValueError("tree_attention: q, k and v must be tensors of one device")
+    Hkv, L, dev = k.shape[1], k.shape[2], q.device
     scales = None
     if k.dtype == torch.float8_e4m3fn and v.dtype == torch.float8_e4m3fn and q.dtype in _DT:
         if k_scale is None or v_scale is None:
@@ -1509,9 +1493,8 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
         raise ValueError("tree_attention: k_scale and v_scale go with float8_e4m3fn k and v")
     elif q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError("tree_attention: q, k and v must share one floating dtype (or k, v float8_e4m3fn with scales)")
-    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
-        raise ValueError("tree_attention: the head dimension must have unit stride")
-    ragged = torch.is_tensor(kv_len) or torch.is_tensor(win_base) or block_table is not None
+    paged = block_table is not None
+    ragged = torch.is_tensor(kv_len) or torch.is_tensor(win_base) or paged
     if not ragged:
         if kv_cap is not None or chunk_tiles or kv_len_add or win_base_add or status_or is not None:
             raise ValueError("tree_attention: kv_cap, chunk_tiles, the addends and status_or go with a kv_len or "
@@ -1524,40 +1507,30 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_limit: 
     if win_bits.dtype not in (torch.int64, torch.uint64) or win_bits.shape != (B, R) or not win_bits.is_contiguous() \
             or win_bits.device != dev:
         raise ValueError(f"tree_attention: win_bits must be a contiguous int64 / uint64 [{B}, {R}] on {dev}")
-    if out is None:
-        out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
-    elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
-        raise ValueError(f"tree_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
-    if block_table is not None:
-        return _tree_attention_paged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles,
-                                     kv_len_add, win_base_add, status_or, workspace, scales, block_table)
+    entry = "sd_tree_attention" + ("_paged" if paged else ("_ragged" if ragged else "") + ("_fp8" if scales else ""))
+    a = getattr(_lib, entry + "_args")()
+    _attn_fill(a, q, k, v, out, scale, scales, paged)
+    a.kv_limit, a.win_bits = kv_limit.data_ptr(), win_bits.data_ptr()
+    keep = None
+    if paged:
+        a.kv_fp8 = int(scales is not None)              # one paged entry for both kinds of pool
     if ragged:
-        return _tree_attention_ragged(q, k, v, kv_limit, win_bits, win_base, kv_len, out, scale, kv_cap, chunk_tiles,
-                                      kv_len_add, win_base_add, status_or, workspace, scales)
-    a = _lib.sd_tree_attention_args() if scales is None else _lib.sd_tree_attention_fp8_args()
-    if scales is not None:
-        a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
-    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype = B, Hq, Hkv, R, D, _DT[q.dtype]
-    a.kv_len, a.kv_alloc, a.splits = kv_len, L, int(splits)
-    a.scale = float(D) ** -0.5 if scale is None else float(scale)
-    _ta_tensors(a, q, k, v, out, kv_limit, win_bits, D)
-    a.win_base = int(win_base)
-    need = lib.sd_tree_attention_workspace_size(B, Hq, Hkv, R, D, kv_len, int(splits))
-    workspace = _ta_workspace(a, workspace, need if tree_attention_splits(B, Hkv, kv_len, splits) > 1 else 0, dev)
-    if scales is None:
-        _lib.check(lib.sd_tree_attention(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention")
+        need, keep = _tree_attention_ragged(a, q, k, kv_cap, chunk_tiles, kv_len, win_base, kv_len_add, win_base_add,
+                                            status_or, block_table)
     else:
-        _lib.check(lib.sd_tree_attention_fp8(C.byref(a), C.c_void_p(_stream_ptr(dev))), "sd_tree_attention_fp8")
+        a.kv_len, a.kv_alloc, a.splits, a.win_base = kv_len, L, int(splits), int(win_base)
+        one = tree_attention_splits(B, Hkv, kv_len, splits) <= 1
+        need = 0 if one else lib.sd_tree_attention_workspace_size(B, Hq, Hkv, R, D, kv_len, int(splits))
+    _ta_run(a, entry, workspace, need, dev)
+    del keep
     return out
 
 
-def _per_sequence(x, B: int, dev, who: str):
+def _per_sequence(x, B: int, dev, name: str):
     """(device pointer or None, host addend, tensor kept alive) of an int or an int64 device tensor [B]."""
     if not torch.is_tensor(x):
         return None, int(x), None
-    if x.dtype != torch.int64 or x.shape != (B,) or x.device != dev or not x.is_contiguous():
-        raise ValueError(f"prefill_attention: a {who} tensor must be a contiguous int64 [{B}] on {dev}")
-    return x.data_ptr(), 0, x
+    return _seq_tensor(x, B, dev, "prefill_attention", f"a {name} tensor").data_ptr(), 0, x
 
 
 def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_len, *, rows=None,
@@ -1581,14 +1554,9 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_len,
     [B, R, Hq, D]; padding rows are zeros.  No key at or beyond kv_len_b is read, no workspace is used and the
     call is capturable.  A page id outside [0, num_pages) is never used as an address: its keys count as zeros
     and SD_ROW_INVALID_DIST is ORed."""
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("prefill_attention: q must be [B, Hq, R, D], k and v [B, Hkv, L, D] (or pools [P, Hkv, S, D])")
+    out = _attn_tensors("prefill_attention", q, k, v, out, block_table, "[B, Hkv, L, D] (or pools [P, Hkv, S, D])")
     B, Hq, R, D = q.shape
-    if k.shape != v.shape or (block_table is None and k.shape[0] != B) or k.shape[3] != D:
-        raise ValueError(f"prefill_attention: k / v shapes {tuple(k.shape)}, {tuple(v.shape)} do not match q {tuple(q.shape)}")
     Hkv, L, dev = k.shape[1], k.shape[2], q.device
-    if not q.is_cuda or k.device != dev or v.device != dev:
-        raise ValueError("prefill_attention: q, k and v must be tensors of one device")
     fp8 = k.dtype == torch.float8_e4m3fn and v.dtype == torch.float8_e4m3fn
     if q.dtype not in _DT or q.dtype == torch.float32:
         raise ValueError("prefill_attention: q must be bfloat16 or float16")
@@ -1598,39 +1566,20 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_len,
                 raise ValueError(f"prefill_attention: float8_e4m3fn k / v need contiguous float32 [{Hkv}] k_scale and v_scale on {dev}")
     elif k_scale is not None or v_scale is not None or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError("prefill_attention: k and v must have q's dtype, or be float8_e4m3fn with k_scale and v_scale")
-    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
-        raise ValueError("prefill_attention: the head dimension must have unit stride")
-    if out is None:
-        out = torch.empty(B, R, Hq, D, dtype=q.dtype, device=dev)
-    elif out.shape != (B, R, Hq, D) or out.dtype != q.dtype or out.device != dev or out.stride(3) != 1:
-        raise ValueError(f"prefill_attention: out must be [{B}, {R}, {Hq}, {D}] {q.dtype} on {dev}, unit stride along D")
     a = _lib.sd_prefill_attention_args()
-    a.batch, a.heads_q, a.heads_kv, a.rows, a.head_dim, a.dtype, a.kv_fp8 = B, Hq, Hkv, R, D, _DT[q.dtype], int(fp8)
+    _attn_fill(a, q, k, v, out, scale, (k_scale, v_scale) if fp8 else None, block_table is not None)
+    a.kv_fp8 = int(fp8)
     if block_table is not None:
         if L not in _PAGE_SIZES:
             raise ValueError(f"prefill_attention: page size {L} is not one of {_PAGE_SIZES}")
         a.max_pages, a.block_table_stride_b = _block_table(block_table, B, dev, "prefill_attention")
         a.page_size, a.num_pages, a.block_table = L, k.shape[0], block_table.data_ptr()
         limit = min(a.max_pages * L, _lib.SD_TREE_ATTN_MAX_KV)
-        a.k_stride_page, a.k_stride_h, a.k_stride_pos = _pool_strides(k)
-        a.v_stride_page, a.v_stride_h, a.v_stride_pos = _pool_strides(v)
     else:
         limit = a.kv_alloc = L
-        a.k_stride_b, a.k_stride_h, a.k_stride_pos = (k.stride(i) if k.shape[i] > 1 else 0 for i in (0, 1, 2))
-        a.v_stride_b, a.v_stride_h, a.v_stride_pos = (v.stride(i) if v.shape[i] > 1 else 0 for i in (0, 1, 2))
-        a.k_stride_pos, a.v_stride_pos = a.k_stride_pos or D, a.v_stride_pos or D
     a.kv_cap = limit if kv_cap is None else int(kv_cap)
     if not 1 <= a.kv_cap <= limit:
         raise ValueError(f"prefill_attention: kv_cap {a.kv_cap} outside 1..{limit}")
-    a.scale = float(D) ** -0.5 if scale is None else float(scale)
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    # a dimension of size 1 may carry any stride: it is never stepped along
-    a.q_stride_b, a.q_stride_h, a.q_stride_r = (q.stride(i) if q.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.q_stride_r = a.q_stride_r or D
-    a.out_stride_b, a.out_stride_r, a.out_stride_h = (out.stride(i) if out.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.out_stride_h = a.out_stride_h or D
-    if fp8:
-        a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
     a.kv_len_dev, len_add, keep_len = _per_sequence(kv_len, B, dev, "kv_len")
     a.rows_dev, n_add, keep_rows = _per_sequence(R if rows is None else rows, B, dev, "rows")
     a.kv_len_add, a.rows_add = len_add + int(kv_len_add), n_add + int(rows_add)
@@ -1674,13 +1623,10 @@ def kv_store_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor
     a = _lib.sd_kv_store_fp8_args()
     a.batch, a.heads, a.rows, a.head_dim, a.dtype = B, H, R, D, _DT[k_new.dtype]
     a.k_new, a.v_new, a.k_cache, a.v_cache = k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
-    # a dimension of size 1 may carry any stride: it is never stepped along
-    a.kn_stride_b, a.kn_stride_h, a.kn_stride_r = (k_new.stride(i) if k_new.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.vn_stride_b, a.vn_stride_h, a.vn_stride_r = (v_new.stride(i) if v_new.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.kn_stride_r, a.vn_stride_r = a.kn_stride_r or D, a.vn_stride_r or D
-    a.kc_stride_b, a.kc_stride_h, a.kc_stride_pos = (k_cache.stride(i) if k_cache.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.vc_stride_b, a.vc_stride_h, a.vc_stride_pos = (v_cache.stride(i) if v_cache.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.kc_stride_pos, a.vc_stride_pos = a.kc_stride_pos or D, a.vc_stride_pos or D
+    a.kn_stride_b, a.kn_stride_h, a.kn_stride_r = _strides3(k_new, D)
+    a.vn_stride_b, a.vn_stride_h, a.vn_stride_r = _strides3(v_new, D)
+    a.kc_stride_b, a.kc_stride_h, a.kc_stride_pos = _strides3(k_cache, D)
+    a.vc_stride_b, a.vc_stride_h, a.vc_stride_pos = _strides3(v_cache, D)
     a.num_positions, a.pos = k_cache.shape[2], int(pos)
     if pos_dev is not None:
         a.pos_dev, a.pos_per_seq = pos_dev.data_ptr(), int(B > 1 and pos_dev.numel() == B)
@@ -1727,19 +1673,17 @@ def kv_store_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
                 raise ValueError(f"kv_store_paged: float8_e4m3fn pools need contiguous float32 [{H}] k_scale and v_scale on {dev}")
     elif k_scale is not None or v_scale is not None:
         raise ValueError("kv_store_paged: k_scale and v_scale go with float8_e4m3fn pools")
-    if pos_dev.dtype != torch.int64 or pos_dev.shape != (B,) or pos_dev.device != dev or not pos_dev.is_contiguous():
-        raise ValueError(f"kv_store_paged: pos_dev must be a contiguous int64 [{B}] on {dev}")
+    _seq_tensor(pos_dev, B, dev, "kv_store_paged", "pos_dev")
     max_pages, bt_stride = _block_table(block_table, B, dev, "kv_store_paged")
     es = k_cache.element_size()
     a = _lib.sd_kv_store_paged_args()
     a.batch, a.heads, a.rows, a.head_dim, a.dtype, a.cache_fp8 = B, H, R, D, _DT[k_new.dtype], int(fp8)
     a.page_size, a.num_pages, a.max_pages = S, num_pages, max_pages
     a.k_new, a.v_new, a.k_cache, a.v_cache = k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
-    a.kn_stride_b, a.kn_stride_h, a.kn_stride_r = (k_new.stride(i) if k_new.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.vn_stride_b, a.vn_stride_h, a.vn_stride_r = (v_new.stride(i) if v_new.shape[i] > 1 else 0 for i in (0, 1, 2))
-    a.kn_stride_r, a.vn_stride_r = a.kn_stride_r or D, a.vn_stride_r or D
-    a.kc_stride_page, a.kc_stride_h, a.kc_stride_pos = (x * es for x in _pool_strides(k_cache))
-    a.vc_stride_page, a.vc_stride_h, a.vc_stride_pos = (x * es for x in _pool_strides(v_cache))
+    a.kn_stride_b, a.kn_stride_h, a.kn_stride_r = _strides3(k_new, D)
+    a.vn_stride_b, a.vn_stride_h, a.vn_stride_r = _strides3(v_new, D)
+    a.kc_stride_page, a.kc_stride_h, a.kc_stride_pos = (x * es for x in _strides3(k_cache, D))
+    a.vc_stride_page, a.vc_stride_h, a.vc_stride_pos = (x * es for x in _strides3(v_cache, D))
     a.pos, a.pos_dev = int(pos), pos_dev.data_ptr()
     a.block_table, a.block_table_stride_b = block_table.data_ptr(), bt_stride
     if fp8:

@@ -5,6 +5,8 @@ and every slot at or beyond len_b (and every position no row sees) holds NaN (FP
 at or beyond ceil(len_b / S) are -1.  Reference: fp64 attention over the visible keys.
 
 Tolerance (unchanged): 2 eps max|V| over the visible keys; FP8: V = v_scale * e4m3 value."""
+import functools
+
 import pytest
 import torch
 
@@ -168,6 +170,69 @@ def _gather(pool, table, S):
     """The logical cache [B, H, max_pages * S, D] a table describes (entries -1 read page 0: never compared)."""
     pages = _bytes(pool)[table.clamp(min=0).long()]           # [B, max_pages, H, S, D], as bytes: any dtype
     return pages.permute(0, 2, 1, 3, 4).reshape(table.shape[0], pool.shape[1], -1, pool.shape[3]).view(pool.dtype)
+
+
+# A chunk of more than 1024 pages: a workgroup stages the first 1024 ids of its chunk and reads the ids behind them
+# from the table as it goes.  The smallest such chunk: S = 16 and 260 tiles, 1040 pages.
+LONG_TILES, LONG_S = 260, 16
+LONG_KEYS = LONG_TILES * 64
+
+
+@functools.lru_cache(maxsize=None)
+def _long_case(fp8, chunks):
+    """One case per (pool type, chunk count), built and referenced once: sequence 0 ends five keys into page 1024 of
+    its last chunk, sequence 1 at kv_cap (its window lies on the pages 1029..1033 of that chunk), sequence 2 stays
+    below 1024 pages."""
+    c0, cap = (chunks - 1) * LONG_KEYS, chunks * LONG_KEYS
+    lens, bases = (c0 + 1024 * LONG_S + 5, cap, 1000), (c0 + 1024 * LONG_S - 4, c0 + 1029 * LONG_S + 6, 900)
+    dtype = HF if fp8 else BF
+    q, k, v, limit, bits, visible = _case(dtype, 64, 2, 1, 3, lens, cap, bases, seed=9)
+    assert visible[0, :, c0 + 1024 * LONG_S:].any() and visible[1, :, c0 + 1030 * LONG_S:c0 + 1031 * LONG_S].any()
+    scales, kr, vr = {}, k, v
+    if fp8:
+        k, v, ks, vs, kr, vr = _quantised(k, v, 1)
+        scales = dict(k_scale=ks.to(DEV), v_scale=vs.to(DEV))
+    want = _reference(q, kr, vr, visible, 64 ** -0.5)
+    seen = visible.any(1)[:, None, :, None].expand(3, 1, k.shape[2], 64)
+    tol = 2 * torch.finfo(dtype).eps * float(vr[seen].double().abs().max())
+    _, perm, num_pages = _places(3, -(-k.shape[2] // LONG_S), seed=chunks)
+    (kp, table), (vp, _) = (_pool(t, lens, LONG_S, perm, num_pages) for t in (k, v))
+    args = (q.to(DEV), _dev(kp), _dev(vp), limit.to(DEV), bits.to(DEV), _long(bases))
+    kw = dict(kv_len=_long(lens), kv_cap=cap, chunk_tiles=LONG_TILES, **scales)
+    return args, kw, table, num_pages, want, tol
+
+
+@pytest.mark.parametrize("chunks", [1, 2], ids=["direct", "chunks2"])
+@pytest.mark.parametrize("fp8", [False, True], ids=["kv16", "fp8"])
+def test_page_ids_behind_the_staged_ones_are_read_from_the_table(fp8, chunks):
+    from specdec_amd import ops
+    args, kw, table, _, want, tol = _long_case(fp8, chunks)
+    assert ops.tree_attention_chunks(3, 1, kw["kv_cap"], LONG_TILES) == chunks
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    out = ops.tree_attention(*args, block_table=table.to(DEV), status_or=status, **kw)
+    assert int(status.item()) == 0
+    got = out.cpu().double()
+    err = float((got - want).abs().max())
+    print(f"[tree-attn-paged] long chunk fp8={fp8} chunks={chunks}: max err {err:.3g}, tol {tol:.3g}")
+    assert torch.isfinite(got).all() and err <= tol
+    # the contiguous ragged call on the cache the table describes: the same arithmetic
+    q, kp, vp, limit, bits, base = args
+    flat = ops.tree_attention(q, _gather(kp, table.to(DEV), LONG_S), _gather(vp, table.to(DEV), LONG_S), limit, bits, base, **kw)
+    assert torch.equal(_bytes(out), _bytes(flat))
+
+
+@pytest.mark.parametrize("fp8", [False, True], ids=["kv16", "fp8"])
+def test_a_page_id_out_of_range_behind_the_staged_ones_is_refused(fp8):
+    from specdec_amd import ops
+    args, kw, table, num_pages, _, _ = _long_case(fp8, 1)
+    clean = ops.tree_attention(*args, block_table=table.to(DEV), **kw)
+    bad = table.clone()
+    bad[1, 1030] = num_pages                                  # keys 16480..16495 of sequence 1: inside its window
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    out = ops.tree_attention(*args, block_table=bad.to(DEV), status_or=status, **kw)
+    assert int(status.item()) == BAD
+    assert torch.isfinite(out[1].float()).all()
+    assert torch.equal(_bytes(out[[0, 2]]), _bytes(clean[[0, 2]]))
 
 
 @pytest.mark.parametrize("fp8", [False, True], ids=["kv16", "fp8"])
